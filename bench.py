@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- IQ Msamples/s demodulated (SC16Q11 -> bits/messages) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload capture|batch|sharded]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload capture|batch|sharded] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,13 +25,28 @@ independent captures of 2^24 samples in one batched call; `sharded` = one
 capture cut into WORLD_SIZE shards, halo + carried state machine state
 exchanged over torch.distributed (nccl = RCCL on the GPU box).
 
-One JSON line is printed by rank 0, with `roofline` for the dominant kernel
-(fused FIR front end, timed with HIP events on its own stream inside the
-library), `single_context` (the same steps strictly one after the other),
-`worst_case` (every window filtered: no quiet shortcut) and, at N = 1,
-`cpu_baseline`: the CPU oracle (plain-C restatement of the reference path, 1
-thread like the reference) timed on this host on a bounded slice of the same
-capture -- also used as a parity check -- and the same code on all host cores.
+One JSON line is printed by rank 0, with `ms_per_step` (one timed step) and
+`roofline` for the dominant kernel (fused FIR front end, timed with HIP events
+on its own stream inside the library during the timed steps).  A plain run
+does nothing else: set up, warm up, time the K steps, print the line.
+
+`--full` adds what takes runs of its own: the share of windows that took the
+quiet shortcut (`quiet_window_fraction`, `roofline.fir_tflops`),
+`single_context` (the same steps strictly one after the other), `worst_case`
+(every window filtered: no quiet shortcut), `fallback_path`, the other
+BASELINE.json `configs`, the sharded workload's check against the whole
+capture and, at N = 1, `cpu_baseline`: the CPU oracle (plain-C restatement of
+the reference path, 1 thread like the reference) timed on this host on a
+bounded slice of the same capture -- also used as a parity check -- and the
+same code on all host cores.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(float64 / float32): the decoded messages (`msg_samples`, `msg_captures`,
+`payloads`), the error positions (`err_samples`), the edge list
+(`edges`, `edge_counts` per capture; a fixed, seeded sample of
+`EDGE_DUMP_MAX` edges when there are more) and `counts` (input / decimated
+samples, edges, messages, errors).  The inputs are seeded, so two builds given
+the same arguments can be compared file for file.
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (fresh
 processes, before anything touches a GPU) and fails if the box has fewer
@@ -59,10 +75,39 @@ FP32_PEAK_TFLOPS = 157.3            # vector fp32 peak
 BYTES_PER_SAMPLE = 4.125            # 4 B read + 1/8 B written per decimated sample (D = 1)
 FIR_FLOP_PER_SAMPLE = 128.0         # 32 real taps x (re, im) x (mul + add)
 CPU_SLICE = 1 << 28                 # 1 GiB slice for the CPU baseline: ~5 s of one host core
+EDGE_DUMP_MAX = 1 << 22             # --dump-outputs: at most 4 Mi edges (32 MB as float64)
 
 
 def golden(kind, name):
     return os.path.join(ROOT, "tests", "golden", kind, name + ".json")
+
+
+def dump_outputs(dirname, res, rx, ncaps):
+    """--dump-outputs: what the last timed step handed its caller, as float64 / float32 .npy files (<= 64 MB)."""
+    import numpy as np
+    edges = [rx.edges(c) for c in range(ncaps)]
+    all_edges = np.concatenate(edges) if edges else np.zeros(0, dtype=np.uint64)
+    if all_edges.size > EDGE_DUMP_MAX:
+        rng = np.random.default_rng(SEED_BASE)
+        all_edges = all_edges[np.sort(rng.choice(all_edges.size, EDGE_DUMP_MAX, replace=False))]
+    errs, _ = rx.errors()
+    st = res.stats
+    arrays = {
+        "msg_samples": res.msg_samples.astype(np.float64),
+        "msg_captures": res.captures.astype(np.float64),
+        "payloads": res.payloads.astype(np.float32),
+        "err_samples": errs.astype(np.float64),
+        "edges": all_edges.astype(np.float64),
+        "edge_counts": np.array([e.size for e in edges], dtype=np.float64),
+        "counts": np.array([st["input_samples"], st["decimated_samples"], st["num_edges"], st["num_messages"],
+                            st["num_errors"]], dtype=np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than 64 MB" % total)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -96,8 +141,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=("capture", "batch", "sharded"), default="capture")
     ap.add_argument("--samples", type=int, default=0, help="samples per capture / per shard (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub-records", action="store_true", help="skip the single_context / worst_case runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: quiet-window share, single_context, "
+                         "worst_case, fallback_path, configs, the sharded check, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-sub-records", action="store_true",
+                    help="with --full: skip the single_context / worst_case / fallback_path / configs runs")
     ap.add_argument("--exact", action="store_true", help="unfused reference-order FIR everywhere")
     ap.add_argument("--filter", default="fs32_fs4", help=argparse.SUPPRESS)   # experiments only
     ap.add_argument("--contexts", type=int, default=3,
@@ -110,6 +161,8 @@ def main():
     ap.add_argument("--allow-shared-gpu", action="store_true",
                     help="rehearsal: let --gpus N start N ranks on a box with fewer GPUs (the line says so; never a scaling number)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -289,13 +342,16 @@ def main():
             res = one_step()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
-        # ---- checker (untimed): the shards' messages, gathered in capture order, against the whole capture --------
-        allmsgs = res
-        if dist is not None:
-            from ookiedokie_amd.distributed import gather_messages
-            allmsgs = gather_messages(res)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, res, rx, 1)
+        # ---- checker (untimed, --full): the shards' messages, gathered in capture order, against the whole capture --
         check = {}
-        if rank == 0:
+        if args.full:
+            allmsgs = res
+            if dist is not None:
+                from ookiedokie_amd.distributed import gather_messages
+                allmsgs = gather_messages(res)
+        if rank == 0 and args.full:
             ms = np.asarray(allmsgs.msg_samples, dtype=np.uint64)
             pays = np.asarray(allmsgs.payloads)
             check["messages"] = int(ms.size)
@@ -377,16 +433,19 @@ def main():
         elapsed, fir_ms, dev_ms, nlaunch = timed_steps(handles, ptrs, ncaps, n, stride, args.steps)
         elapsed = max_over_ranks(elapsed)
         res = rxs[(args.steps - 1) % nctx].result()
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, res, rxs[(args.steps - 1) % nctx], ncaps)
+        sub_records = args.full and not args.no_sub_records
 
-        quiet_frac = 0.0
+        quiet_frac = 0.0 if args.no_quiet_skip else None        # None: not measured (plain run)
         single = worst = None
-        if rank == 0 and not args.no_quiet_skip:
+        if rank == 0 and args.full and not args.no_quiet_skip:
             # untimed diagnostic pass: how many 512-output windows took the quiet shortcut
             cnt = receiver(n, ncaps, count_quiet=True, **kw)
             st = cnt.rx_device(bufs[0].data_ptr(), n, num_captures=ncaps, stride=stride).stats
             quiet_frac = st["quiet_waves"] / max(1, st["total_waves"])
             cnt.close()
-        if rank == 0 and world == 1 and not args.no_sub_records:
+        if rank == 0 and world == 1 and sub_records:
             # ---- the same steps strictly one after the other (one context) ---------------------------------
             k1 = max(3, min(args.steps, 20))
             timed_steps(handles[:1], ptrs[:1], ncaps, n, stride, 2)        # (untimed: the mode's own warm-up)
@@ -410,7 +469,7 @@ def main():
                          "fir_tflops": round(tf, 2), "frac_of_fp32_valu_peak": round(tf / FP32_PEAK_TFLOPS, 4)}
                 wrx.close()
         fallback = None
-        if rank == 0 and world == 1 and not args.no_sub_records and ncaps == 1:
+        if rank == 0 and world == 1 and sub_records and ncaps == 1:
             # ---- what a capture costs when the scan form refuses it: the round form, on a 1 GiB slice ---------
             m = min(n, 1 << 28)
             frx = receiver(m, fsm_rounds=True)
@@ -430,7 +489,7 @@ def main():
             frx.close()
             srx.close()
         configs = None
-        if (rank == 0 and world == 1 and not args.no_sub_records and args.workload == "capture" and n == N_SAMPLES
+        if (rank == 0 and world == 1 and sub_records and args.workload == "capture" and n == N_SAMPLES
                 and args.filter == "fs32_fs4" and not args.no_quiet_skip and not args.exact):
             # ---- the other single-GPU configurations of BASELINE.json, each through the same timed loop --------
             configs = {}
@@ -480,7 +539,8 @@ def main():
             fir_avg_ms = float(np.mean(fir_ms))
             achieved_gbs = BYTES_PER_SAMPLE * n * ncaps / (fir_avg_ms * 1e-3) / 1e9
             # flops actually executed: quiet windows skip the filter altogether
-            fir_tflops = FIR_FLOP_PER_SAMPLE * n * ncaps * (1.0 - quiet_frac) / (fir_avg_ms * 1e-3) / 1e12
+            fir_tflops = (FIR_FLOP_PER_SAMPLE * n * ncaps * (1.0 - quiet_frac) / (fir_avg_ms * 1e-3) / 1e12
+                          if quiet_frac is not None else None)
             traffic = None
             prof = os.path.join(ROOT, "profiles", "traffic.json")
             if os.path.exists(prof) and args.workload == "capture":
@@ -525,7 +585,7 @@ def main():
                     "contexts_in_flight": nctx,
                     "captures_resident": nctx,
                     "quiet_shortcut": not args.no_quiet_skip,
-                    "quiet_window_fraction": round(quiet_frac, 4),
+                    "quiet_window_fraction": round(quiet_frac, 4) if quiet_frac is not None else None,
                 },
                 "roofline": {
                     # the front end of a step goes out as `launches_per_step` grid launches of the same
@@ -546,8 +606,8 @@ def main():
                     "front_end_ms_per_step": round(fir_avg_ms, 4),
                     # the 32-tap FIR sits above the fp32 ridge (SURVEY.md hard part 1); flops
                     # of the windows that really ran the filter:
-                    "fir_tflops": round(fir_tflops, 2),
-                    "frac_of_fp32_valu_peak": round(fir_tflops / FP32_PEAK_TFLOPS, 4),
+                    "fir_tflops": round(fir_tflops, 2) if fir_tflops is not None else None,
+                    "frac_of_fp32_valu_peak": round(fir_tflops / FP32_PEAK_TFLOPS, 4) if fir_tflops is not None else None,
                 },
                 # first kernel start -> last kernel end of one capture (its latency on the device;
                 # with several contexts in flight consecutive captures overlap, so ms_per_step is smaller)
@@ -558,8 +618,8 @@ def main():
                 "configs": configs,
             }
 
-        # ---- CPU baseline: the oracle on this host's cores (rank 0, N = 1 only) -------------
-        if rank == 0 and world == 1 and args.workload == "capture" and not args.no_cpu_baseline:
+        # ---- CPU baseline (--full): the oracle on this host's cores (rank 0, N = 1 only) -------------
+        if rank == 0 and world == 1 and args.workload == "capture" and args.full and not args.no_cpu_baseline:
             import oracle as O
             O.build()
             m = min(CPU_SLICE, n)

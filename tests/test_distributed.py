@@ -274,13 +274,13 @@ def _bench_line(args, timeout=600):
 
 @pytest.mark.gpu
 def test_bench_two_ranks_sharded_on_one_gpu():
-    """`bench.py --gpus 2 --workload sharded`: two ranks (gloo: they share this box's GPU) cut ONE capture in two,
-    exchange halo + carried state, and the line's own check says the sharded result equals the whole capture's."""
+    """`bench.py --gpus 2 --workload sharded --full`: two ranks (gloo: they share this box's GPU) cut ONE capture in
+    two, exchange halo + carried state, and the line's own check says the sharded result equals the whole capture's."""
     import torch
     if torch.cuda.device_count() >= 2:
         pytest.skip("rehearsal of the two-rank path on ONE device")
     d = _bench_line(["--gpus", "2", "--workload", "sharded", "--backend", "gloo", "--samples", "16777216",
-                     "--steps", "2", "--warmup", "1", "--allow-shared-gpu"])
+                     "--steps", "2", "--warmup", "1", "--allow-shared-gpu", "--full"])
     assert d["n_gpus"] == 2 and d["config"]["backend"] == "gloo" and d["config"]["shards"] == 2
     assert d["config"]["samples_per_shard"] == 16777216
     assert d["config"]["sharded_equals_whole"] is True and d["config"]["messages"] > 0

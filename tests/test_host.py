@@ -180,9 +180,11 @@ def test_device_loader_state_slot_rules(tmp_path, oracle):
 
 def test_synth_tx_walk_matches_reference_sm_generate(oracle):
     """The product's tx walk (synth.cpp) gives the run lengths the
-    reference's sm_generate produces for the same payload."""
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built")
+    reference's sm_generate produces for the same payload: live through
+    oracle/_ref where it is built, and always against what it produced
+    (tests/golden/ref_recorded.json)."""
+    with open(os.path.join(GOLDEN, "ref_recorded.json")) as fh:
+        recorded = iter(json.load(fh)["synth_tx"])
     for name, rate in (("p3l-nexa2012", 3000000), ("unknown-remote1", 3000000),
                        ("p3l-nexa2012", 1000000)):
         dev = ok.Device.load(golden_path("devices", name), rate)
@@ -195,8 +197,12 @@ def test_synth_tx_walk_matches_reference_sm_generate(oracle):
         level = (iq[0::2] != 0).astype(np.int8)
         for i in range(min(syn.num_messages, 3)):
             start, payload = syn.message(i)
-            wave = oracle.RefSm(odev).generate(payload, 0.95)
-            ref_i = oracle.ref_pack(wave)[0::2]
+            rec = next(recorded)
+            assert (rec["device"], rec["rate"], rec["message"], rec["payload"]) == (name, rate, i, payload.hex())
+            ref_i = np.concatenate([np.full(n, v, dtype=np.int16) for v, n in rec["i_rle"]])
+            if oracle.have_ref():
+                wave = oracle.RefSm(odev).generate(payload, 0.95)
+                assert (oracle.ref_pack(wave)[0::2] == ref_i).all(), (name, i)
             n = min(ref_i.size, level.size - start)
             assert n > 1000
             assert (iq[0::2][start:start + n] == ref_i[:n]).all(), (name, i)

@@ -309,8 +309,13 @@ def _random_fsm(O, rng, rate, ns=None, max_triggers=4):
 
 
 def test_random_devices_differential_vs_reference_fsm(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+    """Against the reference's state_machine.c: live through oracle/_ref where it is built, and always
+    against what it decoded from these streams (tests/golden/ref_recorded.json)."""
+    import json
+    import os
+    from tests.helpers import GOLDEN
+    with open(os.path.join(GOLDEN, "ref_recorded.json")) as fh:
+        recorded = iter(json.load(fh)["random_fsm"])
     rng = np.random.default_rng(77)
     for it in range(60):
         rate = int(rng.choice([3000000, 1000000, 750000, 48000]))
@@ -321,11 +326,16 @@ def test_random_devices_differential_vs_reference_fsm(oracle):
                 for _ in range(int(rng.integers(20, 200)))]
         stream = stream_from_runs(runs)
         for buf in (97, 4096):
-            ms, pay, es = oracle.RefSm(dev).stream(stream, buf)
+            rec = next(recorded)
+            assert (rec["it"], rec["buf"]) == (it, buf)
+            ms, pay, es = rec["msg_samples"], rec["payloads"], rec["err_samples"]
+            if oracle.have_ref():
+                lms, lpay, les = oracle.RefSm(dev).stream(stream, buf)
+                assert ([int(x) for x in lms], [bytes(p).hex() for p in lpay], [int(x) for x in les]) == (ms, pay, es), it
             oms, opay, oes = oracle.sm_stream(dev, stream, buf)
-            assert list(ms) == list(oms), it
-            assert (pay == opay).all(), it
-            assert list(es) == list(oes), it
+            assert [int(x) for x in oms] == ms, it
+            assert [bytes(p).hex() for p in opay] == pay, it
+            assert [int(x) for x in oes] == es, it
 
 
 def test_oracle_under_sanitizers(oracle, vectors):

@@ -1,10 +1,11 @@
 #!/bin/bash
-mkdir -p gpurun_out/r03
+OUT=${OUT:-out/r03}
+mkdir -p $OUT
 for cfg in "$@"; do
-  env OOKD_DEVELOPER=1 $cfg timeout -k 10 300 python bench.py --filter fs128_fs16_dec4 --steps 24 --warmup 4 --no-cpu-baseline > gpurun_out/r03/dbg.json 2> gpurun_out/r03/dbg.err || { tail -5 gpurun_out/r03/dbg.err; exit 1; }
+  env OOKD_DEVELOPER=1 $cfg timeout -k 10 300 python bench.py --filter fs128_fs16_dec4 --steps 24 --warmup 4 --full --no-cpu-baseline > $OUT/dbg.json 2> $OUT/dbg.err || { tail -5 $OUT/dbg.err; exit 1; }
   python - <<PY
 import json
-d=json.load(open("gpurun_out/r03/dbg.json"))
+d=json.load(open("$OUT/dbg.json"))
 w=d.get("worst_case") or {}
 print("$cfg", "3ctx ms", d["ms_per_step"], "front", round(d["roofline"]["avg_kernel_ms"]*d["roofline"]["launches_per_step"],3), "| 1ctx", d["single_context"]["ms_per_step"], d["single_context"]["kernel_ms"], "| worst", w.get("ms_per_step"), w.get("kernel_ms"), flush=True)
 PY
