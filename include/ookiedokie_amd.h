@@ -169,11 +169,7 @@ enum {
      * up in the per-device span tables built at create time (identical
      * results; exists so the tests can run both). */
     OOKD_RX_SCAN_SIMS = 1u << 5,
-    /* Front end, packed-VALU form: the hardware-dispatched grid of one-tile
-     * workgroups.  This IS the default; the flag only matters to a developer
-     * build that selected the experimental persistent streaming form
-     * (OOKD_DEVELOPER=1 OOKD_FRONT_STREAM=1), where it forces
-     * the grid form back (identical bits). */
+    /* Accepted and ignored: the grid is the only form of the front end. */
     OOKD_RX_FRONT_GRID = 1u << 6,
     /* Never pipeline a long capture in chunks (see pipeline_chunk_samples). */
     OOKD_RX_NO_PIPELINE = 1u << 7,

@@ -1115,9 +1115,7 @@ template <int KS>
 static hipError_t launch_mfma_ks(FrontParams &pp, uint32_t num_captures, uint64_t grid, hipStream_t stream,
                                  hipEvent_t t0, hipEvent_t t1) {
     const void *fn = reinterpret_cast<const void *>(&fir1_mfma_kernel<KS>);
-    // (experiment: OOKD_MFMA_LDS_PAD caps the workgroups per CU, leaving registers / wave slots to other streams' kernels)
-    static const size_t lds_pad = dev_getenv("OOKD_MFMA_LDS_PAD") ? (size_t)atoi(dev_getenv("OOKD_MFMA_LDS_PAD")) : 0;
-    const size_t lds = mfma_lds_bytes<KS>() + lds_pad;
+    const size_t lds = mfma_lds_bytes<KS>();
     hipError_t e = ensure_dynamic_lds(fn, lds);
     if (e != hipSuccess) return e;
     void *args[] = {&pp};

@@ -110,21 +110,6 @@ __host__ __device__ __forceinline__ uint32_t fir1_wave_slots(uint32_t Tp) {
 
 // Sequential, unfused recomputation of one output (guard-band path).
 template <int R>
-__device__ __forceinline__ float2 fir1_exact_body(const float2 *lds, uint32_t j_out,
-                                                const float *taps, uint32_t ntaps) {
-    float re = 0.0f, im = 0.0f;
-    for (uint32_t k = 0; k < ntaps; ++k) {
-        const float2 x = lds[slot<R>(j_out - k)];
-        const float t = taps[k];
-        const float pr = t * x.x;
-        const float pi = t * x.y;
-        re = re + pr;
-        im = im + pi;
-    }
-    return make_float2(re, im);
-}
-
-template <int R>
 __device__ __noinline__ float2 fir1_exact_output(const float2 *lds, uint32_t j_out,
                                                  const float *taps, uint32_t ntaps) {
     float re = 0.0f, im = 0.0f;
@@ -201,10 +186,9 @@ __device__ __forceinline__ v2s as_v2s(uint32_t w) { return __builtin_bit_cast(v2
 
 // Everything behind the staged window of one wave tile: packed MACs over the
 // tap chunks, threshold + guard band, bit packing, optional float output.
-// Stores the tile's bit words (WT: write-through, visible to a kernel that
-// starts while this one still runs) and returns the tile info word
+// Stores the tile's bit words and returns the tile info word
 // (level changes inside the tile | first bit << 30 | last bit << 31).
-template <bool EXACT, int R, bool WT, bool NOCALL = false>
+template <bool EXACT, int R>
 __device__ __forceinline__ uint32_t fir1_tile_compute(const FrontParams &p, float2 *lds, uint32_t Tp, uint64_t t0,
                                                       uint32_t tid, uint32_t cap, uint64_t *words) {
     uint32_t info = 0;
@@ -281,10 +265,7 @@ __device__ __forceinline__ uint32_t fir1_tile_compute(const FrontParams &p, floa
         while (todo) {                          // one copy of the recompute, whichever outputs need it
             const uint32_t r = (uint32_t)__ffs((int)todo) - 1u;
             todo &= todo - 1u;
-            // (NOCALL: the streaming kernel keeps loads in flight in registers the compiler does not
-            //  know to be busy -- nothing may save / restore them around a call)
-            const float2 y = NOCALL ? fir1_exact_body<R>(lds, Tp + R * tid + r, p.taps, p.stage[0].ntaps)
-                                    : fir1_exact_output<R>(lds, Tp + R * tid + r, p.taps, p.stage[0].ntaps);
+            const float2 y = fir1_exact_output<R>(lds, Tp + R * tid + r, p.taps, p.stage[0].ntaps);
             const float pe = power_ref(y.x, y.y);
             mask = (mask & ~(1u << r)) | ((pe >= p.p_star ? 1u : 0u) << r);
         }
@@ -331,10 +312,7 @@ __device__ __forceinline__ uint32_t fir1_tile_compute(const FrontParams &p, floa
         const uint32_t lo = __shfl_xor((uint32_t)w64, (int)d), hi = __shfl_xor((uint32_t)(w64 >> 32), (int)d);
         w64 |= (uint64_t)lo | ((uint64_t)hi << 32);
     }
-    if (tid % kLanesPerWord == 0) {
-        if (WT) __hip_atomic_store(words + (t0 >> 6) + tid / kLanesPerWord, w64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else words[(t0 >> 6) + tid / kLanesPerWord] = w64;
-    }
+    if (tid % kLanesPerWord == 0) words[(t0 >> 6) + tid / kLanesPerWord] = w64;
     return info;
 }
 
@@ -418,228 +396,8 @@ __global__ __launch_bounds__(64 * kFirWgWaves) void fir1_bits_kernel(const Front
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    const uint32_t info = fir1_tile_compute<EXACT, R, false>(p, lds, Tp, t0, tid, cap, words);
+    const uint32_t info = fir1_tile_compute<EXACT, R>(p, lds, Tp, t0, tid, cap, words);
     if (tid == 0) p.tile_info[(uint64_t)cap * p.tiles_per_cap + t0 / kTile] = info;
-}
-
-// ---------------------------------------------------------------------------
-// front end, 1 stage / decimation 1, STREAMING form
-// ---------------------------------------------------------------------------
-//
-// The grid form above is one workgroup per wave tile: half a million tiny
-// workgroups per GiB, which fill every wave slot and nearly all of the LDS of
-// every CU for as long as the grid lasts -- the edge / state machine kernels
-// of the chunk (or capture) before starve beside it.  This form is a
-// PERSISTENT grid of single-wave workgroups, N per CU (the launcher picks N),
-// that pull GROUPS of kStreamGroup = 4 consecutive tiles (2048 outputs, 8 KiB
-// of input) from ticket heads:
-//   * many heads (head = workgroup % H owns the groups = head mod H): one
-//     returning atomic per group, far below what a head sustains, and the
-//     active window of the capture stays dense and moves front to back like a
-//     hardware-dispatched grid's (tools/stream_bw.hip: 6.6-6.7 TB/s at 8..32
-//     waves per CU against 6.9 for the grid shape and 5.3-6.2 for strided or
-//     few-head persistent shapes);
-//   * residency is capped at N waves and N windows of LDS per CU: the rest of
-//     the CU stays free for whatever else is queued on the device;
-//   * a wave issues the nine loads of its group at once (nt: the stream is read
-//     once; 8.5 KiB in flight per waiting wave) with the ticket of its next
-//     group in front of them; inside a group the tap history of a tile is the
-//     tail of the tile before, in registers;
-//   * a quiet group costs its loads, ONE store of zero words and ONE store of
-//     tile infos;
-//   * chunk pipelining: a wave counts the groups it finished per chunk and adds
-//     them to done[chunk] when it moves on to a later chunk (its stores are
-//     write-through and complete by then), so a stream waiting for
-//     done[c] == groups of chunk c may read that prefix of the bit words while
-//     this kernel still runs.
-// Tile arithmetic is the grid form's (fir1_tile_compute), bit for bit.
-// (Deeper software pipelines -- a ring of tiles in registers, double-buffered
-//  groups -- were tried: the compiler's wait counts turn conservative across the
-//  loop (vmcnt(0) behind the issue), and inline-asm loads are unsafe because the
-//  register allocator copies their destination registers while they are in flight.)
-
-struct StreamGroup {            // raw samples of one group: lane L of c[i][0] holds samples 512 i + 4L .., c[i][1] + 256
-    v4u c[kStreamGroup][2];
-    v4u hal;                    // lanes hal0..63: the Tp samples before the group
-};
-
-__device__ __forceinline__ v4u ld_nt(const uint4 *p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p));
-}
-
-constexpr uint32_t kNoGroup = 0xffffffffu;
-
-template <bool EXACT, bool WT>
-__global__ __launch_bounds__(64) void fir1_stream_kernel(const FrontParams p, const StreamCtl ctl) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int R = kFir1RShort;
-    constexpr uint32_t kTile = 64u * R;                 // 512 outputs
-    constexpr uint32_t kGroupOut = kTile * kStreamGroup;
-    static_assert(kTile == 512, "two 16 B loads per lane and tile");
-    const uint32_t tid = threadIdx.x;
-    const uint32_t Tp = p.stage[0].ntaps_pad;           // <= 256
-    const uint32_t hal0 = 64u - Tp / 4u;                // lanes hal0 .. 63 of a history register are valid
-    float2 *lds = reinterpret_cast<float2 *>(smem_raw);
-    const uint32_t H = ctl.num_heads;
-    const uint32_t h = blockIdx.x % H;
-    uint32_t *head = ctl.heads + (size_t)kStreamHeadStride * h;
-    const uint32_t ngroups = ctl.groups_per_cap * ctl.num_caps;
-    const int L = p.quiet_lsb;
-    const bool do_quiet = L > 0 && !p.fir_out;
-    const bool aligned16 = (reinterpret_cast<uintptr_t>(p.iq) & 15u) == 0 && (p.cap_stride & 3u) == 0;
-
-    // (lane 0 only, written over the zero the other lanes keep -- no merge instruction, so the wait for the atomic
-    //  falls where the ticket is resolved.  The build disables the compiler's atomic optimizer,
-    //  which would rewrite this as a wave reduction and wait for the result on the spot.)
-    auto issue_ticket = [&]() {
-        uint32_t t = 0;
-        if (tid == 0) t = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return t;
-    };
-    auto resolve_ticket = [&](uint32_t t) {
-        const uint64_t g = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)t) * H + h;
-        return g < ngroups ? (uint32_t)g : kNoGroup;
-    };
-
-    // chunk accounting (write-through runs): groups this wave finished in chunk `chunk`
-    uint32_t chunk = 0, chunk_count = 0;
-    auto flush_chunk = [&]() {
-        if (WT && ctl.done && chunk_count) {
-            // every store of those groups has reached memory before the chunk counter moves
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (tid == 0) __hip_atomic_fetch_add(ctl.done + chunk, chunk_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        chunk_count = 0;
-    };
-
-    const bool strided = ctl.static_stride != 0;        // experiment: no tickets, group = workgroup + k * grid
-    uint32_t g = strided ? (blockIdx.x < ngroups ? blockIdx.x : kNoGroup) : resolve_ticket(issue_ticket());
-    while (g != kNoGroup) {
-        const uint32_t t_next = strided ? 0u : issue_ticket();         // returns while the group's loads are waited for
-        const uint32_t cap = g / ctl.groups_per_cap;
-        const uint64_t g0 = (uint64_t)(g - cap * ctl.groups_per_cap) * kGroupOut;
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(p.iq) + (uint64_t)cap * p.cap_stride;
-        uint64_t *words = p.bits + (uint64_t)cap * p.words_per_cap;
-        // a group whose window lies inside the capture and can be fetched 16 B at a time
-        const bool inside = aligned16 && g0 >= Tp && g0 + kGroupOut <= p.n_valid;
-        StreamGroup q{};
-        if (inside) {
-            const uint4 *s4 = reinterpret_cast<const uint4 *>(src + g0) + tid;
-#pragma unroll
-            for (int i = 0; i < kStreamGroup; ++i) {
-                q.c[i][0] = ld_nt(s4 + 128 * i);
-                q.c[i][1] = ld_nt(s4 + 128 * i + 64);
-            }
-            q.hal = ld_nt(s4 - 64);     // (lanes below hal0 fetch samples further back: never used)
-        }
-
-        uint32_t quiet_mask = 0, info_vec = 0;
-        bool info_vec_any = false;
-#pragma unroll
-        for (int i = 0; i < kStreamGroup; ++i) {
-            const uint64_t t0 = g0 + (uint64_t)i * kTile;
-            const v4u hal = i == 0 ? q.hal : q.c[i > 0 ? i - 1 : 0][1];    // the tile's tap history: the tail of the tile before
-            bool loud = true;
-            if (inside) {
-                if (do_quiet) {
-                    v2s mx = (v2s){0, 0}, mn = (v2s){0, 0};
-                    const uint32_t w[12] = {q.c[i][0].x, q.c[i][0].y, q.c[i][0].z, q.c[i][0].w, q.c[i][1].x, q.c[i][1].y,
-                                            q.c[i][1].z, q.c[i][1].w, hal.x,       hal.y,       hal.z,       hal.w};
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) {
-                        // lanes below hal0 hold no history (older samples: masked)
-                        const uint32_t v = (k >= 8 && tid < hal0) ? 0u : w[k];
-                        mx = __builtin_elementwise_max(mx, as_v2s(v));
-                        mn = __builtin_elementwise_min(mn, as_v2s(v));
-                    }
-                    loud = !(mx.x < L && mx.y < L && mn.x > -L && mn.y > -L);
-                    loud = __ballot(loud) != 0;
-                }
-                if (loud) {
-                    // window slot j <-> input index t0 - Tp + j
-                    if (tid >= hal0) {
-                        float2 *dst = lds + slot<R>(4u * (tid - hal0));
-                        dst[0] = unpack_iq(hal.x);
-                        dst[1] = unpack_iq(hal.y);
-                        dst[2] = unpack_iq(hal.z);
-                        dst[3] = unpack_iq(hal.w);
-                    }
-                    float2 *d0 = lds + slot<R>(Tp + 4u * tid);
-                    d0[0] = unpack_iq(q.c[i][0].x);
-                    d0[1] = unpack_iq(q.c[i][0].y);
-                    d0[2] = unpack_iq(q.c[i][0].z);
-                    d0[3] = unpack_iq(q.c[i][0].w);
-                    float2 *d1 = lds + slot<R>(Tp + 256u + 4u * tid);
-                    d1[0] = unpack_iq(q.c[i][1].x);
-                    d1[1] = unpack_iq(q.c[i][1].y);
-                    d1[2] = unpack_iq(q.c[i][1].z);
-                    d1[3] = unpack_iq(q.c[i][1].w);
-                }
-            } else {
-                // first / last groups of a capture, halo of a shard, unaligned pointers
-                const uint32_t nvec = (kTile + Tp) >> 2;
-                for (uint32_t v = tid; v < nvec; v += 64) {
-                    const int64_t n = (int64_t)t0 - (int64_t)Tp + 4 * (int64_t)v;
-                    float2 *dst = lds + slot<R>(4 * v);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) dst[k] = fetch_sample(p, src, nullptr, n + k);
-                }
-            }
-            if (loud) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const uint32_t info = fir1_tile_compute<EXACT, R, WT, true>(p, lds, Tp, t0, tid, cap, words);
-                if (tid == (uint32_t)i) info_vec = info;
-                info_vec_any = info_vec_any || info != 0;
-                // the next loud tile rewrites the window: the reads above are done (the LDS is in order)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            } else {
-                quiet_mask |= 1u << i;
-            }
-        }
-        // sparse output (p.sparse): quiet tiles store nothing -- their words and infos are zero already
-        // (launch_clear_tiles); small stores into the read stream cost 3 x their share of the bytes
-        // (tools/stream_bw2.hip).  Loud tiles' words were stored by fir1_tile_compute.
-        if (!p.sparse) {
-            // zero words of the quiet tiles: 8 words per tile, lane l covers words 2l, 2l+1 of the group = tile l / 4
-            if (tid < 4u * kStreamGroup && ((quiet_mask >> (tid >> 2)) & 1u)) {
-                uint64_t *w = words + (g0 >> 6) + 2u * tid;
-                if (WT) {
-                    __hip_atomic_store(w, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(w + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    *reinterpret_cast<uint4 *>(w) = make_uint4(0, 0, 0, 0);
-                }
-            }
-            if (tid < (uint32_t)kStreamGroup) {
-                uint32_t *ti = p.tile_info + (uint64_t)cap * p.tiles_per_cap + (g0 / kTile) + tid;
-                if (WT) __hip_atomic_store(ti, info_vec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else *ti = info_vec;
-            }
-        } else if (info_vec_any) {
-            // infos of the loud tiles only (lane i holds tile i's)
-            if (tid < (uint32_t)kStreamGroup && !((quiet_mask >> tid) & 1u)) {
-                uint32_t *ti = p.tile_info + (uint64_t)cap * p.tiles_per_cap + (g0 / kTile) + tid;
-                if (WT) __hip_atomic_store(ti, info_vec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else *ti = info_vec;
-            }
-        }
-        if (p.quiet_count && tid == 0 && quiet_mask) atomicAdd(p.quiet_count + (g % kQuietCounters), (uint32_t)__popc(quiet_mask));
-        if (WT && ctl.done) {
-            uint32_t c = chunk;
-            while (c + 1 < ctl.num_chunks && g >= ctl.chunk_end[c]) ++c;
-            if (c != chunk) {
-                flush_chunk();
-                chunk = c;
-            }
-            chunk_count++;
-        }
-        if (strided) g = (uint64_t)g + gridDim.x < ngroups ? g + gridDim.x : kNoGroup;
-        else g = resolve_ticket(t_next);
-    }
-    flush_chunk();
 }
 
 // ---------------------------------------------------------------------------
@@ -1329,56 +1087,6 @@ bool front_sparse_capable(const FrontParams &p) {
     // (round 3: the two-stage kernels too -- their quiet tiles stored 36 bytes each, 150 MB of small stores per
     //  16 GiB capture beside the read stream: the backend default filter ran 15 % behind the 1-stage one for it)
     return (use_fir1(p) || use_fir2(p)) && p.quiet_lsb > 0 && !p.fir_out;
-}
-
-bool front_streams(const FrontParams &p) {
-    return !front_uses_mfma(p) && use_fir1(p) && fir1_R(p) == kFir1RShort && p.stage[0].ntaps_pad <= 256u;
-}
-
-static int device_cu_count() {
-    static thread_local int cached_dev = -1, cached = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != cached_dev) {
-        hipDeviceProp_t prop;
-        cached = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                     ? prop.multiProcessorCount : 256;
-        cached_dev = dev;
-    }
-    return cached;
-}
-
-hipError_t launch_front_stream(const FrontParams &p, StreamCtl ctl, bool exact, bool write_through,
-                               hipStream_t stream, hipEvent_t t0, hipEvent_t t1) {
-    if (!front_streams(p) || p.tiles_per_cap % kStreamGroup != 0) return hipErrorInvalidValue;
-    const size_t lds = (size_t)fir1_wave_slots<kFir1RShort>(p.stage[0].ntaps_pad) * sizeof(float2);
-    const uint64_t ngroups = (uint64_t)(p.tiles_per_cap / kStreamGroup) * ctl.num_caps;
-    if (ngroups >= 0xfffffff0ull) return hipErrorInvalidValue;
-    if (ngroups == 0) {
-        if (t0 && hipEventRecord(t0, stream) != hipSuccess) return hipGetLastError();
-        if (t1 && hipEventRecord(t1, stream) != hipSuccess) return hipGetLastError();
-        return hipSuccess;
-    }
-    ctl.groups_per_cap = p.tiles_per_cap / kStreamGroup;
-    uint64_t grid = (uint64_t)device_cu_count() * (ctl.waves_per_cu ? ctl.waves_per_cu : 12u);
-    if (grid > ngroups) grid = ngroups;
-    // heads: as many as the grid has waves (each head still hands out groups in order), at most kStreamHeads
-    ctl.num_heads = (uint32_t)std::min<uint64_t>(grid, (uint64_t)kStreamHeads);
-    const void *fn;
-    if (write_through) {
-        fn = exact ? reinterpret_cast<const void *>(&fir1_stream_kernel<true, true>)
-                   : reinterpret_cast<const void *>(&fir1_stream_kernel<false, true>);
-    } else {
-        fn = exact ? reinterpret_cast<const void *>(&fir1_stream_kernel<true, false>)
-                   : reinterpret_cast<const void *>(&fir1_stream_kernel<false, false>);
-    }
-    hipError_t e = ensure_dynamic_lds(fn, lds);
-    if (e != hipSuccess) return e;
-    FrontParams pp = p;
-    void *args[] = {&pp, &ctl};
-    e = hipExtLaunchKernel(fn, dim3((uint32_t)grid), dim3(64), args, lds, stream, t0, t1, 0);
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

@@ -103,24 +103,6 @@ hipError_t launch_clear_tiles(uint32_t *tile_info, uint64_t *bits, uint64_t ntil
 // does this shape run on a kernel that honours FrontParams::sparse?
 bool front_sparse_capable(const FrontParams &p);
 
-// ---- streaming (persistent) form of the tuned front end ------------------------------
-constexpr int kStreamGroup = 2;         // wave tiles per ticket (1024 outputs, 4 KiB of input)
-constexpr int kStreamHeads = 1024;      // ticket heads (head = workgroup % heads owns groups = head mod heads)
-constexpr int kStreamHeadStride = 16;   // dwords between heads (own 64-B lines: atomics execute at the memory side)
-constexpr int kMaxChunks = 256;
-
-struct StreamCtl {
-    uint32_t *heads;            // [kStreamHeads * kStreamHeadStride] ticket heads, zero at launch
-    uint32_t *done;             // [num_chunks] groups finished per chunk (zero at launch), or null
-    const uint32_t *chunk_end;  // [num_chunks] first group (global, capture-major) past each chunk
-    uint32_t num_chunks;
-    uint32_t num_caps;
-    uint32_t waves_per_cu;      // persistent single-wave workgroups per CU (0 = default)
-    uint32_t groups_per_cap;    // filled in by the launcher: tiles_per_cap / kStreamGroup
-    uint32_t num_heads;         // filled in by the launcher
-    uint32_t static_stride;     // experiment: groups dealt statically (workgroup + k * grid) instead of by ticket
-};
-
 // ---- matrix-core form of the tuned 1-stage front end (fir_mfma.hip) ---------------------
 constexpr uint32_t kMfmaTile = 1024;    // outputs per wave tile: 32 columns x 32 rows of v_mfma_f32_32x32x16_f16
 
@@ -157,12 +139,6 @@ hipError_t ensure_dynamic_lds(const void *func, size_t bytes);
 hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact, hipStream_t stream,
                         hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, uint64_t tile_begin = 0,
                         uint64_t tile_count = ~0ull);
-// Streaming form (1 stage / decimation 1 / <= 256 taps only: front_streams()).  ctl.heads (and
-// ctl.done) must be zero when the kernel starts; write_through: bit words / tile infos are stored
-// past the L2 so that a kernel started while this one runs reads them (ctl.done tells when).
-bool front_streams(const FrontParams &p);
-hipError_t launch_front_stream(const FrontParams &p, StreamCtl ctl, bool exact, bool write_through,
-                               hipStream_t stream, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // 1024-ish output windows ("wave tiles") the tuned kernels split a capture into
 // (0 when the generic kernel serves this shape).
 uint64_t front_wave_tiles(const FrontParams &p);

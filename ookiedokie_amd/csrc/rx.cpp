@@ -12,6 +12,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <utility>
 
 #include "common.hpp"
 #include "ingest.hpp"
@@ -34,9 +35,6 @@ namespace {
 constexpr uint32_t kIterBatch = 4;      // FSM fix-point rounds queued per host sync
 
 constexpr uint64_t kHostMsgFirst = 2048;    // messages copied with the header
-// control block of the streaming front end: ticket heads | per-chunk counters | chunk ends
-constexpr size_t kCtlHeads = 0, kCtlDone = (size_t)kStreamHeads * kStreamHeadStride, kCtlChunkEnd = kCtlDone + kMaxChunks,
-                 kCtlWords = kCtlChunkEnd + kMaxChunks;
 
 struct ResultHeader {
     uint32_t changed[kIterBatch];
@@ -56,6 +54,7 @@ struct Chunk {
     uint32_t blk0, nblk;        // 4096-output blocks
     uint64_t edge_off, edge_cap;        // its region of the edge list
 };
+constexpr int kMaxChunks = 256;
 constexpr uint64_t kPipeDefaultChunk = 1ull << 28;      // input samples
 constexpr uint64_t kPipeTailChunk = 1ull << 25;         // the last chunks shrink down to this: a short exposed chain
 
@@ -74,10 +73,23 @@ struct ookd_rx_gate {
 
 namespace {
 
+// A device allocation, freed with its owner.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), n(std::exchange(o.n, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
     int alloc(size_t count) {
         n = count;
         if (count == 0) return OOKD_OK;
@@ -88,11 +100,6 @@ struct DevBuf {
             return OOKD_ERR_NOMEM;
         }
         return OOKD_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
     }
 };
 
@@ -311,14 +318,38 @@ uint64_t gcd64(uint64_t a, uint64_t b) {
     return a;
 }
 
-}  // namespace
-
-struct ookd_rx {
-    ookd_rx_config cfg{};
+// The streams, events and pinned buffers of a context.  A base of ookd_rx, so that it is destroyed after
+// ookd_rx's members: every device buffer is freed while the streams still exist (with the streams destroyed
+// first, contexts created and destroyed in quick succession hung in their destruction).
+struct RxHandles {
     int dev = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipStream_t s_front = nullptr, s_chain = nullptr;   // chunk pipeline
+    hipEvent_t ev_start = nullptr, ev_end = nullptr;
+    std::vector<hipEvent_t> ev_c0, ev_c1;       // per chunk: front-end kernel start / stop
+    ResultHeader *h_hdr = nullptr;  // pinned
+    MsgDev *h_msgs = nullptr;       // pinned, msg_capacity
+    Ingest ingest;                  // process_host's pinned double buffer (lazy)
+    ~RxHandles() {
+        for (hipEvent_t e : ev_c0) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_c1) if (e) (void)hipEventDestroy(e);
+        if (ev_start) (void)hipEventDestroy(ev_start);
+        if (ev_end) (void)hipEventDestroy(ev_end);
+        if (s_front) (void)hipStreamDestroy(s_front);
+        if (s_chain) (void)hipStreamDestroy(s_chain);
+        if (h_hdr) (void)hipHostFree(h_hdr);
+        if (h_msgs) (void)hipHostFree(h_msgs);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+}  // namespace
+
+struct ookd_rx : RxHandles {
+    ookd_rx_config cfg{};
 
     // filter
     uint32_t num_stages = 0;
@@ -334,12 +365,12 @@ struct ookd_rx {
     uint32_t mfma_g = 0;
     uint32_t mfma_xcd = 2;          // FrontParams::mfma_xcd (OOKD_MFMA_XCD)
     int quiet_lsb = 0;              // 0 = the quiet shortcut never applies
+    uint32_t tile_bits = 0;         // bits per wave tile of the front-end kernel (front_tile_bits), 0 = generic kernel
     bool exact = false;
     bool count_quiet = false;
     DevBuf<uint32_t> d_quiet;       // kQuietCounters spread counters (diagnostics), running totals
     std::vector<uint32_t> quiet_prev;       // what they held after the run before
     DevBuf<uint32_t> d_tile_info;   // per wave tile edge counts written by the tuned front-end kernels
-    DevBuf<uint32_t> d_ctl;         // streaming front end: ticket heads | chunk counters | chunk ends
     // sparse front-end output: quiet tiles store nothing; the tile infos carry the run's stamp and tiles
     // without it read as quiet (kernels.hpp: tile_live).  Extents of the previous run: a change of the
     // geometry zeroes them first.
@@ -353,10 +384,6 @@ struct ookd_rx {
     // on its own half of the CUs
     bool pipe_ok = false;
     uint64_t pipe_chunk_in = 0;     // target input samples per chunk
-    hipStream_t s_front = nullptr, s_chain = nullptr;
-    std::vector<hipStream_t> dummy_streams;     // OOKD_PIPE_DUMMY experiment
-    hipEvent_t ev_start = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> ev_c0, ev_c1;       // per chunk: front-end kernel start / stop
     std::vector<Chunk> chunks;      // of the last run (empty: not pipelined)
     DevBuf<SegState> d_carry;       // [2] state handed from chunk to chunk
     DevBuf<uint64_t> d_chunk_totals;    // [2][2] messages / errors so far
@@ -384,8 +411,6 @@ struct ookd_rx {
     uint32_t sync_mode = 0;                 // of the scan in flight: FsmScanArgs::sync_try
     std::vector<uint64_t> mixed_errs;       // error positions of a run whose refused captures were redone (host side)
     bool mixed_valid = false;
-    bool front_grid = false;        // OOKD_RX_FRONT_GRID: one workgroup per wave tile instead of the streaming form
-    uint32_t stream_waves = 12;     // persistent front-end waves per CU
     uint64_t front_launch_outputs = 1ull << 29;    // decimated samples per front-end grid launch (all captures together)
 
     // device (state machine)
@@ -446,10 +471,7 @@ struct ookd_rx {
     uint32_t scan_fin_cap = 0;
     uint32_t scan_stamp = 0;        // stamps the finish kernel's block aggregates, never 0
     DevBuf<int16_t> d_stage_in;     // process_host staging (lazy)
-    Ingest ingest;                  // its pinned double buffer (lazy)
 
-    ResultHeader *h_hdr = nullptr;  // pinned
-    MsgDev *h_msgs = nullptr;       // pinned, msg_capacity
     ResultHeader *h_hdr_dev = nullptr;      // the same two through the device's mapping
     MsgDev *h_msgs_dev = nullptr;
     bool hdr_dirty = true;          // device header needs zeroing before the next run
@@ -467,77 +489,9 @@ struct ookd_rx {
     ~ookd_rx() {
         if (gate) {
             std::lock_guard<std::mutex> lock(gate->m);
-            if (gate->last == ev[1]) gate->last = nullptr;      // ev[1] is destroyed below
+            if (gate->last == ev[1]) gate->last = nullptr;      // ev[1] is destroyed with RxHandles
         }
-        (void)hipSetDevice(dev);
-        d_taps.release();
-        d_mfma_a.release();
-        d_tables.release();
-        d_big.release();
-        d_bits.release();
-        d_fir.release();
-        d_halo.release();
-        d_tile_info.release();
-        d_ctl.release();
-        d_quiet.release();
-        d_carry.release();
-        d_cap_fallback.release();
-        d_pre.release();
-        d_blk_in.release();
-        d_rowz.release();
-        d_skipc.release();
-        d_sync_rec.release();
-        d_chunk_totals.release();
-        d_fin_tickets.release();
-        for (auto &e : ev_c0) if (e) (void)hipEventDestroy(e);
-        for (auto &e : ev_c1) if (e) (void)hipEventDestroy(e);
-        if (ev_start) (void)hipEventDestroy(ev_start);
-        if (ev_end) (void)hipEventDestroy(ev_end);
-        for (hipStream_t d : dummy_streams) if (d) (void)hipStreamDestroy(d);
-        if (s_front) (void)hipStreamDestroy(s_front);
-        if (s_chain) (void)hipStreamDestroy(s_chain);
-        d_blk_count.release();
-        d_blk_offset.release();
-        d_group_total.release();
-        d_seg_bounds.release();
-        d_edges.release();
-        d_state_in.release();
-        d_state_out.release();
-        d_seg_msgs.release();
-        d_msgs.release();
-        d_seg_msg_count.release();
-        d_seg_err_count.release();
-        d_seg_errs.release();
-        d_hdr.release();
-        d_debug.release();
-        d_block_tab.release();
-        d_lt_off.release();
-        d_lt_n0.release();
-        d_lt_pk.release();
-        d_lt_merged.release();
-        d_ltab.release();
-        d_reach.release();
-        d_cap_group_off.release();
-        d_group_tab.release();
-        d_super_tab.release();
-        d_super_in.release();
-        d_cap_super_off.release();
-        d_cap_end.release();
-        d_cap_block_off.release();
-        d_events.release();
-        d_ev_hot.release();
-        d_app_vals.release();
-        d_scan_errs.release();
-        d_final_state.release();
-        d_fin_off.release();
-        d_fsum.release();
-        d_stage_in.release();
-        if (h_hdr) (void)hipHostFree(h_hdr);
-        if (h_msgs) (void)hipHostFree(h_msgs);
-        for (auto &e : ev) {
-            if (e) (void)hipEventDestroy(e);
-        }
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
+        (void)hipSetDevice(dev);        // for what is freed after this body: the members, then RxHandles
     }
 
     void geometry(uint64_t n_valid, bool pad_to_buffer, uint64_t &n_in, uint64_t &n_out,
@@ -584,10 +538,7 @@ struct ookd_rx {
         p.quiet_lsb = quiet_lsb;
         p.quiet_count = count_quiet ? d_quiet.p : nullptr;
         p.tile_info = d_tile_info.p;
-        {
-            const uint32_t tile_bits = front_tile_bits(p);
-            p.tiles_per_cap = tile_bits ? (uint32_t)(run_words * 64 / tile_bits) : 0;
-        }
+        p.tiles_per_cap = tile_bits ? (uint32_t)(run_words * 64 / tile_bits) : 0;
         p.sparse = sparse ? 1u : 0u;
         p.stamp_bits = tile_stamp << kTileStampShift;
         return p;
@@ -606,7 +557,6 @@ struct ookd_rx {
         e.edges = d_edges.p;
         e.edge_capacity = edge_capacity;
         e.overflow = &d_hdr.p->edge_overflow;
-        const uint32_t tile_bits = front_tile_bits(front_params(nullptr, 0));
         if (tile_bits && d_tile_info.p) {
             e.tile_info = d_tile_info.p;
             e.tiles_per_block = (uint32_t)(kBlockWords * 64) / tile_bits;
@@ -647,7 +597,6 @@ struct ookd_rx {
         f.totals = d_hdr.p->totals;
         f.debug = d_debug.p;
         f.edge_overflow = &d_hdr.p->edge_overflow;
-        const uint32_t tile_bits = front_tile_bits(front_params(nullptr, 0));
         if (tile_bits && d_tile_info.p) {
             f.tile_info = d_tile_info.p;
             f.tiles_per_cap = (uint32_t)(run_words * 64 / tile_bits);
@@ -657,16 +606,23 @@ struct ookd_rx {
         return f;
     }
 
-    uint32_t next_sync_mode() {
-        if (!scan_sync) return sync_mode = 0;
+    uint32_t next_scan_stamp() {
+        if (++scan_stamp == 0) scan_stamp = 1;
+        return scan_stamp;
+    }
+
+    // sync_mode for the next run's scan (scan_args passes it on): called once per run
+    void next_sync_mode() {
+        sync_mode = 0;
+        if (!scan_sync) return;
         // a short edge list goes through the composing kernels faster: the walk ends with its longest region (a few
         // hundred leaves at 0.14 us, whatever the capture's size) -- chain 131 against 153 us for the 46 000 edges of a
         // 1 GiB bench capture, 275 against 400 for the 737 000 of 16 GiB, about even at 20 000.  By the edge count of
         // this context's last run; before there is one, by the capture's length
         const uint64_t expect = stats.num_edges ? stats.num_edges : ((uint64_t)run_n_out * run_caps) >> 12;
-        if (expect < sync_min_edges) return sync_mode = 0;
-        if (sync_backoff == 0) return sync_mode = 2;
-        return sync_mode = (--sync_backoff == 0) ? 1u : 0u;
+        if (expect < sync_min_edges) return;
+        if (sync_backoff == 0) sync_mode = 2;
+        else sync_mode = (--sync_backoff == 0) ? 1u : 0u;
     }
 
     int front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d_halo_ptr,
@@ -675,13 +631,16 @@ struct ookd_rx {
     int run_pipelined(const void *d_iq);
     int prepare_front(FrontParams &fp);
     int run_state_machine(const FsmStateDev *first, bool fresh);
+    FsmScanArgs scan_args() const;
     int fsm_scan(const FsmStateDev *first);
+    int dump_scan_debug();
     int fsm_to_fixpoint(const FsmStateDev *first, bool fresh, bool force_first, const FsmParams *view = nullptr);
     int redo_refused_captures();
     int fetch_results();
     int enqueue_publish();
     PublishParams publish_params() const;
     bool scan_published = false;    // the queued scan ends with the publish step
+    int rearm_header(const ResultHeader &seen);
     int collect_results();
     bool submitted = false;         // a run is queued (ookd_rx_submit_device) and not yet waited for
 };
@@ -691,7 +650,6 @@ struct ookd_rx {
 // runs, except when the geometry changes (rare; keeps "a zero info means zero words" simple to reason
 // about) or the 16-bit stamp wraps (every 2^16 - 1 runs): then every tile the buffer may hold is zeroed.
 int ookd_rx::prepare_front(FrontParams &fp) {
-    const uint32_t tile_bits = front_tile_bits(fp);
     if (!tile_bits) return OOKD_OK;
     if (sparse) {
         const uint64_t tiles = (uint64_t)run_caps * fp.tiles_per_cap;
@@ -722,7 +680,6 @@ int ookd_rx::prepare_front(FrontParams &fp) {
 // left in the current run's extents.
 int ookd_rx::densify_bits() const {
     if (bits_dense || !sparse || !dirty_tiles) return OOKD_OK;
-    const uint32_t tile_bits = front_tile_bits(front_params(nullptr, 0));
     HIPCHK(launch_clear_tiles(d_tile_info.p, d_bits.p, dirty_tiles, dirty_tiles_per_cap, dirty_words_per_cap, tile_bits,
                               tile_stamp << kTileStampShift, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -807,7 +764,6 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     HIPCHK(hipStreamWaitEvent(s_front, ev_start, 0));
     HIPCHK(hipStreamWaitEvent(s_chain, ev_start, 0));
 
-    const uint32_t tile_bits = front_tile_bits(fp);
     const uint32_t tiles_per_block = (uint32_t)kFirTile / tile_bits;
     scan_used = false;
     scan_pending = true;
@@ -822,62 +778,37 @@ int ookd_rx::run_pipelined(const void *d_iq) {
         HIPCHK(launch_front(fp, 1, exact, s_front, ev_c0[c], ev_c1[c], (uint64_t)ch.blk0 * tiles_per_block,
                             (uint64_t)ch.nblk * tiles_per_block));
     }
+    // one scan form for every chunk: a refusal anywhere redoes the capture whole
+    next_sync_mode();
     for (size_t c = 0; c < nc; ++c) {
         const Chunk &ch = chunks[c];
         const bool last = c + 1 == nc;
         HIPCHK(hipStreamWaitEvent(s_chain, ev_c1[c], 0));
-        // ---- its edges: chunk-local positions ----------------------------------------------------------
-        EdgeParams e{};
+        // ---- its edges: chunk-local positions (the run is one capture) -------------------------------------
+        EdgeParams e = edge_params();
         e.bits = d_bits.p + (size_t)ch.blk0 * kBlockWords;
         e.words_per_cap = (uint64_t)ch.nblk * kBlockWords;
         e.n_out = ch.nout;
-        e.num_captures = 1;
         e.blocks_per_cap = ch.nblk;
         e.blk_count = d_blk_count.p + ch.blk0;
         e.blk_offset = d_blk_offset.p + ch.blk0 + c;            // nblk + 1 entries per chunk
-        e.group_total = d_group_total.p;
         e.edges = d_edges.p + ch.edge_off;
         e.edge_capacity = ch.edge_cap;
-        e.overflow = &d_hdr.p->edge_overflow;
         e.tile_info = d_tile_info.p + (size_t)ch.blk0 * tiles_per_block;
-        e.tiles_per_block = tiles_per_block;
         e.total_acc = &d_hdr.p->total_edges;
         e.has_prev = c ? 1u : 0u;
-        e.stamp_bits = fp.stamp_bits;
         HIPCHK(launch_edges(e, s_chain));
         // ---- its state machine, from the chunk before's outgoing state --------------------------------------
-        FsmScanArgs a{};
-        a.f = fsm_params();
+        FsmScanArgs a = scan_args();
         a.f.bits = e.bits;
         a.f.tile_info = e.tile_info;
         a.f.words_per_cap = e.words_per_cap;
         a.f.edges = e.edges;
         a.f.blk_offset = e.blk_offset;
         a.f.blocks_per_cap = ch.nblk;
-        a.f.num_captures = 1;
         a.f.n_out = ch.nout;
         a.f.totals = last ? d_hdr.p->totals : d_chunk_totals.p + 2 * (c & 1);
-        a.D = scan_D;
-        a.S = scan_S;
-        a.SNB = scan_S * (scan_max_bits + 2);
-        a.leaf_block = scan_leaf_block;
-        a.grid_blocks = 1024;
-        a.block_tab = d_block_tab.p;
-        a.lt_off = d_lt_off.p;
-        a.lt_n0 = d_lt_n0.p;
-        a.lt_pk = d_lt_pk.p;
-        a.lt_words = (uint32_t)(d_lt_off.n + d_lt_n0.n + d_lt_pk.n);
-        a.lt_merged = d_lt_merged.p;
-        a.lt_merged_words = lt_merged_rows;
-        a.lt_sync_words = (uint32_t)d_lt_merged.n;
-        a.ltab = d_ltab.p;
-        a.reach = d_reach.p;
-        a.nreach = scan_reach_n;
-        a.nreach_base = scan_reach_base;
-        a.nreach_lv[0] = scan_reach_lv[0];
-        a.nreach_lv[1] = scan_reach_lv[1];
         if (last) {
-            a.publish = publish_params();
             a.publish.total_edges = nullptr;        // accumulated in the header by the edge stages
         } else {
             // messages go to the host as they are resolved; the header only with the last chunk
@@ -887,46 +818,12 @@ int ookd_rx::run_pipelined(const void *d_iq) {
             pp.first_msgs = std::min<uint64_t>(kHostMsgFirst, msg_capacity);
             a.publish = pp;
         }
-        a.cap_group_off = d_cap_group_off.p;
-        a.group_tab = d_group_tab.p;
-        a.cap_super_off = d_cap_super_off.p;
-        a.super_tab = d_super_tab.p;
-        a.super_in = d_super_in.p;
-        a.cap_end = d_cap_end.p;
-        a.cap_first = d_cap_end.p + (max_captures + 8);
-        a.cap_block_off = d_cap_block_off.p;
-        a.total_blocks_cap = scan_blocks_cap;
-        a.events = d_events.p;
-        a.ev_hot = d_ev_hot.p;
-        a.app_vals = d_app_vals.p;
-        a.app_capacity = d_app_vals.n - 64;
-        a.errs = d_scan_errs.p;
-        a.err_capacity = d_scan_errs.n;
-        a.first = nullptr;
         a.first_dev = c ? d_carry.p + ((c - 1) & 1) : nullptr;
         a.pos_origin = ch.out0;
         a.totals_in = c ? d_chunk_totals.p + 2 * ((c - 1) & 1) : nullptr;
-        a.edge_overflow = &d_hdr.p->edge_overflow;
-        a.pre_codes = d_pre.p;
-        a.blk_in = d_blk_in.p;
-        a.rowz = d_rowz.p;
-        a.skipc = d_skipc.p;
-    a.sync_rec = d_sync_rec.p;
-    a.pre_plane = pre_plane;
-    a.sync_fail = &d_hdr.p->sync_fail;
-    a.sync_try = next_sync_mode();
-        a.sync_rec = d_sync_rec.p;
-        a.pre_plane = pre_plane;
-        a.sync_fail = &d_hdr.p->sync_fail;
-        a.sync_try = next_sync_mode();
         a.final_state = d_carry.p + (c & 1);
-        a.fallback = &d_hdr.p->scan_fallback;
-        a.fin_off = d_fin_off.p;
-        a.fsum = d_fsum.p;
         a.fin_ticket = d_fin_tickets.p + c;
-        if (++scan_stamp == 0) scan_stamp = 1;
-        a.run_stamp = scan_stamp;
-        a.fin_blocks_cap = scan_fin_cap;
+        a.run_stamp = next_scan_stamp();
         HIPCHK(launch_fsm_scan(a, s_chain, last ? ev[2] : nullptr));
     }
     scan_published = true;
@@ -946,52 +843,36 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
         const int rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
     }
-    if (!front_grid && front_streams(fp)) {
-        // persistent streaming form: capped residency, other contexts' kernels run beside it
-        HIPCHK(hipMemsetAsync(d_ctl.p, 0, sizeof(uint32_t) * kCtlChunkEnd, stream));
-        StreamCtl ctl{};
-        ctl.heads = d_ctl.p + kCtlHeads;
-        ctl.done = nullptr;
-        ctl.chunk_end = d_ctl.p + kCtlChunkEnd;
-        ctl.num_chunks = 0;
-        ctl.num_caps = run_caps;
-        ctl.waves_per_cu = stream_waves;
-        ctl.static_stride = dev_getenv("OOKD_STREAM_STRIDE") ? 1u : 0u;
+    // The tuned kernels go out as several grid launches of front_launch_tiles wave tiles: while a
+    // grid has workgroups left to dispatch, kernels of OTHER queues (the edges / state machine
+    // chain of the capture before, on another context's stream) are hardly dispatched at all --
+    // they get their turn when a front-end launch has drained (profiles/r02_pipeline_trace.txt),
+    // and once dispatched they run beside the next launch.  ev[0] / ev[1] = start of the first,
+    // end of the last launch.
+    const uint64_t tiles = tile_bits ? (uint64_t)fp.tiles_per_cap : 0;
+    const uint64_t per = tile_bits ? std::max<uint64_t>(1, front_launch_outputs / tile_bits / std::max(1u, run_caps)) : 0;
+    auto launch_all = [&]() -> hipError_t {
         front_launches = 1;
-        HIPCHK(launch_front_stream(fp, ctl, exact, false, stream, ev[0], ev[1]));
-    } else {
-        // The tuned kernels go out as several grid launches of front_launch_tiles wave tiles: while a
-        // grid has workgroups left to dispatch, kernels of OTHER queues (the edges / state machine
-        // chain of the capture before, on another context's stream) are hardly dispatched at all --
-        // they get their turn when a front-end launch has drained (profiles/r02_pipeline_trace.txt),
-        // and once dispatched they run beside the next launch.  ev[0] / ev[1] = start of the first,
-        // end of the last launch.
-        const uint32_t tile_bits = front_tile_bits(fp);
-        const uint64_t tiles = tile_bits ? (uint64_t)fp.tiles_per_cap : 0;
-        const uint64_t per = tile_bits ? std::max<uint64_t>(1, front_launch_outputs / tile_bits / std::max(1u, run_caps)) : 0;
-        auto launch_all = [&]() -> hipError_t {
-            front_launches = 1;
-            if (!tile_bits || tiles <= per + per / 2) return launch_front(fp, run_caps, exact, stream, ev[0], ev[1]);
-            front_launches = (uint32_t)((tiles + per - 1) / per);
-            for (uint64_t t = 0; t < tiles; t += per) {
-                const bool first = t == 0, last = t + per >= tiles;
-                const hipError_t e = launch_front(fp, run_caps, exact, stream, first ? ev[0] : nullptr,
-                                                  last ? ev[1] : nullptr, t, per);
-                if (e != hipSuccess) return e;
-            }
-            return hipSuccess;
-        };
-        if (gate) {
-            // wait + launch + publish under the lock: the event must be on its way before another
-            // context may wait for it
-            std::lock_guard<std::mutex> lock(gate->m);
-            hipEvent_t prev = gate->last;
-            if (prev && prev != ev[1]) HIPCHK(hipStreamWaitEvent(stream, prev, 0));
-            HIPCHK(launch_all());
-            gate->last = ev[1];
-        } else {
-            HIPCHK(launch_all());
+        if (!tile_bits || tiles <= per + per / 2) return launch_front(fp, run_caps, exact, stream, ev[0], ev[1]);
+        front_launches = (uint32_t)((tiles + per - 1) / per);
+        for (uint64_t t = 0; t < tiles; t += per) {
+            const bool first = t == 0, last = t + per >= tiles;
+            const hipError_t e = launch_front(fp, run_caps, exact, stream, first ? ev[0] : nullptr,
+                                              last ? ev[1] : nullptr, t, per);
+            if (e != hipSuccess) return e;
         }
+        return hipSuccess;
+    };
+    if (gate) {
+        // wait + launch + publish under the lock: the event must be on its way before another
+        // context may wait for it
+        std::lock_guard<std::mutex> lock(gate->m);
+        hipEvent_t prev = gate->last;
+        if (prev && prev != ev[1]) HIPCHK(hipStreamWaitEvent(stream, prev, 0));
+        HIPCHK(launch_all());
+        gate->last = ev[1];
+    } else {
+        HIPCHK(launch_all());
     }
     if (run_n_out > 0) HIPCHK(launch_edges(edge_params(), stream));
     return OOKD_OK;
@@ -1182,7 +1063,9 @@ int ookd_rx::run_state_machine(const FsmStateDev *first, bool fresh) {
     return OOKD_OK;
 }
 
-int ookd_rx::fsm_scan(const FsmStateDev *first) {
+// The scan's arguments that follow from the context (and, through fsm_params / publish_params, the run's
+// geometry): fsm_scan and run_pipelined add what is their run's or chunk's own.
+FsmScanArgs ookd_rx::scan_args() const {
     FsmScanArgs a{};
     a.f = fsm_params();
     a.D = scan_D;
@@ -1220,13 +1103,8 @@ int ookd_rx::fsm_scan(const FsmStateDev *first) {
     a.app_capacity = d_app_vals.n - 64;     // fin_msg reads whole 8-byte groups
     a.errs = d_scan_errs.p;
     a.err_capacity = d_scan_errs.n;
-    a.first = first;
     a.final_state = d_final_state.p;
     a.fallback = &d_hdr.p->scan_fallback;
-    if (run_caps > 1) {
-        HIPCHK(hipMemsetAsync(d_cap_fallback.p, 0, run_caps * sizeof(uint32_t), stream));
-        a.cap_fallback = d_cap_fallback.p;
-    }
     a.edge_overflow = &d_hdr.p->edge_overflow;
     a.pre_codes = d_pre.p;
     a.blk_in = d_blk_in.p;
@@ -1235,19 +1113,35 @@ int ookd_rx::fsm_scan(const FsmStateDev *first) {
     a.sync_rec = d_sync_rec.p;
     a.pre_plane = pre_plane;
     a.sync_fail = &d_hdr.p->sync_fail;
-    a.sync_try = next_sync_mode();
     a.fin_off = d_fin_off.p;
     a.fsum = d_fsum.p;
-    a.fin_ticket = d_fin_tickets.p + kMaxChunks;
-    if (++scan_stamp == 0) scan_stamp = 1;
-    a.run_stamp = scan_stamp;
     a.fin_blocks_cap = scan_fin_cap;
+    a.sync_try = sync_mode;
+    return a;
+}
+
+int ookd_rx::fsm_scan(const FsmStateDev *first) {
+    next_sync_mode();
+    FsmScanArgs a = scan_args();
+    a.first = first;
+    if (run_caps > 1) {
+        HIPCHK(hipMemsetAsync(d_cap_fallback.p, 0, run_caps * sizeof(uint32_t), stream));
+        a.cap_fallback = d_cap_fallback.p;
+    }
+    a.fin_ticket = d_fin_tickets.p + kMaxChunks;
+    a.run_stamp = next_scan_stamp();
     // totals / scan_fallback are still zero from the header memset of front_and_edges
     HIPCHK(launch_fsm_scan(a, stream, ev[2]));      // ev[2]: end of its last kernel
     scan_published = true;          // its last kernel also publishes
+    return dump_scan_debug();
+}
+
+// OOKD_DEBUG_SCAN: waits for the scan just queued and prints what its kernels left in d_debug
+int ookd_rx::dump_scan_debug() {
     static const char *const debug_scan = getenv("OOKD_DEBUG_SCAN");     // read once: this is the hot path
-    if (debug_scan) HIPCHK(hipStreamSynchronize(stream));
-    if (debug_scan && d_debug.p) {
+    if (!debug_scan) return OOKD_OK;
+    HIPCHK(hipStreamSynchronize(stream));
+    if (d_debug.p) {
         uint64_t dbg[64];
         HIPCHK(hipMemcpy(dbg, d_debug.p, sizeof(dbg), hipMemcpyDeviceToHost));
         fprintf(stderr, "[scan] block_sims phases: resume %llu gap+rep %llu uniq %llu sims %llu\n",
@@ -1273,7 +1167,7 @@ int ookd_rx::fsm_scan(const FsmStateDev *first) {
                     (unsigned long long)dbg[4 * i + 2], (unsigned long long)(dbg[4 * i + 3] & 0xffffffffu),
                     (unsigned long long)(dbg[4 * i + 3] >> 32));
     }
-    if (debug_scan && debug_scan[0] == '2') {
+    if (debug_scan[0] == '2') {
         uint32_t off[2];
         HIPCHK(hipMemcpy(off, d_cap_block_off.p, 8, hipMemcpyDeviceToHost));
         uint32_t ne32[2];
@@ -1325,6 +1219,21 @@ int ookd_rx::enqueue_publish() {
     return OOKD_OK;
 }
 
+// The publish kernel zeroed the device header: put the front end's counters back, minus the scan's
+// verdict and totals, for a second pass of the state machine over the same edges.  (publish_done:
+// the scan's last kernel counts its workgroups there to find the one that publishes.)
+int ookd_rx::rearm_header(const ResultHeader &seen) {
+    ResultHeader keep = seen;
+    keep.totals[0] = keep.totals[1] = 0;
+    keep.scan_fallback = 0;
+    keep.sync_fail = 0;
+    keep.publish_done = 0;
+    HIPCHK(hipMemcpyAsync(d_hdr.p, &keep, sizeof(keep), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    hdr_dirty = true;
+    return OOKD_OK;
+}
+
 // Waits for the run queued on the stream and turns it into host-side results.
 int ookd_rx::collect_results() {
     const uint64_t first = std::min<uint64_t>(kHostMsgFirst, msg_capacity);
@@ -1345,15 +1254,9 @@ int ookd_rx::collect_results() {
             // the walk from synchronising spans gave up and nothing was queued behind it: the scan again, composing
             // (and so for the next runs of this context)
             sync_backoff = kSyncBackoff;
-            ResultHeader keep = *h_hdr;
-            keep.totals[0] = keep.totals[1] = 0;
-            keep.scan_fallback = 0;
-            keep.sync_fail = 0;
-            keep.publish_done = 0;          // (the scan's last kernel counts its workgroups here to find the one that publishes)
-            HIPCHK(hipMemcpyAsync(d_hdr.p, &keep, sizeof(keep), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            hdr_dirty = true;
-            int rc = run_state_machine(pending_first_valid ? &pending_first : nullptr, true);
+            int rc = rearm_header(*h_hdr);
+            if (rc != OOKD_OK) return rc;
+            rc = run_state_machine(pending_first_valid ? &pending_first : nullptr, true);
             if (rc != OOKD_OK) return rc;
             return fetch_results();
         } else if (h_hdr->edge_overflow) {
@@ -1385,16 +1288,9 @@ int ookd_rx::collect_results() {
             if (getenv("OOKD_DEBUG")) {
                 fprintf(stderr, "[ookd] fsm scan refused (reason %u), using rounds\n", h_hdr->scan_fallback);
             }
-            // the publish kernel zeroed the device header: put the front end's
-            // counters back (minus the scan's verdict and totals) for the second pass
-            ResultHeader keep = *h_hdr;
-            keep.totals[0] = keep.totals[1] = 0;
-            keep.scan_fallback = 0;
-            keep.sync_fail = 0;
-            HIPCHK(hipMemcpyAsync(d_hdr.p, &keep, sizeof(keep), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            hdr_dirty = true;
-            int rc = fsm_to_fixpoint(pending_first_valid ? &pending_first : nullptr, true, false);
+            int rc = rearm_header(*h_hdr);
+            if (rc != OOKD_OK) return rc;
+            rc = fsm_to_fixpoint(pending_first_valid ? &pending_first : nullptr, true, false);
             if (rc != OOKD_OK) return rc;
             stats.fsm_path = 3;
             return fetch_results();
@@ -1478,6 +1374,420 @@ int ookd_rx::collect_results() {
 }
 
 // ---------------------------------------------------------------------------
+// context creation: one step per function, each false on failure (error text set)
+// ---------------------------------------------------------------------------
+namespace {
+
+// stages and their (padded) taps on the device
+bool setup_filter(ookd_rx &rx, const ookd_filter &filter) {
+    if (filter.stages.size() > (size_t)kMaxStages) {
+        set_error("filter has %zu stages, this build supports %d", filter.stages.size(), kMaxStages);
+        return false;
+    }
+    std::vector<float> taps_dev;
+    rx.num_stages = (uint32_t)filter.stages.size();
+    rx.total_decim = filter.total_decimation;
+    uint64_t mult = 1;
+    for (uint32_t s = 0; s < rx.num_stages; ++s) {
+        const auto &st = filter.stages[s];
+        FirStageDev d{};
+        d.decim = st.decimation;
+        d.ntaps = (uint32_t)st.taps.size();
+        d.ntaps_pad = ((d.ntaps + kTapChunk - 1) / kTapChunk) * kTapChunk;
+        d.tap_off = (uint32_t)taps_dev.size();
+        taps_dev.insert(taps_dev.end(), st.taps.begin(), st.taps.end());
+        // zero padding keeps sums bit-identical: acc + (+-0) == acc
+        taps_dev.resize(d.tap_off + d.ntaps_pad, 0.0f);
+        rx.stage[s] = d;
+        rx.halo_needed += (uint64_t)(d.ntaps - 1) * mult;
+        mult *= d.decim;
+    }
+    rx.taps0 = filter.stages[0].taps;
+    if (rx.d_taps.alloc(taps_dev.size()) != OOKD_OK) return false;
+    if (hipMemcpy(rx.d_taps.p, taps_dev.data(), taps_dev.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("tap upload failed");
+        return false;
+    }
+    return true;
+}
+
+// The matrix-core form of the front end (fir_mfma.hip) for taps prepared in mt, whose output is known to
+// within e_n (inputs up to 1, in units of 2048 LSB) or e_w (up to 16) per component.  Filters the band
+// scaling does not suit stay on the packed-VALU kernels: that is not a failure.
+bool setup_mfma(ookd_rx &rx, const MfmaTaps &mt, double e_n, double e_w) {
+    float lo_n, hi_n, lo_w, hi_w;
+    band_from_error(e_n, rx.p_star, lo_n, hi_n);
+    band_from_error(e_w, rx.p_star, lo_w, hi_w);
+    // the kernel compares in accumulator units; thresholds so far from the filter's range that the
+    // power-of-two scaling leaves the normal floats stay on the packed-VALU loop
+    if (!(mfma_scale_band(mt, lo_n, rx.p_lo_n) && mfma_scale_band(mt, hi_n, rx.p_hi_n) &&
+          mfma_scale_band(mt, lo_w, rx.p_lo_w) && mfma_scale_band(mt, hi_w, rx.p_hi_w))) {
+        return true;
+    }
+    // fl(y^2) = c^2 fl(z^2) needs y^2 clear of the subnormals (and of overflow) wherever it decides a bit
+    if (rx.p_star > 0.0f && !(rx.p_star >= 0x1p-100f && rx.p_star <= 0x1p100f)) return true;
+    if (rx.d_mfma_a.alloc(mt.image.size()) != OOKD_OK) return false;
+    if (hipMemcpy(rx.d_mfma_a.p, mt.image.data(), mt.image.size() * sizeof(uint16_t), hipMemcpyHostToDevice) !=
+        hipSuccess) {
+        set_error("tap image upload failed");
+        return false;
+    }
+    rx.mfma_c = mt.c;
+    // wave tiles per wave of a workgroup: more for the long filters, whose workgroups fill a CU and
+    // fetch a 20 / 36 KB image each (config2 sweep: 474 / 545 / 599 / 623 / 635 Gsamples/s at 2 / 4 / 8 / 16 / 32)
+    rx.mfma_g = mt.ksteps <= 6 ? 4u : mt.ksteps <= 10 ? 16u : 32u;
+    if (const char *g = dev_getenv("OOKD_MFMA_G")) rx.mfma_g = (uint32_t)std::min(4096, std::max(1, atoi(g)));
+    // one contiguous run of tiles per XCD: where the halo is a good share of a tile's window -- the decimate-by-4
+    // filter (96 of 1120 samples: 3.0 -> 2.8-2.9 ms per 16 GiB) and the long 1-stage filters (272 of 1296: 1 %)
+    rx.mfma_xcd = 2u | (mt.ksteps >= 10 ? 1u : 0u);
+    if (const char *x = dev_getenv("OOKD_MFMA_XCD")) rx.mfma_xcd = (uint32_t)atoi(x);
+    return true;
+}
+
+// Guard band of the tuned kernels (1 stage / decimation 1, and 2 x decimation 2; the generic kernel
+// always computes in reference order and ignores it), and the matrix-core form where the shape has one
+// and the caller does not ask for the packed-VALU loop.
+bool setup_front_form(ookd_rx &rx, const ookd_filter &filter, uint32_t flags) {
+    std::vector<std::vector<float>> st;
+    for (const auto &f : filter.stages) st.push_back(f.taps);
+    guard_band(st, rx.p_star, rx.p_lo, rx.p_hi);
+    if ((flags & OOKD_RX_FIR_VALU) || dev_getenv("OOKD_FIR_VALU")) return true;
+    MfmaTaps mt;
+    if (rx.num_stages == 2 && rx.stage[0].decim == 2 && rx.stage[1].decim == 2 &&
+        mfma_prepare_taps2(filter.stages[0].taps.data(), rx.stage[0].ntaps, filter.stages[1].taps.data(),
+                           rx.stage[1].ntaps, mt)) {
+        // the backend default shape (two decimate-by-2 stages) folded into one decimate-by-4 product
+        return setup_mfma(rx, mt, mfma_error_bound2(mt, guard_error(st, 1.0), false),
+                          mfma_error_bound2(mt, guard_error(st, 16.0), true));
+    }
+    // 1 stage, decimation 1, <= 256 taps
+    if (rx.num_stages == 1 && rx.stage[0].decim == 1 && mfma_prepare_taps(filter.stages[0].taps.data(), rx.stage[0].ntaps, mt)) {
+        return setup_mfma(rx, mt, mfma_error_bound(mt, rx.stage[0].ntaps, false), mfma_error_bound(mt, rx.stage[0].ntaps, true));
+    }
+    return true;
+}
+
+// The quiet shortcut: input levels below quiet_lsb cannot reach the threshold.
+void setup_quiet_skip(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg) {
+    if (!(cfg.threshold > 0.0f) || !std::isfinite(cfg.threshold) || (cfg.flags & OOKD_RX_NO_QUIET_SKIP)) return;
+    // |y_re|, |y_im| <= S * m with S = prod over stages of sum|h|, m = max |component| in
+    // the window, so |y| <= sqrt(2) * S * m; 0.1 % slack covers every rounding of the
+    // reference's float arithmetic (relative 1e-5 at most) many times over
+    double S = 1.0;
+    for (const auto &st : filter.stages) {
+        double ss = 0.0;
+        for (float t : st.taps) ss += std::fabs((double)t);
+        S *= ss;
+    }
+    if (S > 0.0) {
+        // |v| < quiet_lsb  <=>  |v|/2048 < level (complexf.h:68-77 scaling)
+        const double lvl = (double)cfg.threshold * 0.999 / (1.41421356237309515 * S) * 2048.0;
+        rx.quiet_lsb = lvl >= 32767.0 ? 32767 : (int)std::ceil(lvl);
+    }
+}
+
+// The state machine's tables on the device
+bool setup_device_tables(ookd_rx &rx, const ookd_device &device) {
+    const size_t ns = device.state_duration_us.size();
+    const size_t nt = device.trig_cond.size();
+    const bool big = ns > (size_t)kMaxStates || nt > (size_t)kMaxTriggers;
+    if (ns > (size_t)kMaxStatesBig || nt > (size_t)kMaxTriggersBig || device.num_bits > 254) {
+        set_error("device has %zu states / %zu triggers / %u bits, this build supports %d / %d / 254", ns, nt,
+                  device.num_bits, kMaxStatesBig, kMaxTriggersBig);
+        return false;
+    }
+    // the kernel counts elapsed samples in 32 bits (saturating)
+    auto too_long = [](const std::vector<uint64_t> &v) {
+        for (uint64_t x : v) {
+            if (x != ~0ull && x >= (1ull << 31)) return true;
+        }
+        return false;
+    };
+    if (too_long(device.state_kmin) || too_long(device.state_kmax) || too_long(device.state_kto) ||
+        too_long(device.trig_kmin) || too_long(device.trig_kmax)) {
+        set_error("a device duration/timeout exceeds 2^31 samples at this rate: unsupported");
+        return false;
+    }
+    std::unique_ptr<FsmTablesDev> t(new FsmTablesDev());
+    memset(t.get(), 0, sizeof(FsmTablesDev));
+    fill_fsm_tables(device, *t);
+    if (rx.d_tables.alloc(1) != OOKD_OK) return false;
+    if (hipMemcpy(rx.d_tables.p, t.get(), sizeof(FsmTablesDev), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("table upload failed");
+        return false;
+    }
+    if (big) {
+        // more than 64 states / triggers: the round form with the tables in LDS (the scan's tables and the
+        // lane-resident ones stop at 64)
+        const std::vector<uint32_t> w = big_tables(device, t->quiet_state);
+        if (rx.d_big.alloc(w.size()) != OOKD_OK) return false;
+        if (hipMemcpy(rx.d_big.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("table upload failed");
+            return false;
+        }
+        rx.big_device = true;
+    }
+    rx.have_fsm = true;
+    rx.num_bits = device.num_bits;
+    rx.h_tables = std::move(t);
+    return true;
+}
+
+// Capacities, and the buffers of the front end, the edges and the round form of the state machine
+bool setup_run_buffers(ookd_rx &rx, const ookd_rx_config &cfg) {
+    const uint64_t spb = cfg.samples_per_buffer;
+    // nominal decimated samples per state machine segment (~2^19 by default;
+    // segment_buffers expresses it in input buffers)
+    if (cfg.segment_buffers) {
+        rx.seg_len = std::max<uint64_t>(1, (uint64_t)cfg.segment_buffers * spb / rx.total_decim);
+    } else {
+        rx.seg_len = 1ull << 19;
+    }
+    rx.seg_len = std::min<uint64_t>(rx.seg_len, 1ull << 30);   // 32-bit offsets inside a segment
+    rx.msg_slots = cfg.message_slots ? cfg.message_slots : 32;
+    rx.err_slots = 32;
+    uint32_t blocks = 0, segs = 0;
+    rx.geometry(rx.max_samples, true, rx.max_n_in, rx.max_n_out, rx.max_words, blocks, segs);
+    rx.max_blocks = blocks;
+    rx.max_segs_per_cap = std::max<uint32_t>(segs, 1);
+    const uint64_t total_out = rx.max_n_out * rx.max_captures;
+    rx.edge_capacity = cfg.edge_capacity ? cfg.edge_capacity : total_out / 32 + (1u << 20);
+    if (rx.edge_capacity > 0xfffffff0ull) rx.edge_capacity = 0xfffffff0ull;
+    rx.msg_capacity = cfg.message_capacity ? cfg.message_capacity
+                                           : std::max<uint64_t>(1u << 16, (uint64_t)rx.max_captures * 64);
+
+    const size_t caps = rx.max_captures;
+    const size_t nseg = caps * rx.max_segs_per_cap;
+    int rc = OOKD_OK;
+    rc |= rx.d_bits.alloc(caps * rx.max_words + 64);
+    if (cfg.flags & OOKD_RX_KEEP_FIR) rc |= rx.d_fir.alloc(2 * caps * rx.max_n_out + 2);
+    rc |= rx.d_halo.alloc(2 * (rx.halo_needed + 4));
+    rc |= rx.d_blk_count.alloc(caps * blocks + 1);
+    rc |= rx.d_tile_info.alloc(caps * blocks * 16 + 16);       // smallest wave tile: 256 bits
+    if (const char *w = dev_getenv("OOKD_FRONT_LAUNCH_LOG2")) rx.front_launch_outputs = 1ull << std::min(40, std::max(16, atoi(w)));
+    rc |= rx.d_blk_offset.alloc(caps * blocks + 1 + kMaxChunks);     // (a pipelined run keeps one total per chunk)
+    rc |= rx.d_group_total.alloc((caps * blocks + kScanGroup - 1) / kScanGroup + 1);
+    rc |= rx.d_edges.alloc(rx.edge_capacity + 64);
+    rc |= rx.d_hdr.alloc(1);
+    rx.count_quiet = (cfg.flags & OOKD_RX_COUNT_QUIET) != 0;
+    if (rx.count_quiet) rc |= rx.d_quiet.alloc(kQuietCounters);
+    if (rx.count_quiet && rc == OOKD_OK && hipMemset(rx.d_quiet.p, 0, kQuietCounters * sizeof(uint32_t)) != hipSuccess) rc = OOKD_ERR_HIP;
+    if (rx.have_fsm) {
+        rc |= rx.d_seg_bounds.alloc(caps * (rx.max_segs_per_cap + 1));
+        rc |= rx.d_state_in.alloc(nseg);
+        rc |= rx.d_state_out.alloc(2 * nseg);
+        rc |= rx.d_seg_msgs.alloc(nseg * rx.msg_slots);
+        rc |= rx.d_msgs.alloc(rx.msg_capacity);
+        rc |= rx.d_seg_msg_count.alloc(nseg);
+        rc |= rx.d_seg_err_count.alloc(nseg);
+        rc |= rx.d_seg_errs.alloc(nseg * rx.err_slots);
+        if (getenv("OOKD_DEBUG")) rc |= rx.d_debug.alloc(nseg * 4 + 128);
+    }
+    return rc == OOKD_OK;
+}
+
+// The scan form of the state machine (fsm_scan.hip): its tables and buffers
+bool setup_scan(ookd_rx &rx, const ookd_device &device, const ookd_rx_config &cfg) {
+    const size_t caps = rx.max_captures;
+    // abstract states = states x bit counts + skip x2 + poison
+    rx.scan_S = (uint32_t)device.state_duration_us.size();
+    rx.scan_max_bits = device.num_bits;
+    rx.scan_D = rx.scan_S * (device.num_bits + 2) + 3;
+    rx.scan_ok = !(cfg.flags & OOKD_RX_FSM_ROUNDS) && rx.scan_D <= 384 && device.num_bits <= 254 && !rx.big_device;
+    if (!rx.scan_ok) return true;
+    int rc = OOKD_OK;
+    std::vector<uint16_t> stuck_src;        // normal codes an inert edge can leave stuck (domain extension)
+    std::vector<uint8_t> stuck_rows;
+    if (!(cfg.flags & OOKD_RX_SCAN_SIMS)) {
+        // span tables: packed result of a span as a step function of its length
+        std::vector<uint32_t> off, n0, pk;
+        std::vector<uint16_t> reach;
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool ok = build_leaf_tables(*rx.h_tables, cfg.samples_per_buffer, rx.total_decim, off, n0, pk,
+                                          reach, stuck_src, stuck_rows);
+        if (!ok) {
+            stuck_src.clear();
+            stuck_rows.clear();
+        }
+        if (getenv("OOKD_DEBUG")) {
+            size_t zeros = 0;
+            for (uint32_t v : pk) zeros += v == 0;
+            fprintf(stderr, "[ookd] span tables: %s, %zu intervals (%zu need simulation), %zu codes can get stuck, "
+                            "%zu codes reachable, %.1f ms\n",
+                    ok ? "built" : "REFUSED", n0.size(), zeros, stuck_src.size(), reach.size(),
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            if (getenv("OOKD_DEBUG")[0] == '2') {
+                for (size_t t = 0; t + 1 < off.size(); ++t) {
+                    fprintf(stderr, "[ookd]  row %zu L %zu:", t / 2, t % 2);
+                    for (uint32_t i = off[t]; i < off[t + 1]; ++i) fprintf(stderr, " %u:%08x", n0[i], pk[i]);
+                    fprintf(stderr, "\n");
+                }
+            }
+        }
+        if (ok && !reach.empty()) {
+            const uint32_t d0 = rx.scan_S * (device.num_bits + 2) + 3;
+            rx.scan_reach_base = 0;                // entries are code | level mask << 14, ascending in the code
+            for (uint16_t v : reach) rx.scan_reach_base += (v & 0x3fffu) < d0 ? 1u : 0u;
+            // ... then, for the composition of chunk tables, the codes met at level 0 and those met at
+            // level 1 as two plain lists (a chunk starts at one level: only that list is walked)
+            rx.scan_reach_n = (uint32_t)reach.size();
+            {
+                std::vector<uint16_t> l0, l1;
+                for (uint32_t i = 0; i < rx.scan_reach_base; ++i) {
+                    if (reach[i] & 0x4000u) l0.push_back((uint16_t)(reach[i] & 0x3fffu));
+                    if (reach[i] & 0x8000u) l1.push_back((uint16_t)(reach[i] & 0x3fffu));
+                }
+                rx.scan_reach_lv[0] = (uint32_t)l0.size();
+                rx.scan_reach_lv[1] = (uint32_t)l1.size();
+                reach.insert(reach.end(), l0.begin(), l0.end());
+                reach.insert(reach.end(), l1.begin(), l1.end());
+            }
+            rc |= rx.d_reach.alloc(reach.size());
+            if (rc == OOKD_OK && hipMemcpy(rx.d_reach.p, reach.data(), reach.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
+                rc = OOKD_ERR_HIP;
+            }
+        }
+        if (ok && !n0.empty()) {
+            rc |= rx.d_lt_off.alloc(off.size());
+            rc |= rx.d_lt_n0.alloc(n0.size());
+            rc |= rx.d_lt_pk.alloc(pk.size());
+            if (rc == OOKD_OK &&
+                (hipMemcpy(rx.d_lt_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                 hipMemcpy(rx.d_lt_n0.p, n0.data(), n0.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                 hipMemcpy(rx.d_lt_pk.p, pk.data(), pk.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+                rc = OOKD_ERR_HIP;
+            }
+            std::vector<uint32_t> merged = build_merged_rows(rx.scan_S, off, n0, pk);
+            rx.lt_merged_rows = (uint32_t)merged.size();
+            {
+                // (reach: the level lists were appended behind the scan_reach_n masked codes above)
+                const std::vector<uint16_t> masked(reach.begin(), reach.begin() + (reach.empty() ? 0 : rx.scan_reach_n));
+                append_sync_codes(merged, rx.scan_S, device.num_bits + 2, device.num_bits, masked);
+                rx.scan_sync = !(cfg.flags & OOKD_RX_SCAN_TABLES) && !dev_getenv("OOKD_SCAN_NO_SYNC");
+                if (const char *e = dev_getenv("OOKD_SYNC_MIN_EDGES")) rx.sync_min_edges = strtoull(e, nullptr, 0);
+            }
+            rc |= rx.d_lt_merged.alloc(merged.size());
+            if (rc == OOKD_OK && hipMemcpy(rx.d_lt_merged.p, merged.data(), merged.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+                rc = OOKD_ERR_HIP;
+            }
+        }
+    }
+    std::vector<uint4> image((fsm_scan_ltab_bytes() + 15) / 16);
+    rx.scan_D = fsm_scan_fill_ltab(image.data(), *rx.h_tables, cfg.samples_per_buffer, rx.total_decim,
+                                   stuck_src, stuck_rows);
+    rc |= rx.d_ltab.alloc(image.size());
+    if (rc == OOKD_OK && hipMemcpy(rx.d_ltab.p, image.data(), image.size() * 16, hipMemcpyHostToDevice) != hipSuccess) {
+        rc = OOKD_ERR_HIP;
+    }
+    rx.scan_leaf_block = fsm_scan_leaf_block(rx.scan_D, rx.scan_S, rx.scan_S * (rx.scan_max_bits + 2));
+    rx.scan_blocks_cap = (uint32_t)(rx.edge_capacity / rx.scan_leaf_block + caps + 8);
+    rc |= rx.d_block_tab.alloc((size_t)rx.scan_blocks_cap * ((rx.scan_D + 7u) & ~7u) + 64);
+    {
+        const size_t ngroups = rx.scan_blocks_cap / 16 + caps + 8;
+        rc |= rx.d_cap_group_off.alloc(caps + 1);
+        rc |= rx.d_group_tab.alloc(ngroups * ((rx.scan_D + 7u) & ~7u) + 64);
+        const size_t nsuper = rx.scan_blocks_cap / 64 + caps + 8;
+        rc |= rx.d_cap_super_off.alloc(caps + 1);
+        rc |= rx.d_super_tab.alloc(nsuper * ((rx.scan_D + 7u) & ~7u) + 64);
+        rc |= rx.d_super_in.alloc(nsuper);
+        rc |= rx.d_cap_end.alloc(2 * (caps + 8));         // + cap_first
+    }
+    rc |= rx.d_cap_block_off.alloc(caps + 1);
+    rc |= rx.d_events.alloc(rx.edge_capacity + caps + 8);
+    rc |= rx.d_ev_hot.alloc(rx.edge_capacity + caps + 8);
+    rc |= rx.d_app_vals.alloc(2 * (rx.edge_capacity + caps) + 512 * caps + 1024);
+    rc |= rx.d_scan_errs.alloc(1u << 16);
+    rc |= rx.d_cap_fallback.alloc(caps);
+    // (the walk from synchronising spans keeps a plane of entry codes per candidate)
+    rx.pre_plane = rx.scan_sync ? (size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64 : 0;
+    rc |= rx.d_pre.alloc(((size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64) * (rx.scan_sync ? 4 : 1));
+    rc |= rx.d_rowz.alloc((size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64);
+    rc |= rx.d_skipc.alloc((size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64);
+    rc |= rx.d_sync_rec.alloc(((size_t)rx.scan_blocks_cap + 8) * 10);     // records, digests, selections
+    rc |= rx.d_blk_in.alloc((size_t)rx.scan_blocks_cap + 16);
+    rc |= rx.d_final_state.alloc(caps);
+    rx.scan_fin_cap = (uint32_t)((rx.edge_capacity + caps) / fsm_scan_fin_block() + caps + 8);
+    rc |= rx.d_fin_off.alloc(caps + 1);
+    rc |= rx.d_fsum.alloc(4 * (size_t)rx.scan_fin_cap);
+    // stamped work counters (fsm_scan.hip: take_stamped_ticket): zeroed ONCE -- stamp 0 is no run's
+    rc |= rx.d_fin_tickets.alloc(kMaxChunks + 1);
+    if (rc == OOKD_OK && hipMemset(rx.d_fin_tickets.p, 0, (kMaxChunks + 1) * sizeof(unsigned long long)) != hipSuccess) rc = OOKD_ERR_HIP;
+    // stamped aggregates: the stamp half of every word must start out as "no run"
+    if (rc == OOKD_OK && hipMemset(rx.d_fsum.p, 0, rx.d_fsum.n * sizeof(uint64_t)) != hipSuccess) rc = OOKD_ERR_HIP;
+    return rc == OOKD_OK;
+}
+
+// Sparse front-end output and the pinned result buffers
+bool setup_results(ookd_rx &rx) {
+    // sparse front-end output (1-stage kernels with the quiet shortcut, no float dump): the bit
+    // words and tile infos start out zero and every run zeroes what the run before wrote
+    FrontParams probe = rx.front_params(nullptr, 0);
+    probe.n_out = rx.max_n_out;
+    rx.sparse = front_sparse_capable(probe) && !dev_getenv("OOKD_DENSE_BITS");
+    if (rx.sparse &&
+        (hipMemset(rx.d_bits.p, 0, rx.d_bits.n * sizeof(uint64_t)) != hipSuccess ||
+         hipMemset(rx.d_tile_info.p, 0, rx.d_tile_info.n * sizeof(uint32_t)) != hipSuccess)) {
+        set_error("hipMemset of the bit words failed");
+        return false;
+    }
+    if (hipHostMalloc(reinterpret_cast<void **>(&rx.h_hdr), sizeof(ResultHeader)) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&rx.h_msgs), rx.msg_capacity * sizeof(MsgDev)) != hipSuccess) {
+        set_error("hipHostMalloc failed");
+        return false;
+    }
+    memset(rx.h_hdr, 0, sizeof(ResultHeader));
+    if (hipHostGetDevicePointer(reinterpret_cast<void **>(&rx.h_hdr_dev), rx.h_hdr, 0) != hipSuccess ||
+        hipHostGetDevicePointer(reinterpret_cast<void **>(&rx.h_msgs_dev), rx.h_msgs, 0) != hipSuccess) {
+        set_error("pinned result buffers are not mapped into the device");
+        return false;
+    }
+    return true;
+}
+
+// The chunk pipeline: two internal streams, each on its own half of the CUs
+bool setup_pipeline(ookd_rx &rx, const ookd_rx_config &cfg) {
+    // off unless asked for (pipeline_chunk_samples, or OOKD_PIPELINE=1 for the default chunk): with the
+    // hardware-dispatched front end the chain's kernels are hardly dispatched while a front-end grid
+    // has workgroups pending, and the chunked run is slower than the whole one
+    uint64_t want = cfg.pipeline_chunk_samples;
+    if (!want && dev_getenv("OOKD_PIPELINE")) want = kPipeDefaultChunk;
+    rx.pipe_chunk_in = want ? want : kPipeDefaultChunk;
+    rx.pipe_ok = want != 0 && rx.have_fsm && rx.scan_ok && rx.tile_bits != 0 && !(cfg.flags & OOKD_RX_NO_PIPELINE) &&
+                 cfg.pipeline_chunk_samples != ~0ull && !dev_getenv("OOKD_NO_PIPELINE") &&
+                 rx.max_n_out >= 2 * (rx.pipe_chunk_in / rx.total_decim);
+    if (!rx.pipe_ok) return true;
+    // every other CU of every XCD for the front end, the rest for the chain (an UNEVEN mask
+    // slows the front end: the dispatcher deals workgroups evenly over the XCDs).
+    // OOKD_PIPE_MASKS=front,chain (hex, per 32 CUs; 0 = no mask) overrides.
+    uint32_t mf = 0x55555555u, mc = 0xAAAAAAAAu;
+    if (const char *m = dev_getenv("OOKD_PIPE_MASKS")) {
+        char *end = nullptr;
+        mf = (uint32_t)strtoul(m, &end, 16);
+        mc = (end && *end == ',') ? (uint32_t)strtoul(end + 1, nullptr, 16) : 0u;
+    }
+    auto make = [&](hipStream_t &s, uint32_t pattern) {
+        if (pattern == 0) return hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        uint32_t mask[8];
+        for (auto &w : mask) w = pattern;
+        hipError_t e = hipExtStreamCreateWithCUMask(&s, 8, mask);
+        if (e != hipSuccess) {          // (no CU masking on this system: plain streams still pipeline)
+            (void)hipGetLastError();
+            e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        }
+        return e;
+    };
+    if (make(rx.s_front, mf) != hipSuccess || make(rx.s_chain, mc) != hipSuccess ||
+        hipEventCreateWithFlags(&rx.ev_start, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&rx.ev_end, hipEventDisableTiming) != hipSuccess) {
+        set_error("creating the pipeline streams failed");
+        return false;
+    }
+    return rx.d_carry.alloc(2) == OOKD_OK && rx.d_chunk_totals.alloc(4) == OOKD_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 extern "C" {
@@ -1524,419 +1834,16 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
     rx->max_captures = cfg->max_captures ? cfg->max_captures : 1;
     rx->max_samples = cfg->max_samples;
 
-    // ---- filter ---------------------------------------------------------------
-    std::vector<float> taps_dev;
-    if (filter) {
-        if (filter->stages.size() > (size_t)kMaxStages) {
-            set_error("filter has %zu stages, this build supports %d", filter->stages.size(), kMaxStages);
-            return nullptr;
-        }
-        rx->num_stages = (uint32_t)filter->stages.size();
-        rx->total_decim = filter->total_decimation;
-        uint64_t mult = 1;
-        for (uint32_t s = 0; s < rx->num_stages; ++s) {
-            const auto &st = filter->stages[s];
-            FirStageDev d{};
-            d.decim = st.decimation;
-            d.ntaps = (uint32_t)st.taps.size();
-            d.ntaps_pad = ((d.ntaps + kTapChunk - 1) / kTapChunk) * kTapChunk;
-            d.tap_off = (uint32_t)taps_dev.size();
-            taps_dev.insert(taps_dev.end(), st.taps.begin(), st.taps.end());
-            // zero padding keeps sums bit-identical: acc + (+-0) == acc
-            taps_dev.resize(d.tap_off + d.ntaps_pad, 0.0f);
-            rx->stage[s] = d;
-            rx->halo_needed += (uint64_t)(d.ntaps - 1) * mult;
-            mult *= d.decim;
-        }
-        rx->taps0 = filter->stages[0].taps;
-        if (rx->d_taps.alloc(taps_dev.size()) != OOKD_OK) return nullptr;
-        if (hipMemcpy(rx->d_taps.p, taps_dev.data(), taps_dev.size() * sizeof(float),
-                      hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("tap upload failed");
-            return nullptr;
-        }
-    }
+    if (filter && !setup_filter(*rx, *filter)) return nullptr;
     rx->p_star = power_threshold(cfg->threshold);
     rx->p_lo = rx->p_hi = rx->p_star;
-    if (!rx->exact && filter) {
-        // used by the tuned kernels (1 stage / decimation 1, and 2 x decimation 2); the
-        // generic kernel always computes in reference order and ignores the band
-        std::vector<std::vector<float>> st;
-        for (const auto &f : filter->stages) st.push_back(f.taps);
-        guard_band(st, rx->p_star, rx->p_lo, rx->p_hi);
-        // 1 stage, decimation 1, <= 256 taps: the product runs on the matrix cores (fir_mfma.hip) unless the
-        // caller asks for the packed-VALU loop (or for the experimental streaming form, which only exists for it)
-        MfmaTaps mt;
-        bool use_mfma = false;
-        if (rx->num_stages == 2 && rx->stage[0].decim == 2 && rx->stage[1].decim == 2 && !(cfg->flags & OOKD_RX_FIR_VALU) &&
-            !dev_getenv("OOKD_FIR_VALU") &&
-            mfma_prepare_taps2(filter->stages[0].taps.data(), rx->stage[0].ntaps, filter->stages[1].taps.data(),
-                               rx->stage[1].ntaps, mt)) {
-            // the backend default shape (two decimate-by-2 stages) folded into one decimate-by-4 product
-            float lo_n, hi_n, lo_w, hi_w;
-            band_from_error(mfma_error_bound2(mt, guard_error(st, 1.0), false), rx->p_star, lo_n, hi_n);
-            band_from_error(mfma_error_bound2(mt, guard_error(st, 16.0), true), rx->p_star, lo_w, hi_w);
-            use_mfma = mfma_scale_band(mt, lo_n, rx->p_lo_n) && mfma_scale_band(mt, hi_n, rx->p_hi_n) &&
-                       mfma_scale_band(mt, lo_w, rx->p_lo_w) && mfma_scale_band(mt, hi_w, rx->p_hi_w);
-            if (rx->p_star > 0.0f && !(rx->p_star >= 0x1p-100f && rx->p_star <= 0x1p100f)) use_mfma = false;
-        }
-        if (rx->num_stages == 1 && rx->stage[0].decim == 1 && !(cfg->flags & OOKD_RX_FIR_VALU) &&
-            !dev_getenv("OOKD_FRONT_STREAM") && !dev_getenv("OOKD_FIR_VALU") &&
-            mfma_prepare_taps(filter->stages[0].taps.data(), rx->stage[0].ntaps, mt)) {
-            float lo_n, hi_n, lo_w, hi_w;
-            band_from_error(mfma_error_bound(mt, rx->stage[0].ntaps, false), rx->p_star, lo_n, hi_n);
-            band_from_error(mfma_error_bound(mt, rx->stage[0].ntaps, true), rx->p_star, lo_w, hi_w);
-            // the kernel compares in accumulator units; thresholds so far from the filter's range that the
-            // power-of-two scaling leaves the normal floats stay on the packed-VALU loop
-            use_mfma = mfma_scale_band(mt, lo_n, rx->p_lo_n) && mfma_scale_band(mt, hi_n, rx->p_hi_n) &&
-                       mfma_scale_band(mt, lo_w, rx->p_lo_w) && mfma_scale_band(mt, hi_w, rx->p_hi_w);
-            // fl(y^2) = c^2 fl(z^2) needs y^2 clear of the subnormals (and of overflow) wherever it decides a bit
-            if (rx->p_star > 0.0f && !(rx->p_star >= 0x1p-100f && rx->p_star <= 0x1p100f)) use_mfma = false;
-        }
-        if (use_mfma) {
-            if (rx->d_mfma_a.alloc(mt.image.size()) != OOKD_OK) return nullptr;
-            if (hipMemcpy(rx->d_mfma_a.p, mt.image.data(), mt.image.size() * sizeof(uint16_t),
-                          hipMemcpyHostToDevice) != hipSuccess) {
-                set_error("tap image upload failed");
-                return nullptr;
-            }
-            rx->mfma_c = mt.c;
-            // wave tiles per wave of a workgroup: more for the long filters, whose workgroups fill a CU and
-            // fetch a 20 / 36 KB image each (config2 sweep: 474 / 545 / 599 / 623 / 635 Gsamples/s at 2 / 4 / 8 / 16 / 32)
-            rx->mfma_g = mt.ksteps <= 6 ? 4u : mt.ksteps <= 10 ? 16u : 32u;
-            if (const char *g = dev_getenv("OOKD_MFMA_G")) rx->mfma_g = (uint32_t)std::min(4096, std::max(1, atoi(g)));
-            // one contiguous run of tiles per XCD: where the halo is a good share of a tile's window -- the decimate-by-4
-            // filter (96 of 1120 samples: 3.0 -> 2.8-2.9 ms per 16 GiB) and the long 1-stage filters (272 of 1296: 1 %)
-            rx->mfma_xcd = 2u | (mt.ksteps >= 10 ? 1u : 0u);
-            if (const char *x = dev_getenv("OOKD_MFMA_XCD")) rx->mfma_xcd = (uint32_t)atoi(x);
-        }
-    }
-    if (filter && cfg->threshold > 0.0f && std::isfinite(cfg->threshold) && !(cfg->flags & OOKD_RX_NO_QUIET_SKIP)) {
-        // |y_re|, |y_im| <= S * m with S = prod over stages of sum|h|, m = max |component| in
-        // the window, so |y| <= sqrt(2) * S * m; 0.1 % slack covers every rounding of the
-        // reference's float arithmetic (relative 1e-5 at most) many times over
-        double S = 1.0;
-        for (const auto &st : filter->stages) {
-            double ss = 0.0;
-            for (float t : st.taps) ss += std::fabs((double)t);
-            S *= ss;
-        }
-        if (S > 0.0) {
-            // |v| < quiet_lsb  <=>  |v|/2048 < level (complexf.h:68-77 scaling)
-            const double lvl = (double)cfg->threshold * 0.999 / (1.41421356237309515 * S) * 2048.0;
-            rx->quiet_lsb = lvl >= 32767.0 ? 32767 : (int)std::ceil(lvl);
-        }
-    }
-
-    // ---- state machine ------------------------------------------------------------
-    if (device) {
-        const size_t ns = device->state_duration_us.size();
-        const size_t nt = device->trig_cond.size();
-        const bool big = ns > (size_t)kMaxStates || nt > (size_t)kMaxTriggers;
-        if (ns > (size_t)kMaxStatesBig || nt > (size_t)kMaxTriggersBig || device->num_bits > 254) {
-            set_error("device has %zu states / %zu triggers / %u bits, this build supports %d / %d / 254", ns, nt,
-                      device->num_bits, kMaxStatesBig, kMaxTriggersBig);
-            return nullptr;
-        }
-        // the kernel counts elapsed samples in 32 bits (saturating)
-        auto too_long = [](const std::vector<uint64_t> &v) {
-            for (uint64_t x : v) {
-                if (x != ~0ull && x >= (1ull << 31)) return true;
-            }
-            return false;
-        };
-        if (too_long(device->state_kmin) || too_long(device->state_kmax) || too_long(device->state_kto) ||
-            too_long(device->trig_kmin) || too_long(device->trig_kmax)) {
-            set_error("a device duration/timeout exceeds 2^31 samples at this rate: unsupported");
-            return nullptr;
-        }
-        std::unique_ptr<FsmTablesDev> t(new FsmTablesDev());
-        memset(t.get(), 0, sizeof(FsmTablesDev));
-        fill_fsm_tables(*device, *t);
-        if (rx->d_tables.alloc(1) != OOKD_OK) return nullptr;
-        if (hipMemcpy(rx->d_tables.p, t.get(), sizeof(FsmTablesDev), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("table upload failed");
-            return nullptr;
-        }
-        if (big) {
-            // more than 64 states / triggers: the round form with the tables in LDS (the scan's tables and the
-            // lane-resident ones stop at 64)
-            const std::vector<uint32_t> w = big_tables(*device, t->quiet_state);
-            if (rx->d_big.alloc(w.size()) != OOKD_OK) return nullptr;
-            if (hipMemcpy(rx->d_big.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-                set_error("table upload failed");
-                return nullptr;
-            }
-            rx->big_device = true;
-        }
-        rx->have_fsm = true;
-        rx->num_bits = device->num_bits;
-        rx->h_tables = std::move(t);
-    }
-
-    // ---- capacities -------------------------------------------------------------------
-    const uint64_t spb = cfg->samples_per_buffer;
-    // nominal decimated samples per state machine segment (~2^19 by default;
-    // segment_buffers expresses it in input buffers)
-    if (cfg->segment_buffers) {
-        rx->seg_len = std::max<uint64_t>(1, (uint64_t)cfg->segment_buffers * spb / rx->total_decim);
-    } else {
-        rx->seg_len = 1ull << 19;
-    }
-    rx->seg_len = std::min<uint64_t>(rx->seg_len, 1ull << 30);   // 32-bit offsets inside a segment
-    rx->msg_slots = cfg->message_slots ? cfg->message_slots : 32;
-    rx->err_slots = 32;
-    uint32_t blocks = 0, segs = 0;
-    rx->geometry(rx->max_samples, true, rx->max_n_in, rx->max_n_out, rx->max_words, blocks, segs);
-    rx->max_blocks = blocks;
-    rx->max_segs_per_cap = std::max<uint32_t>(segs, 1);
-    const uint64_t total_out = rx->max_n_out * rx->max_captures;
-    rx->edge_capacity = cfg->edge_capacity ? cfg->edge_capacity : total_out / 32 + (1u << 20);
-    if (rx->edge_capacity > 0xfffffff0ull) rx->edge_capacity = 0xfffffff0ull;
-    rx->msg_capacity = cfg->message_capacity
-                           ? cfg->message_capacity
-                           : std::max<uint64_t>(1u << 16, (uint64_t)rx->max_captures * 64);
-
-    const size_t caps = rx->max_captures;
-    const size_t nseg = caps * rx->max_segs_per_cap;
-    int rc = OOKD_OK;
-    rc |= rx->d_bits.alloc(caps * rx->max_words + 64);
-    if (cfg->flags & OOKD_RX_KEEP_FIR) rc |= rx->d_fir.alloc(2 * caps * rx->max_n_out + 2);
-    rc |= rx->d_halo.alloc(2 * (rx->halo_needed + 4));
-    rc |= rx->d_blk_count.alloc(caps * blocks + 1);
-    rc |= rx->d_tile_info.alloc(caps * blocks * 16 + 16);       // smallest wave tile: 256 bits
-    rc |= rx->d_ctl.alloc(kCtlWords);
-    // the streaming (persistent) form is experimental: it caps the front end's residency, but is
-    // slower than the hardware-dispatched grid; OOKD_FRONT_STREAM=1 selects it
-    rx->front_grid = (cfg->flags & OOKD_RX_FRONT_GRID) != 0 || !dev_getenv("OOKD_FRONT_STREAM");
-    if (const char *w = dev_getenv("OOKD_STREAM_WAVES")) rx->stream_waves = (uint32_t)std::max(1, atoi(w));
-    if (const char *w = dev_getenv("OOKD_FRONT_LAUNCH_LOG2")) rx->front_launch_outputs = 1ull << std::min(40, std::max(16, atoi(w)));
-    rc |= rx->d_blk_offset.alloc(caps * blocks + 1 + kMaxChunks);     // (a pipelined run keeps one total per chunk)
-    rc |= rx->d_group_total.alloc((caps * blocks + kScanGroup - 1) / kScanGroup + 1);
-    rc |= rx->d_edges.alloc(rx->edge_capacity + 64);
-    rc |= rx->d_hdr.alloc(1);
-    rx->count_quiet = (cfg->flags & OOKD_RX_COUNT_QUIET) != 0;
-    if (rx->count_quiet) rc |= rx->d_quiet.alloc(kQuietCounters);
-    if (rx->count_quiet && rc == OOKD_OK && hipMemset(rx->d_quiet.p, 0, kQuietCounters * sizeof(uint32_t)) != hipSuccess) rc = OOKD_ERR_HIP;
-    if (rx->have_fsm) {
-        rc |= rx->d_seg_bounds.alloc(caps * (rx->max_segs_per_cap + 1));
-        rc |= rx->d_state_in.alloc(nseg);
-        rc |= rx->d_state_out.alloc(2 * nseg);
-        rc |= rx->d_seg_msgs.alloc(nseg * rx->msg_slots);
-        rc |= rx->d_msgs.alloc(rx->msg_capacity);
-        rc |= rx->d_seg_msg_count.alloc(nseg);
-        rc |= rx->d_seg_err_count.alloc(nseg);
-        rc |= rx->d_seg_errs.alloc(nseg * rx->err_slots);
-        if (getenv("OOKD_DEBUG")) rc |= rx->d_debug.alloc(nseg * 4 + 128);
-        // scan form: abstract states = states x bit counts + skip x2 + poison
-        rx->scan_S = (uint32_t)device->state_duration_us.size();
-        rx->scan_max_bits = device->num_bits;
-        rx->scan_D = rx->scan_S * (device->num_bits + 2) + 3;
-        rx->scan_ok = !(cfg->flags & OOKD_RX_FSM_ROUNDS) && rx->scan_D <= 384 && device->num_bits <= 254 && !rx->big_device;
-        std::vector<uint16_t> stuck_src;        // normal codes an inert edge can leave stuck (domain extension)
-        std::vector<uint8_t> stuck_rows;
-        if (rx->scan_ok && !(cfg->flags & OOKD_RX_SCAN_SIMS)) {
-            // span tables: packed result of a span as a step function of its length
-            std::vector<uint32_t> off, n0, pk;
-            std::vector<uint16_t> reach;
-            const auto t0 = std::chrono::steady_clock::now();
-            const bool ok = build_leaf_tables(*rx->h_tables, cfg->samples_per_buffer, rx->total_decim, off, n0, pk,
-                                              reach, stuck_src, stuck_rows);
-            if (!ok) {
-                stuck_src.clear();
-                stuck_rows.clear();
-            }
-            if (getenv("OOKD_DEBUG")) {
-                size_t zeros = 0;
-                for (uint32_t v : pk) zeros += v == 0;
-                fprintf(stderr, "[ookd] span tables: %s, %zu intervals (%zu need simulation), %zu codes can get stuck, "
-                                "%zu codes reachable, %.1f ms\n",
-                        ok ? "built" : "REFUSED", n0.size(), zeros, stuck_src.size(), reach.size(),
-                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-                if (getenv("OOKD_DEBUG")[0] == '2') {
-                    for (size_t t = 0; t + 1 < off.size(); ++t) {
-                        fprintf(stderr, "[ookd]  row %zu L %zu:", t / 2, t % 2);
-                        for (uint32_t i = off[t]; i < off[t + 1]; ++i) fprintf(stderr, " %u:%08x", n0[i], pk[i]);
-                        fprintf(stderr, "\n");
-                    }
-                }
-            }
-            if (ok && !reach.empty()) {
-                const uint32_t d0 = rx->scan_S * (device->num_bits + 2) + 3;
-                rx->scan_reach_base = 0;                // entries are code | level mask << 14, ascending in the code
-                for (uint16_t v : reach) rx->scan_reach_base += (v & 0x3fffu) < d0 ? 1u : 0u;
-                // ... then, for the composition of chunk tables, the codes met at level 0 and those met at
-                // level 1 as two plain lists (a chunk starts at one level: only that list is walked)
-                rx->scan_reach_n = (uint32_t)reach.size();
-                {
-                    std::vector<uint16_t> l0, l1;
-                    for (uint32_t i = 0; i < rx->scan_reach_base; ++i) {
-                        if (reach[i] & 0x4000u) l0.push_back((uint16_t)(reach[i] & 0x3fffu));
-                        if (reach[i] & 0x8000u) l1.push_back((uint16_t)(reach[i] & 0x3fffu));
-                    }
-                    rx->scan_reach_lv[0] = (uint32_t)l0.size();
-                    rx->scan_reach_lv[1] = (uint32_t)l1.size();
-                    reach.insert(reach.end(), l0.begin(), l0.end());
-                    reach.insert(reach.end(), l1.begin(), l1.end());
-                }
-                rc |= rx->d_reach.alloc(reach.size());
-                if (rc == OOKD_OK && hipMemcpy(rx->d_reach.p, reach.data(), reach.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-                    rc = OOKD_ERR_HIP;
-                }
-            }
-            if (ok && !n0.empty()) {
-                rc |= rx->d_lt_off.alloc(off.size());
-                rc |= rx->d_lt_n0.alloc(n0.size());
-                rc |= rx->d_lt_pk.alloc(pk.size());
-                if (rc == OOKD_OK &&
-                    (hipMemcpy(rx->d_lt_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                     hipMemcpy(rx->d_lt_n0.p, n0.data(), n0.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                     hipMemcpy(rx->d_lt_pk.p, pk.data(), pk.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
-                    rc = OOKD_ERR_HIP;
-                }
-                std::vector<uint32_t> merged = build_merged_rows(rx->scan_S, off, n0, pk);
-                rx->lt_merged_rows = (uint32_t)merged.size();
-                {
-                    // (reach: the level lists were appended behind the scan_reach_n masked codes above)
-                    const std::vector<uint16_t> masked(reach.begin(), reach.begin() + (reach.empty() ? 0 : rx->scan_reach_n));
-                    append_sync_codes(merged, rx->scan_S, device->num_bits + 2, device->num_bits, masked);
-                    rx->scan_sync = !(cfg->flags & OOKD_RX_SCAN_TABLES) && !dev_getenv("OOKD_SCAN_NO_SYNC");
-                    if (const char *e = dev_getenv("OOKD_SYNC_MIN_EDGES")) rx->sync_min_edges = strtoull(e, nullptr, 0);
-                }
-                rc |= rx->d_lt_merged.alloc(merged.size());
-                if (rc == OOKD_OK && hipMemcpy(rx->d_lt_merged.p, merged.data(), merged.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-                    rc = OOKD_ERR_HIP;
-                }
-            }
-        }
-        if (rx->scan_ok) {
-            std::vector<uint4> image((fsm_scan_ltab_bytes() + 15) / 16);
-            rx->scan_D = fsm_scan_fill_ltab(image.data(), *rx->h_tables, cfg->samples_per_buffer, rx->total_decim,
-                                            stuck_src, stuck_rows);
-            rc |= rx->d_ltab.alloc(image.size());
-            if (rc == OOKD_OK &&
-                hipMemcpy(rx->d_ltab.p, image.data(), image.size() * 16, hipMemcpyHostToDevice) != hipSuccess) {
-                rc = OOKD_ERR_HIP;
-            }
-            rx->scan_leaf_block = fsm_scan_leaf_block(rx->scan_D, rx->scan_S, rx->scan_S * (rx->scan_max_bits + 2));
-            rx->scan_blocks_cap = (uint32_t)(rx->edge_capacity / rx->scan_leaf_block + caps + 8);
-            rc |= rx->d_block_tab.alloc((size_t)rx->scan_blocks_cap * ((rx->scan_D + 7u) & ~7u) + 64);
-            {
-                const size_t ngroups = rx->scan_blocks_cap / 16 + caps + 8;
-                rc |= rx->d_cap_group_off.alloc(caps + 1);
-                rc |= rx->d_group_tab.alloc(ngroups * ((rx->scan_D + 7u) & ~7u) + 64);
-                const size_t nsuper = rx->scan_blocks_cap / 64 + caps + 8;
-                rc |= rx->d_cap_super_off.alloc(caps + 1);
-                rc |= rx->d_super_tab.alloc(nsuper * ((rx->scan_D + 7u) & ~7u) + 64);
-                rc |= rx->d_super_in.alloc(nsuper);
-                rc |= rx->d_cap_end.alloc(2 * (caps + 8));         // + cap_first
-            }
-            rc |= rx->d_cap_block_off.alloc(caps + 1);
-            rc |= rx->d_events.alloc(rx->edge_capacity + caps + 8);
-            rc |= rx->d_ev_hot.alloc(rx->edge_capacity + caps + 8);
-            rc |= rx->d_app_vals.alloc(2 * (rx->edge_capacity + caps) + 512 * caps + 1024);
-            rc |= rx->d_scan_errs.alloc(1u << 16);
-            rc |= rx->d_cap_fallback.alloc(caps);
-            // (the walk from synchronising spans keeps a plane of entry codes per candidate)
-            rx->pre_plane = rx->scan_sync ? (size_t)rx->scan_blocks_cap * rx->scan_leaf_block + 64 : 0;
-            rc |= rx->d_pre.alloc(((size_t)rx->scan_blocks_cap * rx->scan_leaf_block + 64) * (rx->scan_sync ? 4 : 1));
-            rc |= rx->d_rowz.alloc((size_t)rx->scan_blocks_cap * rx->scan_leaf_block + 64);
-            rc |= rx->d_skipc.alloc((size_t)rx->scan_blocks_cap * rx->scan_leaf_block + 64);
-            rc |= rx->d_sync_rec.alloc(((size_t)rx->scan_blocks_cap + 8) * 10);     // records, digests, selections
-            rc |= rx->d_blk_in.alloc((size_t)rx->scan_blocks_cap + 16);
-            rc |= rx->d_final_state.alloc(caps);
-            rx->scan_fin_cap = (uint32_t)((rx->edge_capacity + caps) / fsm_scan_fin_block() + caps + 8);
-            rc |= rx->d_fin_off.alloc(caps + 1);
-            rc |= rx->d_fsum.alloc(4 * (size_t)rx->scan_fin_cap);
-            // stamped work counters (fsm_scan.hip: take_stamped_ticket): zeroed ONCE -- stamp 0 is no run's
-            rc |= rx->d_fin_tickets.alloc(kMaxChunks + 1);
-            if (rc == OOKD_OK && hipMemset(rx->d_fin_tickets.p, 0, (kMaxChunks + 1) * sizeof(unsigned long long)) != hipSuccess) rc = OOKD_ERR_HIP;
-            // stamped aggregates: the stamp half of every word must start out as "no run"
-            if (rc == OOKD_OK && hipMemset(rx->d_fsum.p, 0, rx->d_fsum.n * sizeof(uint64_t)) != hipSuccess) rc = OOKD_ERR_HIP;
-        }
-    }
-    if (rc != OOKD_OK) return nullptr;
-    {
-        // sparse front-end output (1-stage kernels with the quiet shortcut, no float dump): the bit
-        // words and tile infos start out zero and every run zeroes what the run before wrote
-        FrontParams probe = rx->front_params(nullptr, 0);
-        probe.n_out = rx->max_n_out;
-        rx->sparse = front_sparse_capable(probe) && !dev_getenv("OOKD_DENSE_BITS");
-        if (rx->sparse &&
-            (hipMemset(rx->d_bits.p, 0, rx->d_bits.n * sizeof(uint64_t)) != hipSuccess ||
-             hipMemset(rx->d_tile_info.p, 0, rx->d_tile_info.n * sizeof(uint32_t)) != hipSuccess)) {
-            set_error("hipMemset of the bit words failed");
-            return nullptr;
-        }
-    }
-    if (hipHostMalloc(reinterpret_cast<void **>(&rx->h_hdr), sizeof(ResultHeader)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&rx->h_msgs), rx->msg_capacity * sizeof(MsgDev)) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        return nullptr;
-    }
-    memset(rx->h_hdr, 0, sizeof(ResultHeader));
-    if (hipHostGetDevicePointer(reinterpret_cast<void **>(&rx->h_hdr_dev), rx->h_hdr, 0) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void **>(&rx->h_msgs_dev), rx->h_msgs, 0) != hipSuccess) {
-        set_error("pinned result buffers are not mapped into the device");
-        return nullptr;
-    }
-    // ---- chunk pipeline: two internal streams, each on its own half of the CUs -----------------------
-    {
-        FrontParams probe = rx->front_params(nullptr, 0);
-        probe.n_out = rx->max_n_out;
-        const bool tuned = front_tile_bits(probe) != 0;
-        // off unless asked for (pipeline_chunk_samples, or OOKD_PIPELINE=1 for the default chunk): with the
-        // hardware-dispatched front end the chain's kernels are hardly dispatched while a front-end grid
-        // has workgroups pending, and the chunked run is slower than the whole one
-        uint64_t want = cfg->pipeline_chunk_samples;
-        if (!want && dev_getenv("OOKD_PIPELINE")) want = kPipeDefaultChunk;
-        rx->pipe_chunk_in = want ? want : kPipeDefaultChunk;
-        rx->pipe_ok = want != 0 && rx->have_fsm && rx->scan_ok && tuned && !(cfg->flags & OOKD_RX_NO_PIPELINE) &&
-                      cfg->pipeline_chunk_samples != ~0ull && !dev_getenv("OOKD_NO_PIPELINE") &&
-                      rx->max_n_out >= 2 * (rx->pipe_chunk_in / rx->total_decim);
-    }
-    if (rx->pipe_ok) {
-        // every other CU of every XCD for the front end, the rest for the chain (an UNEVEN mask
-        // slows the front end: the dispatcher deals workgroups evenly over the XCDs).
-        // OOKD_PIPE_MASKS=front,chain (hex, per 32 CUs; 0 = no mask) overrides.
-        uint32_t mf = 0x55555555u, mc = 0xAAAAAAAAu;
-        if (const char *m = dev_getenv("OOKD_PIPE_MASKS")) {
-            char *end = nullptr;
-            mf = (uint32_t)strtoul(m, &end, 16);
-            mc = (end && *end == ',') ? (uint32_t)strtoul(end + 1, nullptr, 16) : 0u;
-        }
-        auto make = [&](hipStream_t &s, uint32_t pattern) {
-            if (pattern == 0) return hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-            uint32_t mask[8];
-            for (auto &w : mask) w = pattern;
-            hipError_t e = hipExtStreamCreateWithCUMask(&s, 8, mask);
-            if (e != hipSuccess) {          // (no CU masking on this system: plain streams still pipeline)
-                (void)hipGetLastError();
-                e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-            }
-            return e;
-        };
-        bool made = make(rx->s_front, mf) == hipSuccess;
-        if (const char *k = dev_getenv("OOKD_PIPE_DUMMY")) {       // experiment: shift the queue -> pipe assignment
-            for (int i = 0; i < atoi(k); ++i) {
-                hipStream_t d = nullptr;
-                (void)hipStreamCreateWithFlags(&d, hipStreamNonBlocking);
-                // a queue only exists once something was submitted to it
-                (void)hipMemsetAsync(rx->d_hdr.p, 0, 4, d);
-                (void)hipStreamSynchronize(d);
-                rx->dummy_streams.push_back(d);         // destroyed with the context
-            }
-        }
-        if (!made || make(rx->s_chain, mc) != hipSuccess ||
-            hipEventCreateWithFlags(&rx->ev_start, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&rx->ev_end, hipEventDisableTiming) != hipSuccess) {
-            set_error("creating the pipeline streams failed");
-            return nullptr;
-        }
-        if (rx->d_carry.alloc(2) != OOKD_OK || rx->d_chunk_totals.alloc(4) != OOKD_OK) {
-            return nullptr;
-        }
-    }
+    if (filter && !rx->exact && !setup_front_form(*rx, *filter, cfg->flags)) return nullptr;
+    if (filter) setup_quiet_skip(*rx, *filter, *cfg);
+    if (device && !setup_device_tables(*rx, *device)) return nullptr;
+    if (!setup_run_buffers(*rx, *cfg)) return nullptr;
+    if (rx->have_fsm && !setup_scan(*rx, *device, *cfg)) return nullptr;
+    rx->tile_bits = front_tile_bits(rx->front_params(nullptr, 0));     // the front end's form is settled
+    if (!setup_results(*rx) || !setup_pipeline(*rx, *cfg)) return nullptr;
     rx->gate = static_cast<ookd_rx_gate *>(cfg->front_gate);
     // (tests: start the tile stamp near its wrap-around)
     if (const char *e = dev_getenv("OOKD_TILE_STAMP_START")) rx->tile_stamp = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), kTileStampMax);

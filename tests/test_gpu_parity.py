@@ -1130,20 +1130,21 @@ def test_context_is_reusable_across_sizes(ok, oracle, vectors):
 
 
 @pytest.mark.parametrize("filt", ["fs32_fs4", "fs128_fs16_dec4"])
-@pytest.mark.parametrize("chunk,stream_form,read_bits,stamp0", [(0, False, True, None), (32768, False, True, None), (0, True, True, None),
-                                                                (0, False, False, None), (32768, False, False, None),
-                                                                (0, False, False, 0xffff - 3), (0, False, True, 0xffff - 2)])
-def test_sparse_bit_words_do_not_leak_between_runs(ok, oracle, vectors, chunk, stream_form, read_bits, stamp0, filt, monkeypatch):
+# (the ids keep the shape they had when a case also chose between two front-end forms)
+@pytest.mark.parametrize("chunk,read_bits,stamp0", [pytest.param(0, True, None, id="0-False-True-None"),
+                                                    pytest.param(32768, True, None, id="32768-False-True-None"),
+                                                    pytest.param(0, False, None, id="0-False-False-None"),
+                                                    pytest.param(32768, False, None, id="32768-False-False-None"),
+                                                    pytest.param(0, False, 0xffff - 3, id="0-False-False-65532"),
+                                                    pytest.param(0, True, 0xffff - 2, id="0-False-True-65533")])
+def test_sparse_bit_words_do_not_leak_between_runs(ok, oracle, vectors, chunk, read_bits, stamp0, filt, monkeypatch):
     """The tuned front ends (1 stage; the two decimate-by-2 stages of the backend default) store nothing for quiet tiles: what earlier runs left in their words
     and tile infos carries those runs' stamps and must read as quiet (kernels.hpp: tile_live), for the
     edge stage, the state machine and -- after ookd_rx_get_bits has zeroed the stale tiles -- for the
     raw words.  Different captures of equal and of different lengths through one context, whole and
-    pipelined in chunks, hardware-dispatched and streaming front end, with the words read back after
+    pipelined in chunks, with the words read back after
     every run (which cleans up) and never (stale tiles of many runs pile up), and across the wrap of the
     16-bit stamp: bits, edges and messages of every run must be the oracle's."""
-    if stream_form:
-        monkeypatch.setenv("OOKD_DEVELOPER", "1")
-        monkeypatch.setenv("OOKD_FRONT_STREAM", "1")
     if stamp0 is not None:
         monkeypatch.setenv("OOKD_DEVELOPER", "1")
         monkeypatch.setenv("OOKD_TILE_STAMP_START", str(stamp0))
@@ -1152,8 +1153,6 @@ def test_sparse_bit_words_do_not_leak_between_runs(ok, oracle, vectors, chunk, s
     shift = 2 * 77000                       # the same waveform moved: pulses where A has silence
     b = np.concatenate([rng.integers(-40, 41, size=shift).astype(np.int16), a[:-shift]])
     c = rng.integers(-40, 41, size=a.size).astype(np.int16)         # silence: nothing may survive
-    if stream_form and filt != "fs32_fs4":
-        pytest.skip("the streaming form only exists for the 1-stage front end")
     f = _flt(ok, filt)
     of = _ofir(oracle, filt)
     d = _dev(ok, "p3l-nexa2012", RATE // of.total_decimation)
