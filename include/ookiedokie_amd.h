@@ -267,8 +267,42 @@ typedef struct ookd_rx_stats {
                                        first start -> last end                */
     uint32_t scan_entry_form;       /* how the scan found the leaves' entry states: 1 walk from
                                        synchronising spans, 2 composed block tables, 0 no scan */
-    uint32_t reserved;
+    uint32_t front_form;            /* the front-end kernel the run launched: OOKD_FRONT_* */
 } ookd_rx_stats;
+
+/* Front-end forms (ookd_rx_stats.front_form, ookd_front_info.form): which
+ * kernel computed the filter, power and threshold.  0 = no run yet. */
+enum {
+    OOKD_FRONT_NO_FILTER = 1,       /* no filter: threshold on the samples      */
+    OOKD_FRONT_GENERIC = 2,         /* any shape, reference order throughout    */
+    OOKD_FRONT_FIR1_VALU = 3,       /* 1 stage, decimation 1, <= 256 taps:
+                                       packed-VALU FMA + guard band             */
+    OOKD_FRONT_FIR1_VALU_EXACT = 4, /* ... reference order (OOKD_RX_EXACT_FIR)  */
+    OOKD_FRONT_FIR1_MFMA = 5,       /* ... matrix cores + guard band            */
+    OOKD_FRONT_FIR2_VALU = 6,       /* 2 x decimate-by-2 (<= 16, <= 32 taps):
+                                       packed-VALU FMA + guard band             */
+    OOKD_FRONT_FIR2_VALU_EXACT = 7, /* ... reference order (OOKD_RX_EXACT_FIR)  */
+    OOKD_FRONT_FIR2_MFMA = 8        /* ... folded decimate-by-4 on the matrix
+                                       cores + guard band                       */
+};
+
+/* The front end a context settled on at create time, and the forward error
+ * bounds its guard bands were built from.  Bounds are per component of a
+ * filter output, in output units (2048 LSB = 1): a sample whose power lies
+ * in the band around p_star is recomputed in the reference's order, so bits
+ * are the reference's as long as |y_kernel - y_ref| stays within them. */
+typedef struct ookd_front_info {
+    uint32_t form;                  /* OOKD_FRONT_* of a run started now       */
+    uint32_t mfma_ksteps;           /* K-steps of the matrix-core product (0 = none prepared) */
+    float p_star;                   /* smallest power whose sqrtf >= threshold */
+    float p_lo, p_hi;               /* the packed-VALU kernels' band           */
+    float mfma_c;                   /* matrix-core accumulator -> output scale */
+    double err_nominal;             /* matrix-core form, samples in [-2048, 2047] */
+    double err_wide;                /* matrix-core form, any int16 samples     */
+    double err_valu;                /* packed-VALU form, any int16 samples     */
+    double mfma_delta;              /* sum |h - (h1 + h2)|: what the two fp16
+                                       tap pieces do not carry                 */
+} ookd_front_info;
 
 ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
                         const ookd_device *device);
@@ -334,6 +368,7 @@ int ookd_scan_domain_info(const ookd_device *device,
 uint64_t ookd_rx_num_messages(const ookd_rx *rx);
 const ookd_message *ookd_rx_messages(const ookd_rx *rx);
 int ookd_rx_get_stats(const ookd_rx *rx, ookd_rx_stats *out);
+int ookd_rx_get_front_info(const ookd_rx *rx, ookd_front_info *out);
 
 /* Parity / recorder taps (device -> host copies of intermediate data):
  *   bits  : 1 bit per decimated sample, LSB-first in 64-bit words, per

@@ -44,6 +44,15 @@ RX_SCAN_SIMS = 32
 RX_NO_PIPELINE = 128
 RX_FIR_VALU = 256
 RX_SCAN_TABLES = 512
+# front-end forms (stats["front_form"], Receiver.front_info()["form"]): OOKD_FRONT_*
+FRONT_NO_FILTER = 1
+FRONT_GENERIC = 2
+FRONT_FIR1_VALU = 3
+FRONT_FIR1_VALU_EXACT = 4
+FRONT_FIR1_MFMA = 5
+FRONT_FIR2_VALU = 6
+FRONT_FIR2_VALU_EXACT = 7
+FRONT_FIR2_MFMA = 8
 DEFAULT_THRESHOLD = 0.1                 # ookiedokie_cfg.c:27
 DEFAULT_RATE = 3000000                  # ookiedokie_cfg.c:32
 DEFAULT_SAMPLES_PER_BUF = 8192          # ookiedokie_cfg.c:34
@@ -111,7 +120,16 @@ class RxStats(C.Structure):
         ("fir_kernel_ms", C.c_float), ("total_device_ms", C.c_float),
         ("quiet_waves", C.c_uint64), ("total_waves", C.c_uint64),
         ("pipeline_chunks", C.c_uint32), ("front_launches", C.c_uint32),
-        ("scan_entry_form", C.c_uint32), ("reserved", C.c_uint32),
+        ("scan_entry_form", C.c_uint32), ("front_form", C.c_uint32),
+    ]
+
+
+class FrontInfo(C.Structure):
+    _fields_ = [
+        ("form", C.c_uint32), ("mfma_ksteps", C.c_uint32),
+        ("p_star", C.c_float), ("p_lo", C.c_float), ("p_hi", C.c_float), ("mfma_c", C.c_float),
+        ("err_nominal", C.c_double), ("err_wide", C.c_double), ("err_valu", C.c_double),
+        ("mfma_delta", C.c_double),
     ]
 
 
@@ -176,6 +194,7 @@ _PROTOTYPES = {
     "ookd_rx_num_messages": (C.c_uint64, [C.c_void_p]),
     "ookd_rx_messages": (C.POINTER(Message), [C.c_void_p]),
     "ookd_rx_get_stats": (C.c_int, [C.c_void_p, C.POINTER(RxStats)]),
+    "ookd_rx_get_front_info": (C.c_int, [C.c_void_p, C.POINTER(FrontInfo)]),
     "ookd_rx_bit_words": (C.c_uint64, [C.c_void_p]),
     "ookd_rx_get_bits": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "ookd_rx_get_edges": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
@@ -642,6 +661,13 @@ class Receiver:
         s = RxStats()
         _check(lib().ookd_rx_get_stats(self._h, C.byref(s)))
         return {name: getattr(s, name) for name, _ in RxStats._fields_}
+
+    def front_info(self) -> dict:
+        """The front end this context runs (form: FRONT_*) and the per-component error bounds its guard
+        bands were built from, in output units (2048 LSB = 1)."""
+        f = FrontInfo()
+        _check(lib().ookd_rx_get_front_info(self._h, C.byref(f)))
+        return {name: getattr(f, name) for name, _ in FrontInfo._fields_}
 
     def _result(self) -> RxResult:
         n = int(lib().ookd_rx_num_messages(self._h))

@@ -992,6 +992,19 @@ static bool use_fir2(const FrontParams &p) {
            p.stage[0].ntaps <= Fir2Dec4::T1 && p.stage[1].ntaps <= Fir2Dec4::T2 && p.origin % 4 == 0;
 }
 
+uint32_t front_form(const FrontParams &p, bool exact) {
+    if (p.num_stages == 0) return OOKD_FRONT_NO_FILTER;
+    if (use_fir1(p)) {
+        if (front_uses_mfma(p) && !exact) return OOKD_FRONT_FIR1_MFMA;
+        return exact ? OOKD_FRONT_FIR1_VALU_EXACT : OOKD_FRONT_FIR1_VALU;
+    }
+    if (use_fir2(p)) {
+        if (front_uses_mfma2(p) && !exact) return OOKD_FRONT_FIR2_MFMA;
+        return exact ? OOKD_FRONT_FIR2_VALU_EXACT : OOKD_FRONT_FIR2_VALU;
+    }
+    return OOKD_FRONT_GENERIC;
+}
+
 uint64_t front_wave_tiles(const FrontParams &p) {
     if (p.num_stages == 0) return ((p.n_out + kFirTile - 1) / kFirTile) * (kFirTile / kWaveTile);
     if (use_fir1(p)) return ((p.n_out + kFirTile - 1) / kFirTile) * (kFirTile / (64 * fir1_R(p)));
@@ -1029,7 +1042,8 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
     FrontParams pp = p;
     void *args[] = {&pp};
     uint64_t grid = 0;
-    if (p.num_stages == 0) {
+    const uint32_t form = front_form(p, exact);
+    if (form == OOKD_FRONT_NO_FILTER) {
         // whole 4096-sample blocks, so every bit word of the capture is written
         range((p.n_out + kFirTile - 1) / kFirTile * kFirWaves, grid, pp);
         if (grid == 0) return hipSuccess;
@@ -1037,10 +1051,10 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
                                                 dim3((uint32_t)grid, num_captures), dim3(64), args, 0, stream, t0, t1, 0);
         return e != hipSuccess ? e : hipGetLastError();
     }
-    if (use_fir1(p) && front_uses_mfma(p) && !exact) {
+    if (form == OOKD_FRONT_FIR1_MFMA) {
         return launch_front_mfma(p, num_captures, stream, t0, t1, tile_begin, tile_count);
     }
-    if (use_fir1(p)) {
+    if (form == OOKD_FRONT_FIR1_VALU || form == OOKD_FRONT_FIR1_VALU_EXACT) {
         const size_t lds = fir1_lds_bytes(p);
         // whole 4096-output blocks, so every bit word of the capture is written
         const int R = fir1_R(p);
@@ -1061,10 +1075,10 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
         e = hipExtLaunchKernel(fn, dim3((uint32_t)grid, num_captures), dim3(64 * kFirWgWaves), args, lds_req, stream, t0, t1, 0);
         return e != hipSuccess ? e : hipGetLastError();
     }
-    if (use_fir2(p) && front_uses_mfma2(p) && !exact) {
+    if (form == OOKD_FRONT_FIR2_MFMA) {
         return launch_front_mfma2(p, num_captures, stream, t0, t1, tile_begin, tile_count);
     }
-    if (use_fir2(p)) {
+    if (form == OOKD_FRONT_FIR2_VALU || form == OOKD_FRONT_FIR2_VALU_EXACT) {
         const size_t lds = (size_t)kFir2Waves * Fir2Dec4::wave_bytes;
         range((p.n_out + (uint64_t)kFir2Waves * Fir2Dec4::F - 1) / ((uint64_t)kFir2Waves * Fir2Dec4::F), grid, pp);
         if (grid == 0) return hipSuccess;

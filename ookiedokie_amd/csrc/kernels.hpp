@@ -139,6 +139,8 @@ hipError_t ensure_dynamic_lds(const void *func, size_t bytes);
 hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact, hipStream_t stream,
                         hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, uint64_t tile_begin = 0,
                         uint64_t tile_count = ~0ull);
+// the kernel launch_front runs for this shape: OOKD_FRONT_* (it dispatches on this, so a run reports what ran)
+uint32_t front_form(const FrontParams &p, bool exact);
 // 1024-ish output windows ("wave tiles") the tuned kernels split a capture into
 // (0 when the generic kernel serves this shape).
 uint64_t front_wave_tiles(const FrontParams &p);

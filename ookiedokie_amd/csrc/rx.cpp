@@ -364,6 +364,10 @@ struct ookd_rx : RxHandles {
     float mfma_c = 0, p_lo_n = 0, p_hi_n = 0, p_lo_w = 0, p_hi_w = 0;
     uint32_t mfma_g = 0;
     uint32_t mfma_xcd = 2;          // FrontParams::mfma_xcd (OOKD_MFMA_XCD)
+    // forward bounds the bands were built from (ookd_rx_get_front_info), per component, output units
+    double err_n = 0, err_w = 0, err_valu = 0, mfma_delta = 0;
+    uint32_t mfma_ksteps = 0;
+    uint32_t run_form = 0;          // OOKD_FRONT_* the last run launched (front_form)
     int quiet_lsb = 0;              // 0 = the quiet shortcut never applies
     uint32_t tile_bits = 0;         // bits per wave tile of the front-end kernel (front_tile_bits), 0 = generic kernel
     bool exact = false;
@@ -756,6 +760,7 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     if (hdr_dirty) HIPCHK(hipMemsetAsync(d_hdr.p, 0, sizeof(ResultHeader), stream));
     hdr_dirty = true;
     FrontParams fp = front_params(d_iq, run_n_valid);
+    run_form = front_form(fp, exact);
     {
         const int rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
@@ -839,6 +844,7 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
     FrontParams fp = front_params(d_iq, stride);
     fp.halo = d_halo_ptr;
     fp.halo_len = halo_len;
+    run_form = front_form(fp, exact);
     {
         const int rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
@@ -1302,6 +1308,7 @@ int ookd_rx::collect_results() {
     stats.num_messages = 0;
     stats.num_errors = 0;
     stats.guard_recomputes = h_hdr->recompute;
+    stats.front_form = run_form;
     stats.total_waves = front_wave_tiles(front_params(nullptr, 0)) * run_caps;
     if (stats.total_waves) {
         if (count_quiet) {
@@ -1415,6 +1422,10 @@ bool setup_filter(ookd_rx &rx, const ookd_filter &filter) {
 // within e_n (inputs up to 1, in units of 2048 LSB) or e_w (up to 16) per component.  Filters the band
 // scaling does not suit stay on the packed-VALU kernels: that is not a failure.
 bool setup_mfma(ookd_rx &rx, const MfmaTaps &mt, double e_n, double e_w) {
+    rx.err_n = e_n;
+    rx.err_w = e_w;
+    rx.mfma_ksteps = mt.ksteps;
+    rx.mfma_delta = mt.delta;
     float lo_n, hi_n, lo_w, hi_w;
     band_from_error(e_n, rx.p_star, lo_n, hi_n);
     band_from_error(e_w, rx.p_star, lo_w, hi_w);
@@ -1451,6 +1462,7 @@ bool setup_front_form(ookd_rx &rx, const ookd_filter &filter, uint32_t flags) {
     std::vector<std::vector<float>> st;
     for (const auto &f : filter.stages) st.push_back(f.taps);
     guard_band(st, rx.p_star, rx.p_lo, rx.p_hi);
+    rx.err_valu = guard_error(st, 16.0);
     if ((flags & OOKD_RX_FIR_VALU) || dev_getenv("OOKD_FIR_VALU")) return true;
     MfmaTaps mt;
     if (rx.num_stages == 2 && rx.stage[0].decim == 2 && rx.stage[1].decim == 2 &&
@@ -2166,6 +2178,23 @@ const ookd_message *ookd_rx_messages(const ookd_rx *rx) {
 int ookd_rx_get_stats(const ookd_rx *rx, ookd_rx_stats *out) {
     if (!rx || !out) return OOKD_ERR_ARG;
     *out = rx->stats;
+    return OOKD_OK;
+}
+
+int ookd_rx_get_front_info(const ookd_rx *rx, ookd_front_info *out) {
+    if (!rx || !out) return OOKD_ERR_ARG;
+    ookd_front_info f{};
+    f.form = front_form(rx->front_params(nullptr, 0), rx->exact);
+    f.mfma_ksteps = rx->mfma_ksteps;
+    f.p_star = rx->p_star;
+    f.p_lo = rx->p_lo;
+    f.p_hi = rx->p_hi;
+    f.mfma_c = rx->mfma_c;
+    f.err_nominal = rx->err_n;
+    f.err_wide = rx->err_w;
+    f.err_valu = rx->err_valu;
+    f.mfma_delta = rx->mfma_delta;
+    *out = f;
     return OOKD_OK;
 }
 

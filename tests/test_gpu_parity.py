@@ -9,6 +9,7 @@ import json
 import os
 
 import contextlib
+import math
 
 import numpy as np
 import pytest
@@ -70,6 +71,20 @@ def _sync_walk_forced(on=True):
                 os.environ[k] = old[k]
 
 
+def _form_for(ok, of, exact=False, valu=False):
+    """the front-end kernel launch_front runs for a filter (the rules of kernels.hip front_form and rx.cpp
+    setup_front_form; thresholds within [2^-50, 2^50] and taps near unit gain: the matrix cores never refuse)"""
+    if of is None:
+        return ok.FRONT_NO_FILTER
+    n = [int(of.stage_taps(s).size) for s in range(of.num_stages)]
+    d = [int(of.decimation[s]) for s in range(of.num_stages)]
+    if d == [1] and -(-n[0] // 32) * 32 <= 256:
+        return ok.FRONT_FIR1_VALU_EXACT if exact else ok.FRONT_FIR1_VALU if valu else ok.FRONT_FIR1_MFMA
+    if d == [2, 2] and n[0] <= 16 and n[1] <= 32:
+        return ok.FRONT_FIR2_VALU_EXACT if exact else ok.FRONT_FIR2_VALU if valu else ok.FRONT_FIR2_MFMA
+    return ok.FRONT_GENERIC
+
+
 def _compare(ok, oracle, iq, filt, devname, spb=8192, thr=0.1, exact=False, check_fir=False,
              segment_buffers=0, rate=RATE, expect_scan=True):
     """Runs the capture through every form of the state machine (scan of
@@ -101,6 +116,7 @@ def _compare(ok, oracle, iq, filt, devname, spb=8192, thr=0.1, exact=False, chec
                              pipeline_chunk_samples=chunk, fir_valu=valu, scan_tables=bool(tables))
         got = rx.rx(iq)
         assert got.stats["decimated_samples"] == want.decimated
+        assert got.stats["front_form"] == _form_for(ok, of, exact, valu)
         if tables and got.stats["fsm_path"] == 1:
             assert got.stats["scan_entry_form"] == 2
         if chunk and expect_scan and spb % 4096 == 0 and n >= 16 * spb and got.stats["fsm_fallback_reason"] == 0:
@@ -416,7 +432,9 @@ def test_mfma_fir_tap_counts(ok, oracle, tmp_path, ntaps):
         scale = float(np.abs(taps).sum()) * float(np.abs(iq.astype(np.int32)).max()) / 2048.0
         for valu in (False, True):
             rx = ok.Receiver(f, None, max_samples=n, threshold=thr, edge_capacity=n + 64, keep_fir=True, fir_valu=valu)
-            rx.rx(iq)
+            got = rx.rx(iq)
+            form = ok.FRONT_GENERIC if ntaps > 256 else ok.FRONT_FIR1_VALU if valu else ok.FRONT_FIR1_MFMA
+            assert got.stats["front_form"] == form, (ntaps, wide, valu)
             assert (rx.bits() == want.bits).all(), (ntaps, wide, valu)
             assert list(rx.edges()) == list(edges_of(want.bits))
             y = rx.fir_output()
@@ -424,7 +442,8 @@ def test_mfma_fir_tap_counts(ok, oracle, tmp_path, ntaps):
             rx.close()
             # and without the float output (quiet shortcut armed, sparse words)
             rx = ok.Receiver(f, None, max_samples=n, threshold=thr, edge_capacity=n + 64, fir_valu=valu)
-            rx.rx(iq)
+            got = rx.rx(iq)
+            assert got.stats["front_form"] == form, (ntaps, wide, valu)
             assert (rx.bits() == want.bits).all(), (ntaps, wide, valu)
             rx.close()
 
@@ -453,7 +472,15 @@ def test_mfma_fir_tap_magnitudes(ok, oracle, tmp_path, scale):
     want = oracle.rx(iq, of, thr, None, 8192, want_bits=True)
     assert 0.2 < want.bits.mean() < 0.8
     rx = ok.Receiver(f, None, max_samples=n, threshold=thr, edge_capacity=n + 64)
-    rx.rx(iq)
+    got = rx.rx(iq)
+    # the matrix-core form unless setup_front_form refuses: tap scaling beyond 2^+-100 (mfma_prepare_taps), p_star
+    # outside [2^-100, 2^100], band edges that do not scale into normal floats in accumulator units (mfma_scale_band)
+    _, e = math.frexp(float(np.abs(taps.astype(np.float64)).max()))
+    sh = 15 - e
+    p = float(np.float32(thr)) ** 2
+    lc = math.log2(p) + 2 * (11 + sh)
+    refused = abs(sh) > 100 or not (2.0 ** -100 <= p <= 2.0 ** 100) or not (-125 < lc < 127)
+    assert got.stats["front_form"] == (ok.FRONT_FIR1_VALU if refused else ok.FRONT_FIR1_MFMA), (scale, refused)
     assert (rx.bits() == want.bits).all()
     rx.close()
 
@@ -476,6 +503,7 @@ def test_mfma_guard_band_forces_exact_recompute_255_taps(ok, oracle, tmp_path):
     rx = ok.Receiver(f, None, max_samples=n, edge_capacity=n + 1024)
     got = rx.rx(iq)
     want = oracle.rx(iq, of, 0.1, None, 8192, want_bits=True)
+    assert got.stats["front_form"] == ok.FRONT_FIR1_MFMA
     assert (rx.bits() == want.bits).all()
     assert got.stats["guard_recomputes"] > 20
     assert 0.05 < want.bits.mean() < 0.95
@@ -505,6 +533,7 @@ def test_guard_band_forces_exact_recompute(ok, oracle, filt):
     rx = ok.Receiver(f, None, max_samples=n, edge_capacity=n + 1024)
     got = rx.rx(iq)
     want = oracle.rx(iq, of, 0.1, None, 8192, want_bits=True)
+    assert got.stats["front_form"] == (ok.FRONT_FIR2_MFMA if of.num_stages == 2 else ok.FRONT_FIR1_MFMA)
     assert (rx.bits() == want.bits).all()
     assert got.stats["guard_recomputes"] > 20
     assert list(rx.edges()) == list(edges_of(want.bits))

@@ -54,16 +54,29 @@ def test_struct_layouts_match_header(tmp_path):
     assert C.sizeof(ok.FsmState) == 64
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ookiedokie_amd.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(ookd_rx_config), sizeof(ookd_rx_stats),\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu", sizeof(ookd_rx_config), sizeof(ookd_rx_stats),\n'
                    '  sizeof(ookd_message), sizeof(ookd_fsm_state), offsetof(ookd_rx_config, pipeline_chunk_samples),\n'
-                   '  offsetof(ookd_rx_stats, pipeline_chunks)); return 0; }\n')
+                   '  offsetof(ookd_rx_stats, pipeline_chunks));\n'
+                   '  printf(" %zu %zu", offsetof(ookd_rx_stats, front_form), sizeof(ookd_front_info));\n'
+                   '#define F(m) printf(" %zu", offsetof(ookd_front_info, m));\n'
+                   '  F(form) F(mfma_ksteps) F(p_star) F(p_lo) F(p_hi) F(mfma_c) F(err_nominal) F(err_wide) F(err_valu)\n'
+                   '  F(mfma_delta)\n'
+                   '  printf(" %d %d %d %d %d %d %d %d\\n", OOKD_FRONT_NO_FILTER, OOKD_FRONT_GENERIC, OOKD_FRONT_FIR1_VALU,\n'
+                   '         OOKD_FRONT_FIR1_VALU_EXACT, OOKD_FRONT_FIR1_MFMA, OOKD_FRONT_FIR2_VALU,\n'
+                   '         OOKD_FRONT_FIR2_VALU_EXACT, OOKD_FRONT_FIR2_MFMA); return 0; }\n')
     exe = tmp_path / "sizes"
     r = subprocess.run(["gcc", "-std=c99", "-I", os.path.dirname(ok.HEADER_PATH), str(src), "-o", str(exe)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
-    assert got == [C.sizeof(ok.RxConfig), C.sizeof(ok.RxStats), C.sizeof(ok.Message), C.sizeof(ok.FsmState),
-                   ok.RxConfig.pipeline_chunk_samples.offset, ok.RxStats.pipeline_chunks.offset]
+    assert got[:6] == [C.sizeof(ok.RxConfig), C.sizeof(ok.RxStats), C.sizeof(ok.Message), C.sizeof(ok.FsmState),
+                       ok.RxConfig.pipeline_chunk_samples.offset, ok.RxStats.pipeline_chunks.offset]
+    # front_form took the place of the last reserved word: size and offsets unchanged
+    assert C.sizeof(ok.RxStats) == 104 and ok.RxStats.front_form.offset == 100 == got[6]
+    assert got[7] == C.sizeof(ok.FrontInfo)
+    assert got[8:18] == [getattr(ok.FrontInfo, name).offset for name, _ in ok.FrontInfo._fields_]
+    assert got[18:] == [ok.FRONT_NO_FILTER, ok.FRONT_GENERIC, ok.FRONT_FIR1_VALU, ok.FRONT_FIR1_VALU_EXACT,
+                        ok.FRONT_FIR1_MFMA, ok.FRONT_FIR2_VALU, ok.FRONT_FIR2_VALU_EXACT, ok.FRONT_FIR2_MFMA]
 
 
 @pytest.mark.parametrize("name", ["fs32_fs4", "fs128_fs16_dec4", "unity1", "unity16"])

@@ -2,7 +2,9 @@
 """Randomised differential run of the matrix-core FIR form (csrc/fir_mfma.hip) on the GPU box: random filters
 (1..256 taps: windowed sincs, random, sparse, wide dynamic range), random captures (nominal / wide sample range,
 quiet and loud stretches, amplitudes hovering around the threshold), random thresholds and lengths; the bits of the
-matrix-core form and of the packed-VALU form must be the CPU oracle's, the floats within 1e-5 of the scale.
+matrix-core form and of the packed-VALU form must be the CPU oracle's, the floats within 1e-5 of the scale.  Which
+kernel ran comes from stats["front_form"]; the worst |y - y_ref| over the bound the guard band was built from
+(Receiver.front_info(): err_nominal / err_wide / err_valu) is kept per form.
 Not part of the test suite (minutes); prints a JSON summary.
 
     python tools/fuzz_mfma.py [--seconds 300] [--seed 1]
@@ -88,7 +90,10 @@ def main():
     rng = np.random.default_rng(args.seed)
     tmp = tempfile.mkdtemp()
     stats = dict(cases=0, receivers=0, samples=0, recomputes=0, mfma_cases=0, valu_only_cases=0, max_err_over_scale=0.0,
-                 mismatches=[])
+                 max_err_over_bound={}, mismatches=[])
+    mfma_forms = (ok.FRONT_FIR1_MFMA, ok.FRONT_FIR2_MFMA)
+    form_names = {ok.FRONT_FIR1_VALU: "fir1_valu", ok.FRONT_FIR1_MFMA: "fir1_mfma", ok.FRONT_FIR2_VALU: "fir2_valu",
+                  ok.FRONT_FIR2_MFMA: "fir2_mfma", ok.FRONT_GENERIC: "generic"}
     t_end = time.time() + args.seconds
     last = time.time()
     while time.time() < t_end:
@@ -128,12 +133,17 @@ def main():
         scale = float(np.abs(taps.astype(np.float64)).sum()) * float(np.abs(iq.astype(np.int32)).max()) / 2048.0
         stats["cases"] += 1
         stats["samples"] += n
+        wide = bool(iq.max() > 2047) or bool(iq.min() < -2048)
+        default_form = None
         for valu in (False, True):
             for keep in (False, True):
                 rx = ok.Receiver(flt, None, max_samples=n, threshold=thr, samples_per_buffer=spb, edge_capacity=n + 64,
                                  keep_fir=keep, fir_valu=valu)
                 got = rx.rx(iq)
                 stats["receivers"] += 1
+                form = int(got.stats["front_form"])
+                if not valu:
+                    default_form = form
                 bits = rx.bits()
                 okb = bits.size == want.bits.size and bool((bits == want.bits).all())
                 okf = True
@@ -142,6 +152,12 @@ def main():
                     err = float(np.abs(y - want.fir.astype(np.float64)).max()) / scale
                     if not valu:
                         stats["max_err_over_scale"] = max(stats["max_err_over_scale"], err)
+                    info = rx.front_info()
+                    bound = info["err_valu"] if form not in mfma_forms else info["err_wide" if wide else "err_nominal"]
+                    if form != ok.FRONT_GENERIC and bound > 0:
+                        r = float(np.abs(y - want.fir.astype(np.float64)).max()) / bound
+                        key = form_names.get(form, str(form)) + ("_wide" if wide else "_nominal")
+                        stats["max_err_over_bound"][key] = max(stats["max_err_over_bound"].get(key, 0.0), r)
                     okf = bool((np.abs(y - want.fir) <= 1e-5 * np.maximum(np.abs(want.fir), scale)).all())
                 if not valu and not keep:
                     stats["recomputes"] += int(got.stats["guard_recomputes"])
@@ -150,6 +166,10 @@ def main():
                                                     floats_ok=okf, seed=args.seed, case=stats["cases"],
                                                     first_diff=int(np.nonzero(bits != want.bits)[0][0]) if not okb and bits.size == want.bits.size else -1))
                 rx.close()
+        if default_form in mfma_forms:
+            stats["mfma_cases"] += 1
+        else:
+            stats["valu_only_cases"] += 1
         if len(stats["mismatches"]) > 5:
             break
     stats["seconds"] = args.seconds
