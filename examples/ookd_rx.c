@@ -27,7 +27,7 @@ static int fail(const char *what)
 int main(int argc, char **argv)
 {
     if (argc < 5) {
-        fprintf(stderr, "usage: %s <capture.sc16q11> <device.json> <filter.json|none> <samplerate> "
+        fprintf(stderr, "usage: %s <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> "
                         "[csv|pretty] [dig.csv]\n", argv[0]);
         return EXIT_FAILURE;
     }
@@ -72,6 +72,7 @@ int main(int argc, char **argv)
     rc.threshold = cfg.rx_threshold;
     rc.samples_per_buffer = cfg.samples_per_buffer;
     rc.max_samples = n ? n : 1;
+    rc.flags = (uint32_t) sdr_hip_file_sample_flags(sdr);   /* a .cs8 / .cu8 capture: an 8-bit context */
     rx = ookd_rx_create(&rc, filter, device);
     if (!rx) { fail("ookd_rx_create"); goto out; }
 

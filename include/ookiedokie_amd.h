@@ -189,7 +189,20 @@ enum {
      * for short edge lists and for captures without such spans (no one within
      * 512 edges).  Identical results; the flag exists so the tests can run
      * both (stats.scan_entry_form). */
-    OOKD_RX_SCAN_TABLES = 1u << 9
+    OOKD_RX_SCAN_TABLES = 1u << 9,
+    /* Sample format of every capture (and shard halo) the context is given.  Neither bit: SC16Q11,
+     * int16 I,Q, 4 bytes per sample (bladeRF).  One of them: 8-bit I,Q pairs, 2 bytes per sample --
+     *   CS8: signed bytes, the `.cs8` files HackRF tools write (hackrf_transfer);
+     *   CU8: unsigned bytes around 128, the `.cu8` files rtl_sdr writes.
+     * An 8-bit sample IS the SC16Q11 sample of 16 times its value:
+     *   CS8 v (int8)  = SC16Q11 16 * v,    CU8 u (uint8) = SC16Q11 16 * (u - 128),
+     * so the unpacked float is v / 128 = (16 v) / 2048 exactly, and a run computes, bit for bit,
+     * what the same context without the flag computes on the capture widened to int16 that way.
+     * The fused front ends (OOKD_FRONT_*_8) read the 2-byte samples themselves; nothing widens the
+     * capture in HBM first.  Zero padding is value 0 of the format (the byte 128 for CU8).  Both
+     * bits set: ookd_rx_create fails. */
+    OOKD_RX_SAMPLES_CS8 = 1u << 10,
+    OOKD_RX_SAMPLES_CU8 = 1u << 11
 };
 
 /* Contexts created with the same gate (and on the same device) queue their front-end kernels one
@@ -282,8 +295,16 @@ enum {
     OOKD_FRONT_FIR2_VALU = 6,       /* 2 x decimate-by-2 (<= 16, <= 32 taps):
                                        packed-VALU FMA + guard band             */
     OOKD_FRONT_FIR2_VALU_EXACT = 7, /* ... reference order (OOKD_RX_EXACT_FIR)  */
-    OOKD_FRONT_FIR2_MFMA = 8        /* ... folded decimate-by-4 on the matrix
+    OOKD_FRONT_FIR2_MFMA = 8,       /* ... folded decimate-by-4 on the matrix
                                        cores + guard band                       */
+    /* 8-bit contexts (OOKD_RX_SAMPLES_CS8 / _CU8): the fused forms that read the
+     * 2-byte samples themselves.  An 8-bit run that reports one of the numbers
+     * above ran that 16-bit kernel on a widened staging copy of the capture
+     * (OOKD_RX_FIR_VALU, OOKD_RX_EXACT_FIR, filters the matrix cores refuse,
+     * generic shapes); the staging buffer is allocated on the first such run. */
+    OOKD_FRONT_NO_FILTER_8 = 9,
+    OOKD_FRONT_FIR1_MFMA_8 = 10,
+    OOKD_FRONT_FIR2_MFMA_8 = 11
 };
 
 /* The front end a context settled on at create time, and the forward error
@@ -307,6 +328,11 @@ typedef struct ookd_front_info {
 ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
                         const ookd_device *device);
 void ookd_rx_destroy(ookd_rx *rx);
+/* Bytes per input sample of this context: 4 (SC16Q11) or 2 (CS8 / CU8).  Everywhere below a sample
+ * count, stride or halo length counts samples of that size, and a pointer to samples is a pointer
+ * to that format: int16 pairs or byte pairs, aligned to 2 bytes at least (16-byte aligned captures
+ * take the fast path). */
+uint32_t ookd_rx_sample_bytes(const ookd_rx *rx);
 
 /* Demodulate `num_captures` independent captures of `samples_per_capture`
  * SC16Q11 samples each, already resident in HBM at d_iq (int16 I,Q
@@ -331,14 +357,16 @@ int ookd_rx_submit_device(ookd_rx *rx, const void *d_iq,
 int ookd_rx_wait(ookd_rx *rx);
 
 /* Same over a host buffer: stages it to HBM first (PCIe-bound; never the
- * figure bench.py reports). */
+ * figure bench.py reports).  `iq` holds num_samples samples in the context's
+ * format (ookd_rx_sample_bytes each; cast the byte pairs of an 8-bit capture). */
 int ookd_rx_process_host(ookd_rx *rx, const int16_t *iq,
                          uint64_t num_samples);
 
 /* One shard of a larger capture (multi-GPU split).
  *   halo / halo_samples : the last input samples of the previous shard
  *       (host pointer, at least ookd_rx_halo_samples(rx) of them), or NULL
- *       for the first shard (zero history);
+ *       for the first shard (zero history); like the capture it is in the
+ *       context's sample format, halo_samples counting samples;
  *   last_shard : non-zero => zero pad to a whole buffer; otherwise
  *       num_samples must be a multiple of lcm(spb, total decimation);
  *   runs the front end (FIR, threshold, edges) and ONE speculative state
@@ -556,11 +584,17 @@ int sdr_hip_file_rx(void *handle, struct complexf *samples, unsigned int count);
 int sdr_hip_file_tx(void *handle, const struct complexf *samples,
                     unsigned int count);
 int sdr_hip_file_flush(void *handle);
+/* The capture's format follows its file name: `.cs8` / `.cu8` (any case) are 8-bit I,Q pairs as
+ * OOKD_RX_SAMPLES_CS8 / _CU8 describe them, anything else is SC16Q11.  sdr_hip_file_rx unpacks an
+ * 8-bit sample to v / 128.0f. */
 /* Extra, beyond the vtable: the whole capture as a device pointer
- * (int16 I,Q interleaved) for the fused path; loads the file to HBM on
+ * (raw, in the file's format) for the fused path; loads the file to HBM on
  * first use. */
 int sdr_hip_file_capture(void *handle, const void **d_iq,
                          uint64_t *num_samples);
+/* 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8: what to OR into ookd_rx_config.flags for a
+ * context that takes sdr_hip_file_capture's pointer. */
+int sdr_hip_file_sample_flags(void *handle);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,11 @@ RX_SCAN_SIMS = 32
 RX_NO_PIPELINE = 128
 RX_FIR_VALU = 256
 RX_SCAN_TABLES = 512
+# sample format of a context's captures: neither = SC16Q11; 8-bit I,Q pairs, CS8 v = SC16Q11 16 v (HackRF .cs8),
+# CU8 u = SC16Q11 16 (u - 128) (rtl_sdr .cu8)
+RX_SAMPLES_CS8 = 1024
+RX_SAMPLES_CU8 = 2048
+SAMPLE_FORMATS = {"sc16q11": (0, np.int16), "cs8": (RX_SAMPLES_CS8, np.int8), "cu8": (RX_SAMPLES_CU8, np.uint8)}
 # front-end forms (stats["front_form"], Receiver.front_info()["form"]): OOKD_FRONT_*
 FRONT_NO_FILTER = 1
 FRONT_GENERIC = 2
@@ -53,6 +58,9 @@ FRONT_FIR1_MFMA = 5
 FRONT_FIR2_VALU = 6
 FRONT_FIR2_VALU_EXACT = 7
 FRONT_FIR2_MFMA = 8
+FRONT_NO_FILTER_8 = 9                   # the fused forms of an 8-bit context
+FRONT_FIR1_MFMA_8 = 10
+FRONT_FIR2_MFMA_8 = 11
 DEFAULT_THRESHOLD = 0.1                 # ookiedokie_cfg.c:27
 DEFAULT_RATE = 3000000                  # ookiedokie_cfg.c:32
 DEFAULT_SAMPLES_PER_BUF = 8192          # ookiedokie_cfg.c:34
@@ -182,6 +190,7 @@ _PROTOTYPES = {
     "ookd_device_tables": (C.c_int, [C.c_void_p, C.POINTER(FsmTables)]),
     "ookd_rx_create": (C.c_void_p, [C.POINTER(RxConfig), C.c_void_p, C.c_void_p]),
     "ookd_rx_destroy": (None, [C.c_void_p]),
+    "ookd_rx_sample_bytes": (C.c_uint32, [C.c_void_p]),
     "ookd_rx_process_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "ookd_rx_submit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "ookd_scan_domain_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -236,6 +245,7 @@ _PROTOTYPES = {
     "sdr_hip_file_tx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
     "sdr_hip_file_flush": (C.c_int, [C.c_void_p]),
     "sdr_hip_file_capture": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "sdr_hip_file_sample_flags": (C.c_int, [C.c_void_p]),
 }
 
 
@@ -560,14 +570,18 @@ class Receiver:
                  quiet_skip: bool = True, count_quiet: bool = False, scan_sims: bool = False,
                  pipeline: bool = True, pipeline_chunk_samples: int = 0,
                  front_gate: Optional["FrontGate"] = None, fir_valu: bool = False,
-                 scan_tables: bool = False):
+                 scan_tables: bool = False, sample_format: str = "sc16q11"):
+        if sample_format not in SAMPLE_FORMATS:
+            raise ValueError("sample_format must be one of %s" % ", ".join(sorted(SAMPLE_FORMATS)))
+        self.sample_format = sample_format
+        fmt_flag, self._sample_dtype = SAMPLE_FORMATS[sample_format]
         cfg = RxConfig()
         cfg.hip_device = hip_device
         cfg.flags = ((RX_EXACT_FIR if exact_fir else 0) | (RX_KEEP_FIR if keep_fir else 0)
                      | (RX_FSM_ROUNDS if fsm_rounds else 0) | (0 if quiet_skip else RX_NO_QUIET_SKIP)
                      | (RX_COUNT_QUIET if count_quiet else 0) | (RX_SCAN_SIMS if scan_sims else 0)
                      | (0 if pipeline else RX_NO_PIPELINE)
-                     | (RX_FIR_VALU if fir_valu else 0) | (RX_SCAN_TABLES if scan_tables else 0))
+                     | (RX_FIR_VALU if fir_valu else 0) | (RX_SCAN_TABLES if scan_tables else 0) | fmt_flag)
         cfg.threshold = threshold
         cfg.samples_per_buffer = samples_per_buffer
         cfg.max_samples = max_samples
@@ -591,7 +605,7 @@ class Receiver:
     # -- runs ---------------------------------------------------------------
     def rx_device(self, d_iq_ptr: int, samples_per_capture: int, num_captures: int = 1,
                   stride: Optional[int] = None) -> RxResult:
-        """Captures already resident in HBM (int16 I,Q interleaved)."""
+        """Captures already resident in HBM (I,Q interleaved, in the context's sample format)."""
         _check(lib().ookd_rx_process_device(self._h, d_iq_ptr, num_captures, samples_per_capture,
                                             stride if stride is not None else samples_per_capture))
         return self._result()
@@ -623,8 +637,9 @@ class Receiver:
         return s
 
     def rx(self, iq: np.ndarray) -> RxResult:
-        """Host capture (staged over PCIe first)."""
-        iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+        """Host capture (staged over PCIe first): 2 n values I,Q of the context's sample format -- int16 for
+        "sc16q11" (anything numpy converts, as before), an int8 array for "cs8", a uint8 array for "cu8"."""
+        iq = self._samples(iq)
         _check(lib().ookd_rx_process_host(self._h, iq.ctypes.data, iq.size // 2))
         return self._result()
 
@@ -636,7 +651,7 @@ class Receiver:
             # a device (or host) tensor an RCCL recv landed in: handed over as it is, never staged through numpy
             hp, hn = halo.data_ptr(), halo.numel() // 2
         elif halo is not None:
-            halo = np.ascontiguousarray(halo, dtype=np.int16).reshape(-1)
+            halo = self._samples(halo)
             hp, hn = halo.ctypes.data, halo.size // 2
         _check(lib().ookd_rx_shard_begin(self._h, d_iq_ptr, num_samples, hp, hn, int(last_shard),
                                          C.byref(state_in) if state_in is not None else None,
@@ -647,6 +662,19 @@ class Receiver:
         out = FsmState()
         _check(lib().ookd_rx_shard_refine(self._h, C.byref(state_in), C.byref(out)))
         return self._result(), out
+
+    def _samples(self, iq) -> np.ndarray:
+        """A host array as contiguous samples of this context's format; an 8-bit context takes its own dtype only
+        (converting would silently reinterpret the other format's bytes)."""
+        if self.sample_format != "sc16q11" and np.asarray(iq).dtype != self._sample_dtype:
+            raise TypeError("this Receiver takes %s samples as %s, not %s"
+                            % (self.sample_format, np.dtype(self._sample_dtype).name, np.asarray(iq).dtype.name))
+        return np.ascontiguousarray(iq, dtype=self._sample_dtype).reshape(-1)
+
+    @property
+    def sample_bytes(self) -> int:
+        """Bytes per input sample: 4 (sc16q11) or 2 (cs8, cu8)."""
+        return int(lib().ookd_rx_sample_bytes(self._h))
 
     @property
     def halo_samples(self) -> int:
@@ -857,6 +885,16 @@ class HipFileBackend:
 
     def flush(self) -> int:
         return lib().sdr_hip_file_flush(self._h)
+
+    @property
+    def sample_flags(self) -> int:
+        """0, RX_SAMPLES_CS8 or RX_SAMPLES_CU8 by the file's name (sdr_hip_file_sample_flags)."""
+        return int(lib().sdr_hip_file_sample_flags(self._h))
+
+    @property
+    def sample_format(self) -> str:
+        """The `sample_format` a Receiver for capture() is created with."""
+        return {0: "sc16q11", RX_SAMPLES_CS8: "cs8", RX_SAMPLES_CU8: "cu8"}[self.sample_flags]
 
     def capture(self) -> Tuple[int, int]:
         p, n = C.c_void_p(0), C.c_uint64(0)

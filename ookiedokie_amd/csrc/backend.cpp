@@ -8,6 +8,7 @@
 // block is unpacked (:119) -- here by the unpack kernel on the GPU.  tx is
 // the reference's truncating pack (complexf.h:87-96) + fwrite; it is not on
 // the hot path and stays on the host.
+#include <cctype>
 #include <cerrno>
 #include <cstdio>
 #include <cstring>
@@ -35,6 +36,8 @@ struct HipFile {
     int16_t *d_capture = nullptr;
     uint64_t capture_samples = 0;
     std::string path;
+    uint32_t fmt = kFmtSc16;        // from the file name: .cs8 / .cu8, anything else SC16Q11
+    size_t sbytes = 4;              // bytes per sample of it
     Ingest ingest;
 
     ~HipFile() {
@@ -47,6 +50,16 @@ struct HipFile {
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
+
+// the capture's format by its file name's extension (no field for it in the reference's config struct)
+uint32_t format_of(const std::string &path) {
+    if (path.size() < 4) return kFmtSc16;
+    std::string ext = path.substr(path.size() - 4);
+    for (char &c : ext) c = (char)tolower((unsigned char)c);
+    if (ext == ".cs8") return kFmtCs8;
+    if (ext == ".cu8") return kFmtCu8;
+    return kFmtSc16;
+}
 
 }  // namespace
 
@@ -66,6 +79,8 @@ void *sdr_hip_file_init(const struct ookiedokie_cfg *cfg_v) {
     h->rx = (cfg->direction == 0);
     h->buf_len = cfg->samples_per_buffer;
     h->path = cfg->sdr_args;
+    h->fmt = format_of(h->path);
+    h->sbytes = sample_bytes(h->fmt);
     if (h->rx) {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -98,14 +113,16 @@ int sdr_hip_file_rx(void *handle, struct complexf *samples_v, unsigned int count
     unsigned total = 0;
     while (status == 0 && total < count) {
         const unsigned to_read = std::min(h->buf_len, count - total);
-        const size_t n = fread(h->h_raw, 4, to_read, h->file);
+        const size_t sb = h->sbytes;
+        const size_t n = fread(h->h_raw, sb, to_read, h->file);
         if (n == 0) {
             status = OOKD_FILE_EOF;
         } else if (n < to_read) {
-            memset(h->h_raw + 2 * n, 0, 4 * (size_t)(to_read - n));
+            // the format's zero (bladeRF_file.c:113-117 pads the unpacked zero)
+            memset(reinterpret_cast<char *>(h->h_raw) + sb * n, h->fmt == kFmtCu8 ? 0x80 : 0, sb * (size_t)(to_read - n));
         }
-        bool ok = hipMemcpyAsync(h->d_raw, h->h_raw, (size_t)to_read * 4, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        ok = ok && launch_unpack(h->d_raw, h->d_out, to_read, h->stream) == hipSuccess;
+        bool ok = hipMemcpyAsync(h->d_raw, h->h_raw, (size_t)to_read * sb, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        ok = ok && launch_unpack(h->d_raw, h->fmt, h->d_out, to_read, h->stream) == hipSuccess;
         ok = ok && hipMemcpyAsync(samples, h->d_out, (size_t)to_read * 8, hipMemcpyDeviceToHost, h->stream) == hipSuccess;
         ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
         if (!ok) {
@@ -152,25 +169,32 @@ int sdr_hip_file_capture(void *handle, const void **d_iq, uint64_t *num_samples)
         fseek(f, 0, SEEK_END);
         const long long bytes = ftell(f);
         fseek(f, 0, SEEK_SET);
-        const uint64_t n = bytes > 0 ? (uint64_t)bytes / 4 : 0;     // whole samples only
-        if (hipMalloc(reinterpret_cast<void **>(&h->d_capture), (n + 4) * 4) != hipSuccess) {
+        const size_t sb = h->sbytes;
+        const uint64_t n = bytes > 0 ? (uint64_t)bytes / sb : 0;    // whole samples only
+        if (hipMalloc(reinterpret_cast<void **>(&h->d_capture), (n + 4) * sb) != hipSuccess) {
             fclose(f);
-            set_error("hip_file: capture allocation of %llu bytes failed", (unsigned long long)n * 4);
+            set_error("hip_file: capture allocation of %llu bytes failed", (unsigned long long)(n * sb));
             return OOKD_ERR_NOMEM;
         }
         // pinned double-buffered ingest: fread of block k+1 overlaps the DMA of block k
-        const long long got = h->ingest.from_file(f, h->d_capture, n * 4);
+        const long long got = h->ingest.from_file(f, h->d_capture, n * sb);
         if (got < 0) {
             fclose(f);
             return OOKD_ERR_HIP;
         }
-        const uint64_t done = (uint64_t)got / 4;
+        const uint64_t done = (uint64_t)got / sb;
         fclose(f);
         h->capture_samples = done;
     }
     *d_iq = h->d_capture;
     *num_samples = h->capture_samples;
     return OOKD_OK;
+}
+
+int sdr_hip_file_sample_flags(void *handle) {
+    const HipFile *h = static_cast<const HipFile *>(handle);
+    if (!h) return 0;
+    return h->fmt == kFmtCs8 ? (int)OOKD_RX_SAMPLES_CS8 : h->fmt == kFmtCu8 ? (int)OOKD_RX_SAMPLES_CU8 : 0;
 }
 
 }  // extern "C"

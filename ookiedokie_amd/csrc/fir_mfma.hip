@@ -46,6 +46,10 @@
 // Everything around the product is the packed-VALU kernel's: raw non-temporal 16 B
 // loads, the quiet shortcut on the raw samples, sparse output with run stamps, tile
 // infos for the edge stage, no workgroup barrier (one wave = one workgroup).
+//
+// 8-bit captures (CS8 / CU8, template parameter FMT): the same kernels with everything between the global load and
+// the fp16 window in the format -- half as many raw vectors per window, byte -> fp16 of 16 v through v_perm_b32 and one
+// packed fma (expand8 / scale8), the quiet test on the bytes, the exact recompute through widen8, no wide branch.
 #include "kernels.hpp"
 #include "common.hpp"
 
@@ -70,13 +74,15 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 // half index of window sample j inside a plane: 8 pad halfs per 32 samples
 __host__ __device__ constexpr uint32_t mslot(uint32_t j) { return j + 8u * (j >> 5); }
 
-template <int KS>
+// FMT (kFmt*): the 8-bit formats' raw window is half as many bytes -- a 16 B vector holds 8 samples
+template <int KS, int FMT = (int)kFmtSc16>
 struct MfmaGeom {
     static constexpr uint32_t Tp = 16u * (KS - 2);              // tap history the window holds
     static constexpr uint32_t W = kMfmaTile + Tp;               // window samples (a multiple of 32)
     static constexpr uint32_t plane = mslot(W);                 // halfs per plane (a multiple of 8)
     static constexpr uint32_t lds_bytes = plane * 2u * 2u;      // re + im
-    static constexpr uint32_t nvec = W / 4u;                    // 16 B raw vectors
+    static constexpr uint32_t vsamples = FMT == (int)kFmtSc16 ? 4u : 8u;   // samples per 16 B raw vector
+    static constexpr uint32_t nvec = W / vsamples;              // 16 B raw vectors
     static constexpr int rounds = (int)((nvec + 63u) / 64u);
 };
 
@@ -108,30 +114,54 @@ __device__ __forceinline__ P uniform_ptr(P ptr) {
 __device__ __forceinline__ v2s as_v2sm(uint32_t w) { return __builtin_bit_cast(v2s, w); }
 
 typedef const __attribute__((address_space(1))) uint32_t *gptr32;
+typedef const __attribute__((address_space(1))) uint16_t *gptr16;
 typedef const __attribute__((address_space(1))) float *gptrf;
 
 // what the boundary handling needs, as scalars (a reference to the kernel's parameter block would put
 // the whole block on the stack)
-struct RawSrc {
-    gptr32 src;             // the capture
-    gptr32 halo;            // samples in front of it (newest last) or null
+template <int FMT>
+struct RawSrcT {
+    typedef typename std::conditional<FMT == (int)kFmtSc16, uint32_t, uint16_t>::type elem;     // one raw sample
+    typedef const __attribute__((address_space(1))) elem *ptr;
+    ptr src;                // the capture
+    ptr halo;               // samples in front of it (newest last) or null
     uint32_t halo_len;
     uint64_t n_valid;       // samples present; beyond: zeros (bladeRF_file.c:113-117)
 };
 
-__device__ __forceinline__ uint32_t fetch_raw_m(const RawSrc &rs, int64_t n) {
+typedef RawSrcT<(int)kFmtSc16> RawSrc;
+
+// sample n as the format holds it; outside the capture and its halo: the format's zero
+template <int FMT>
+__device__ __forceinline__ uint32_t fetch_fmt_m(const RawSrcT<FMT> &rs, int64_t n) {
+    const uint32_t z = FMT == (int)kFmtSc16 ? 0u : zero8<FMT>();
+    if (n < 0) {
+        const int64_t h = (int64_t)rs.halo_len + n;
+        if (h < 0 || !rs.halo) return z;
+        return rs.halo[h];
+    }
+    if ((uint64_t)n >= rs.n_valid) return z;
+    return rs.src[n];
+}
+
+// sample n as an SC16Q11 dword (I | Q << 16): what the exact recompute reads, whatever the format
+template <int FMT>
+__device__ __forceinline__ uint32_t fetch_raw_m(const RawSrcT<FMT> &rs, int64_t n) {
     if (n < 0) {
         const int64_t h = (int64_t)rs.halo_len + n;
         if (h < 0 || !rs.halo) return 0u;
-        return rs.halo[h];
+        if constexpr (FMT == (int)kFmtSc16) return rs.halo[h];
+        else return widen8<FMT>(rs.halo[h]);
     }
     if ((uint64_t)n >= rs.n_valid) return 0u;
-    return rs.src[n];
+    if constexpr (FMT == (int)kFmtSc16) return rs.src[n];
+    else return widen8<FMT>(rs.src[n]);
 }
 
 // Reference-order recomputation of output `n` (= input index: one stage, decimation 1)
 // from the capture itself: fir.c:313-318, separately rounded multiply and add.
-__device__ __forceinline__ float2 mfma_exact_output(const RawSrc &rs, gptrf taps, uint32_t T, int64_t n) {
+template <int FMT>
+__device__ __forceinline__ float2 mfma_exact_output(const RawSrcT<FMT> &rs, gptrf taps, uint32_t T, int64_t n) {
     const float s = 1.0f / 2048.0f;
     float re = 0.0f, im = 0.0f;
     for (uint32_t k = 0; k < T; ++k) {
@@ -169,6 +199,62 @@ __device__ __forceinline__ void cvt4(uint4 q, uint32_t mask, uint2 &re, uint2 &i
     im = make_uint2(cvt2<1>(w0, w1), cvt2<1>(w2, w3));
 }
 
+// ---- 8-bit formats ---------------------------------------------------------------------------------
+// A raw dword holds two samples, I0 Q0 I1 Q1.  With u = the byte as CU8 holds it (CS8: v ^ 0x80 = v + 128), the
+// half 0x6400 | u is the fp16 number 1024 + u (ulp 1 there): one v_perm_b32 puts two bytes of a plane under two
+// 0x64 bytes.  These halfs order like u as unsigned 16-bit integers -- the quiet test runs on them -- and one
+// packed fma, 16 * (1024 + u) - 18432 = 16 (u - 128), makes the window value: exact (a 12-bit integer times 16),
+// nominal (|.| <= 2048), the factor 16 in the sample and nothing folded into mfma_c or the bands.
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef unsigned short v2us __attribute__((ext_vector_type(2)));
+
+template <int FMT>
+__device__ __forceinline__ void expand8(uint32_t w, uint32_t &re, uint32_t &im) {
+    if (FMT == (int)kFmtCs8) w ^= 0x80808080u;
+    re = __builtin_amdgcn_perm(0x64646464u, w, 0x04020400u);
+    im = __builtin_amdgcn_perm(0x64646464u, w, 0x04030401u);
+}
+
+__device__ __forceinline__ uint32_t scale8(uint32_t t) {
+    const h2 k = {(_Float16)16.0f, (_Float16)16.0f}, b = {(_Float16)-18432.0f, (_Float16)-18432.0f};
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_fma(__builtin_bit_cast(h2, t), k, b));
+}
+
+// eight raw samples -> eight fp16 I and eight fp16 Q
+template <int FMT>
+__device__ __forceinline__ void cvt8(uint4 q, uint4 &re, uint4 &im) {
+    uint32_t r0, r1, r2, r3, i0, i1, i2, i3;
+    expand8<FMT>(q.x, r0, i0);
+    expand8<FMT>(q.y, r1, i1);
+    expand8<FMT>(q.z, r2, i2);
+    expand8<FMT>(q.w, r3, i3);
+    re = make_uint4(scale8(r0), scale8(r1), scale8(r2), scale8(r3));
+    im = make_uint4(scale8(i0), scale8(i1), scale8(i2), scale8(i3));
+}
+
+// The quiet test of an 8-bit window.  loud: some |I| or |Q| >= quiet_lsb, which is in SC16Q11 LSB whatever the
+// format -- the window is quiet exactly when its widened copy is: 16 |v| < L <=> |v| <= (L - 1) >> 4.  (No 8-bit
+// sample lies beyond +-2048: there is no "wide" to find.)
+template <int FMT, int ROUNDS>
+__device__ __forceinline__ void window_levels8(const uint4 (&q)[ROUNDS], int L, bool &loud) {
+    v2us mx = (v2us){0x6480, 0x6480}, mn = mx;              // value 0, as the 16-bit test starts from
+#pragma unroll
+    for (int i = 0; i < ROUNDS; ++i) {
+        const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t re, im;
+            expand8<FMT>(w[k], re, im);
+            const v2us a = __builtin_bit_cast(v2us, re), b = __builtin_bit_cast(v2us, im);
+            mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(a, b));
+            mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(a, b));
+        }
+    }
+    const int m = (L - 1) >> 4;                             // quiet: -m <= v <= m
+    const uint32_t hi = 0x6480u + (uint32_t)(m < 127 ? m : 127), lo = 0x6480u - (uint32_t)(m < 128 ? m : 128);
+    loud = L <= 0 || mx.x > hi || mx.y > hi || mn.x < lo || mn.y < lo;
+}
+
 // Workgroup = kMfmaWaves wavefronts that share ONE copy of the A-fragment image in LDS (8 KB with 32
 // taps, 36 KB with 255) and otherwise work alone: each wave pulls tiles (FrontParams::mfma_g per wave)
 // from a ticket in LDS, so a wave that drew loud tiles does not hold the others up, and a quiet tile costs
@@ -202,8 +288,9 @@ __host__ __device__ constexpr uint32_t mfma_lds_bytes() {
     return (uint32_t)KS * 2u * 1024u + kMfmaCtlBytes + (uint32_t)mfma_waves<KS>() * MfmaGeom<KS>::lds_bytes;
 }
 
-struct MfmaTileCtx {            // uniform per workgroup
-    RawSrc rs;
+template <int FMT>
+struct MfmaTileCtxT {           // uniform per workgroup
+    RawSrcT<FMT> rs;
     uint32_t *ctl;              // LDS: [0] next ticket, [1] image ready
     uint32_t tickets;           // per workgroup
     uint64_t tile_base, tile_end;
@@ -217,7 +304,8 @@ struct MfmaTileCtx {            // uniform per workgroup
 // XCD then goes through ONE contiguous eighth of the launch, and the halo a tile shares with the next one (96 of 1120
 // samples for the decimate-by-4 filter) is read by the same XCD twice -- the second time from its L2 -- instead of by
 // two XCDs from memory once each.
-__device__ __forceinline__ bool mfma_take_ticket(const MfmaTileCtx &c, uint32_t tid, uint64_t &tile) {
+template <int FMT>
+__device__ __forceinline__ bool mfma_take_ticket(const MfmaTileCtxT<FMT> &c, uint32_t tid, uint64_t &tile) {
     uint32_t tk = 0;
     if (tid == 0) tk = __hip_atomic_fetch_add(&c.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
@@ -226,17 +314,18 @@ __device__ __forceinline__ bool mfma_take_ticket(const MfmaTileCtx &c, uint32_t 
     return tk < c.tickets && v + c.tile_base < c.tile_end;
 }
 
-template <int KS>
-__device__ __forceinline__ bool mfma_interior(const MfmaTileCtx &c, uint64_t tile) {
+// (the window starts a multiple of 32 samples into the capture: 16-byte aligned with the capture at 2 B per sample too)
+template <int KS, int FMT>
+__device__ __forceinline__ bool mfma_interior(const MfmaTileCtxT<FMT> &c, uint64_t tile) {
     const uint64_t t0 = tile * kMfmaTile;
     return c.aligned16 && t0 >= MfmaGeom<KS>::Tp && t0 + kMfmaTile <= c.rs.n_valid;
 }
 
-// vector v <-> input samples t0 - Tp + 4v .. + 3
-template <int KS>
-__device__ __forceinline__ void mfma_issue_loads(const MfmaTileCtx &c, uint64_t tile, uint32_t tid,
-                                                 uint4 (&q)[MfmaGeom<KS>::rounds]) {
-    using Gm = MfmaGeom<KS>;
+// vector v <-> input samples t0 - Tp + 4v .. + 3 (8-bit formats: + 8v .. + 7)
+template <int KS, int FMT>
+__device__ __forceinline__ void mfma_issue_loads(const MfmaTileCtxT<FMT> &c, uint64_t tile, uint32_t tid,
+                                                 uint4 (&q)[MfmaGeom<KS, FMT>::rounds]) {
+    using Gm = MfmaGeom<KS, FMT>;
     const gbytes src4 = uniform_ptr((gbytes)(c.rs.src + (tile * kMfmaTile - Gm::Tp)));
 #pragma unroll
     for (int i = 0; i < Gm::rounds; ++i) {
@@ -249,26 +338,39 @@ __device__ __forceinline__ void mfma_issue_loads(const MfmaTileCtx &c, uint64_t 
 
 // first / last tiles of a capture, halo of a shard, unaligned pointers: sample by sample, staged raw
 // through the (free) LDS window so that the code stays a compact loop
-template <int KS>
-__device__ __noinline__ void mfma_boundary_stage(RawSrc rs, uint64_t t0, uint32_t tid, uint4 *stage) {
-    using Gm = MfmaGeom<KS>;
-    for (uint32_t v = tid; v < Gm::nvec; v += 64u) {
-        const int64_t s0 = (int64_t)t0 - (int64_t)Gm::Tp + 4 * (int64_t)v;
-        uint4 w;
+// one raw 16 B vector of the window, its first sample s0, sample by sample in the format's own layout
+template <int FMT>
+__device__ __forceinline__ uint4 fetch_vec_m(const RawSrcT<FMT> &rs, int64_t s0) {
+    uint4 w;
+    if constexpr (FMT == (int)kFmtSc16) {
         w.x = fetch_raw_m(rs, s0);
         w.y = fetch_raw_m(rs, s0 + 1);
         w.z = fetch_raw_m(rs, s0 + 2);
         w.w = fetch_raw_m(rs, s0 + 3);
-        stage[v] = w;
+    } else {
+        w.x = fetch_fmt_m(rs, s0) | (fetch_fmt_m(rs, s0 + 1) << 16);
+        w.y = fetch_fmt_m(rs, s0 + 2) | (fetch_fmt_m(rs, s0 + 3) << 16);
+        w.z = fetch_fmt_m(rs, s0 + 4) | (fetch_fmt_m(rs, s0 + 5) << 16);
+        w.w = fetch_fmt_m(rs, s0 + 6) | (fetch_fmt_m(rs, s0 + 7) << 16);
+    }
+    return w;
+}
+
+template <int KS, int FMT>
+__device__ __noinline__ void mfma_boundary_stage(RawSrcT<FMT> rs, uint64_t t0, uint32_t tid, uint4 *stage) {
+    using Gm = MfmaGeom<KS, FMT>;
+    for (uint32_t v = tid; v < Gm::nvec; v += 64u) {
+        const int64_t s0 = (int64_t)t0 - (int64_t)Gm::Tp + (int64_t)Gm::vsamples * (int64_t)v;
+        stage[v] = fetch_vec_m(rs, s0);
     }
 }
 
-template <int KS>
-__device__ __forceinline__ void mfma_boundary_loads(const MfmaTileCtx &c, uint64_t tile, uint32_t tid, unsigned char *win,
-                                                    uint4 (&q)[MfmaGeom<KS>::rounds]) {
-    using Gm = MfmaGeom<KS>;
+template <int KS, int FMT>
+__device__ __forceinline__ void mfma_boundary_loads(const MfmaTileCtxT<FMT> &c, uint64_t tile, uint32_t tid, unsigned char *win,
+                                                    uint4 (&q)[MfmaGeom<KS, FMT>::rounds]) {
+    using Gm = MfmaGeom<KS, FMT>;
     uint4 *stage = reinterpret_cast<uint4 *>(win);
-    mfma_boundary_stage<KS>(c.rs, tile * kMfmaTile, tid, stage);
+    mfma_boundary_stage<KS, FMT>(c.rs, tile * kMfmaTile, tid, stage);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -282,18 +384,26 @@ __device__ __forceinline__ void mfma_boundary_loads(const MfmaTileCtx &c, uint64
 }
 
 // raw window -> fp16 planes in LDS (masked: a wide tile's upper / lower bits)
-template <int KS>
-__device__ __forceinline__ void mfma_convert(const uint4 (&q)[MfmaGeom<KS>::rounds], uint32_t mask, uint32_t tid,
+// (8-bit formats: no mask, one piece; a vector's 8 halfs per plane never straddle a pad: one 16 B store each)
+template <int KS, int FMT>
+__device__ __forceinline__ void mfma_convert(const uint4 (&q)[MfmaGeom<KS, FMT>::rounds], uint32_t mask, uint32_t tid,
                                              _Float16 *pl_re, _Float16 *pl_im) {
-    using Gm = MfmaGeom<KS>;
+    using Gm = MfmaGeom<KS, FMT>;
 #pragma unroll
     for (int i = 0; i < Gm::rounds; ++i) {
         const uint32_t v = tid + 64u * i;
         if (64u * (i + 1) <= Gm::nvec || v < Gm::nvec) {
-            uint2 r4, i4;
-            cvt4(q[i], mask, r4, i4);
-            *reinterpret_cast<uint2 *>(pl_re + mslot(4u * v)) = r4;
-            *reinterpret_cast<uint2 *>(pl_im + mslot(4u * v)) = i4;
+            if constexpr (FMT == (int)kFmtSc16) {
+                uint2 r4, i4;
+                cvt4(q[i], mask, r4, i4);
+                *reinterpret_cast<uint2 *>(pl_re + mslot(4u * v)) = r4;
+                *reinterpret_cast<uint2 *>(pl_im + mslot(4u * v)) = i4;
+            } else {
+                uint4 r8, i8;
+                cvt8<FMT>(q[i], r8, i8);
+                *reinterpret_cast<uint4 *>(pl_re + mslot(8u * v)) = r8;
+                *reinterpret_cast<uint4 *>(pl_im + mslot(8u * v)) = i8;
+            }
         }
     }
     // the window is private to this wavefront and the LDS executes one wave's accesses in
@@ -358,19 +468,21 @@ __device__ __noinline__ void mfma_fetch_image(const void *image, unsigned char *
     }
 }
 
-template <int KS>
+template <int KS, int FMT>
 __global__ __launch_bounds__(64 * mfma_waves<KS>()) __attribute__((amdgpu_waves_per_eu(4)))
 void fir1_mfma_kernel(const FrontParams p) {
     constexpr int kMfmaWaves = mfma_waves<KS>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    using Gm = MfmaGeom<KS>;
+    using Gm = MfmaGeom<KS, FMT>;
+    typedef typename RawSrcT<FMT>::elem raw_t;
+    typedef typename RawSrcT<FMT>::ptr raw_ptr;
     constexpr uint32_t kImgBytes = (uint32_t)KS * 2u * 1024u;
     uint32_t tid = threadIdx.x & 63u;       // (made opaque once per tile: see the loop head)
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t cap = blockIdx.y;
-    MfmaTileCtx c;
-    c.rs.src = (gptr32)(reinterpret_cast<const uint32_t *>(p.iq) + (uint64_t)cap * p.cap_stride);
-    c.rs.halo = (gptr32)reinterpret_cast<const uint32_t *>(p.halo);
+    MfmaTileCtxT<FMT> c;
+    c.rs.src = (raw_ptr)(reinterpret_cast<const raw_t *>(p.iq) + (uint64_t)cap * p.cap_stride);
+    c.rs.halo = (raw_ptr)reinterpret_cast<const raw_t *>(p.halo);
     c.rs.halo_len = p.halo_len;
     c.rs.n_valid = p.n_valid;
     c.ctl = reinterpret_cast<uint32_t *>(smem_raw + kImgBytes);
@@ -400,8 +512,8 @@ void fir1_mfma_kernel(const FrontParams p) {
     uint64_t tile = 0;
     if (!mfma_take_ticket(c, tid, tile)) return;
     uint4 q[Gm::rounds];
-    if (mfma_interior<KS>(c, tile)) mfma_issue_loads<KS>(c, tile, tid, q);
-    else mfma_boundary_loads<KS>(c, tile, tid, win, q);
+    if (mfma_interior<KS, FMT>(c, tile)) mfma_issue_loads<KS, FMT>(c, tile, tid, q);
+    else mfma_boundary_loads<KS, FMT>(c, tile, tid, win, q);
     for (;;) {
         // Everything per lane below is a function of the lane id; left alone the compiler computes a dozen
         // offsets and addresses from it ONCE, keeps them alive across the whole loop and, out of registers,
@@ -411,25 +523,31 @@ void fir1_mfma_kernel(const FrontParams p) {
         const uint32_t n = tid & 31u, hh = tid >> 5;
         const uint64_t t0 = tile * kMfmaTile;
         // ---- quiet test (exact: kernels.hip) and range of the window ------------------------------
-        v2s mx = (v2s){0, 0}, mn = (v2s){0, 0};
+        bool loud, wide;
+        if constexpr (FMT == (int)kFmtSc16) {
+            v2s mx = (v2s){0, 0}, mn = (v2s){0, 0};
 #pragma unroll
-        for (int i = 0; i < Gm::rounds; ++i) {
-            mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].x), as_v2sm(q[i].y)));
-            mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].z), as_v2sm(q[i].w)));
-            mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].x), as_v2sm(q[i].y)));
-            mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].z), as_v2sm(q[i].w)));
+            for (int i = 0; i < Gm::rounds; ++i) {
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].x), as_v2sm(q[i].y)));
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].z), as_v2sm(q[i].w)));
+                mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].x), as_v2sm(q[i].y)));
+                mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].z), as_v2sm(q[i].w)));
+            }
+            const int L = p.quiet_lsb;
+            loud = !(mx.x < L && mx.y < L && mn.x > -L && mn.y > -L);
+            wide = __ballot(mx.x > 2047 || mx.y > 2047 || mn.x < -2048 || mn.y < -2048) != 0;
+        } else {
+            window_levels8<FMT>(q, p.quiet_lsb, loud);
+            wide = false;
         }
-        const int L = p.quiet_lsb;
-        const bool loud = !(mx.x < L && mx.y < L && mn.x > -L && mn.y > -L);
         const bool quiet = (!fout && __ballot(loud) == 0) || (p.mfma_debug & 1u);
-        const bool wide = __ballot(mx.x > 2047 || mx.y > 2047 || mn.x < -2048 || mn.y < -2048) != 0;
 
         uint64_t tile_n = 0;
         bool more = false, pre = false;
         if (quiet) {
             more = mfma_take_ticket(c, tid, tile_n);
-            pre = more && mfma_interior<KS>(c, tile_n);
-            if (pre) mfma_issue_loads<KS>(c, tile_n, tid, q);
+            pre = more && mfma_interior<KS, FMT>(c, tile_n);
+            if (pre) mfma_issue_loads<KS, FMT>(c, tile_n, tid, q);
             if (!p.sparse) {
                 if (tid < kMfmaTile / 64) *reinterpret_cast<gptr64>(uniform_ptr((gbytes_w)(words + (t0 >> 6))) + 8u * tid) = 0;
                 if (tid == 0) *uniform_ptr(tile_info + tile) = 0;
@@ -444,20 +562,21 @@ void fir1_mfma_kernel(const FrontParams p) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
             f16x are, aim;
-            if (!wide) {
-                mfma_convert<KS>(q, 0xffffffffu, tid, pl_re, pl_im);
+            if (FMT != (int)kFmtSc16 || !wide) {
+                mfma_convert<KS, FMT>(q, 0xffffffffu, tid, pl_re, pl_im);
                 more = mfma_take_ticket(c, tid, tile_n);
-                pre = more && mfma_interior<KS>(c, tile_n);
-                if (pre) mfma_issue_loads<KS>(c, tile_n, tid, q);
+                pre = more && mfma_interior<KS, FMT>(c, tile_n);
+                if (pre) mfma_issue_loads<KS, FMT>(c, tile_n, tid, q);
                 mfma_ksteps<KS, true>(a_img, pl_re, pl_im, tid, are, aim);
-            } else {
+            } else if constexpr (FMT == (int)kFmtSc16) {
                 // a sample beyond +-2048 somewhere in the window: upper bits, then the low five bits
-                mfma_convert<KS>(q, 0xffe0ffe0u, tid, pl_re, pl_im);
+                // (no 8-bit sample is: their instantiations do not hold this branch)
+                mfma_convert<KS, FMT>(q, 0xffe0ffe0u, tid, pl_re, pl_im);
                 mfma_ksteps<KS, true>(a_img, pl_re, pl_im, tid, are, aim);
-                mfma_convert<KS>(q, 0x001f001fu, tid, pl_re, pl_im);
+                mfma_convert<KS, FMT>(q, 0x001f001fu, tid, pl_re, pl_im);
                 more = mfma_take_ticket(c, tid, tile_n);
-                pre = more && mfma_interior<KS>(c, tile_n);
-                if (pre) mfma_issue_loads<KS>(c, tile_n, tid, q);
+                pre = more && mfma_interior<KS, FMT>(c, tile_n);
+                if (pre) mfma_issue_loads<KS, FMT>(c, tile_n, tid, q);
                 mfma_ksteps<KS, false>(a_img, pl_re, pl_im, tid, are, aim);
             }
 
@@ -558,7 +677,7 @@ void fir1_mfma_kernel(const FrontParams p) {
         }   // loud tile
 
         if (!more) break;
-        if (!pre) mfma_boundary_loads<KS>(c, tile_n, tid, win, q);       // (the LDS window is free: every read of it is done)
+        if (!pre) mfma_boundary_loads<KS, FMT>(c, tile_n, tid, win, q);       // (the LDS window is free: every read of it is done)
         tile = tile_n;
     }
 }
@@ -582,8 +701,13 @@ void fir1_mfma_kernel(const FrontParams p) {
 constexpr uint32_t kF2Out = 256;                // final outputs per wave tile
 constexpr uint32_t kF2Tp = 96;                  // input history in the window (>= 77)
 constexpr uint32_t kF2W = 4 * kF2Out + kF2Tp;   // 1120 window samples
-constexpr uint32_t kF2Nvec = kF2W / 4;          // 280 raw vectors
-constexpr int kF2Rounds = (int)((kF2Nvec + 63) / 64);
+// raw 16 B vectors of the window and the load rounds they take: 280 / 5 at 4 B per sample, 140 / 3 at 2 B
+template <int FMT>
+struct F2Geom {
+    static constexpr uint32_t vsamples = FMT == (int)kFmtSc16 ? 4u : 8u;
+    static constexpr uint32_t nvec = kF2W / vsamples;
+    static constexpr int rounds = (int)((nvec + 63) / 64);
+};
 constexpr int kF2KS = 5;
 constexpr int kF2Waves = 4;
 // one pad chunk (8 halfs) per 64 samples: column stride 72 halfs
@@ -601,7 +725,8 @@ struct F2Taps {                 // what the exact recompute needs
 };
 
 // Reference-order recomputation of final output m: the n2 stage-1 outputs it reads, each from the capture, then stage 2
-__device__ __forceinline__ float2 fir2_mfma_exact_output(const RawSrc &rs, const F2Taps &ft, int64_t m) {
+template <int FMT>
+__device__ __forceinline__ float2 fir2_mfma_exact_output(const RawSrcT<FMT> &rs, const F2Taps &ft, int64_t m) {
     const float s = 1.0f / 2048.0f;
     float re2 = 0.0f, im2 = 0.0f;
     for (uint32_t k2 = 0; k2 < ft.n2; ++k2) {
@@ -628,12 +753,17 @@ __device__ __forceinline__ float2 fir2_mfma_exact_output(const RawSrc &rs, const
     return make_float2(re2, im2);
 }
 
-__device__ __forceinline__ bool f2_interior(const MfmaTileCtx &c, uint64_t tile) {
+template <int FMT>
+__device__ __forceinline__ bool f2_interior(const MfmaTileCtxT<FMT> &c, uint64_t tile) {
     const uint64_t i0 = tile * (4ull * kF2Out);
     return c.aligned16 && i0 >= kF2Tp && i0 + 4ull * kF2Out <= c.rs.n_valid;
 }
 
-__device__ __forceinline__ void f2_issue_loads(const MfmaTileCtx &c, uint64_t tile, uint32_t tid, uint4 (&q)[kF2Rounds]) {
+template <int FMT>
+__device__ __forceinline__ void f2_issue_loads(const MfmaTileCtxT<FMT> &c, uint64_t tile, uint32_t tid,
+                                               uint4 (&q)[F2Geom<FMT>::rounds]) {
+    constexpr uint32_t kF2Nvec = F2Geom<FMT>::nvec;
+    constexpr int kF2Rounds = F2Geom<FMT>::rounds;
     const gbytes src4 = uniform_ptr((gbytes)(c.rs.src + (tile * (4ull * kF2Out) - kF2Tp)));
 #pragma unroll
     for (int i = 0; i < kF2Rounds; ++i) {
@@ -642,20 +772,19 @@ __device__ __forceinline__ void f2_issue_loads(const MfmaTileCtx &c, uint64_t ti
     }
 }
 
-__device__ __noinline__ void f2_boundary_stage(RawSrc rs, uint64_t i0, uint32_t tid, uint4 *stage) {
-    for (uint32_t v = tid; v < kF2Nvec; v += 64u) {
-        const int64_t s0 = (int64_t)i0 - (int64_t)kF2Tp + 4 * (int64_t)v;
-        uint4 w;
-        w.x = fetch_raw_m(rs, s0);
-        w.y = fetch_raw_m(rs, s0 + 1);
-        w.z = fetch_raw_m(rs, s0 + 2);
-        w.w = fetch_raw_m(rs, s0 + 3);
-        stage[v] = w;
+template <int FMT>
+__device__ __noinline__ void f2_boundary_stage(RawSrcT<FMT> rs, uint64_t i0, uint32_t tid, uint4 *stage) {
+    for (uint32_t v = tid; v < F2Geom<FMT>::nvec; v += 64u) {
+        const int64_t s0 = (int64_t)i0 - (int64_t)kF2Tp + (int64_t)F2Geom<FMT>::vsamples * (int64_t)v;
+        stage[v] = fetch_vec_m(rs, s0);
     }
 }
 
-__device__ __forceinline__ void f2_boundary_loads(const MfmaTileCtx &c, uint64_t tile, uint32_t tid, unsigned char *win,
-                                                  uint4 (&q)[kF2Rounds]) {
+template <int FMT>
+__device__ __forceinline__ void f2_boundary_loads(const MfmaTileCtxT<FMT> &c, uint64_t tile, uint32_t tid, unsigned char *win,
+                                                  uint4 (&q)[F2Geom<FMT>::rounds]) {
+    constexpr uint32_t kF2Nvec = F2Geom<FMT>::nvec;
+    constexpr int kF2Rounds = F2Geom<FMT>::rounds;
     uint4 *stage = reinterpret_cast<uint4 *>(win);
     f2_boundary_stage(c.rs, tile * (4ull * kF2Out), tid, stage);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -670,16 +799,26 @@ __device__ __forceinline__ void f2_boundary_loads(const MfmaTileCtx &c, uint64_t
     __builtin_amdgcn_wave_barrier();
 }
 
-__device__ __forceinline__ void f2_convert(const uint4 (&q)[kF2Rounds], uint32_t mask, uint32_t tid, _Float16 *pl_re,
+template <int FMT>
+__device__ __forceinline__ void f2_convert(const uint4 (&q)[F2Geom<FMT>::rounds], uint32_t mask, uint32_t tid, _Float16 *pl_re,
                                            _Float16 *pl_im) {
+    constexpr uint32_t kF2Nvec = F2Geom<FMT>::nvec;
+    constexpr int kF2Rounds = F2Geom<FMT>::rounds;
 #pragma unroll
     for (int i = 0; i < kF2Rounds; ++i) {
         const uint32_t v = tid + 64u * i;
         if (64u * (i + 1) <= kF2Nvec || v < kF2Nvec) {
-            uint2 r4, i4;
-            cvt4(q[i], mask, r4, i4);
-            *reinterpret_cast<uint2 *>(pl_re + f2slot(4u * v)) = r4;
-            *reinterpret_cast<uint2 *>(pl_im + f2slot(4u * v)) = i4;
+            if constexpr (FMT == (int)kFmtSc16) {
+                uint2 r4, i4;
+                cvt4(q[i], mask, r4, i4);
+                *reinterpret_cast<uint2 *>(pl_re + f2slot(4u * v)) = r4;
+                *reinterpret_cast<uint2 *>(pl_im + f2slot(4u * v)) = i4;
+            } else {
+                uint4 r8, i8;
+                cvt8<FMT>(q[i], r8, i8);
+                *reinterpret_cast<uint4 *>(pl_re + f2slot(8u * v)) = r8;
+                *reinterpret_cast<uint4 *>(pl_im + f2slot(8u * v)) = i8;
+            }
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -725,15 +864,19 @@ __device__ __noinline__ void f2_fetch_image(const void *image, unsigned char *sm
     }
 }
 
+template <int FMT>
 __global__ __launch_bounds__(64 * kF2Waves) __attribute__((amdgpu_waves_per_eu(4)))
 void fir2_mfma_kernel(const FrontParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    constexpr int kF2Rounds = F2Geom<FMT>::rounds;
+    typedef typename RawSrcT<FMT>::elem raw_t;
+    typedef typename RawSrcT<FMT>::ptr raw_ptr;
     uint32_t tid = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t cap = blockIdx.y;
-    MfmaTileCtx c;
-    c.rs.src = (gptr32)(reinterpret_cast<const uint32_t *>(p.iq) + (uint64_t)cap * p.cap_stride);
-    c.rs.halo = (gptr32)reinterpret_cast<const uint32_t *>(p.halo);
+    MfmaTileCtxT<FMT> c;
+    c.rs.src = (raw_ptr)(reinterpret_cast<const raw_t *>(p.iq) + (uint64_t)cap * p.cap_stride);
+    c.rs.halo = (raw_ptr)reinterpret_cast<const raw_t *>(p.halo);
     c.rs.halo_len = p.halo_len;
     c.rs.n_valid = p.n_valid;
     c.ctl = reinterpret_cast<uint32_t *>(smem_raw + kF2ImgBytes);
@@ -773,18 +916,24 @@ void fir2_mfma_kernel(const FrontParams p) {
         asm volatile("" : "+v"(tid));
         const uint32_t n = tid & 15u, g = tid >> 4;
         const uint64_t M0 = tile * kF2Out;
-        v2s mx = (v2s){0, 0}, mn = (v2s){0, 0};
+        bool loud, wide;
+        if constexpr (FMT == (int)kFmtSc16) {
+            v2s mx = (v2s){0, 0}, mn = (v2s){0, 0};
 #pragma unroll
-        for (int i = 0; i < kF2Rounds; ++i) {
-            mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].x), as_v2sm(q[i].y)));
-            mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].z), as_v2sm(q[i].w)));
-            mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].x), as_v2sm(q[i].y)));
-            mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].z), as_v2sm(q[i].w)));
+            for (int i = 0; i < kF2Rounds; ++i) {
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].x), as_v2sm(q[i].y)));
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2sm(q[i].z), as_v2sm(q[i].w)));
+                mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].x), as_v2sm(q[i].y)));
+                mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2sm(q[i].z), as_v2sm(q[i].w)));
+            }
+            const int L = p.quiet_lsb;
+            loud = !(mx.x < L && mx.y < L && mn.x > -L && mn.y > -L);
+            wide = __ballot(mx.x > 2047 || mx.y > 2047 || mn.x < -2048 || mn.y < -2048) != 0;
+        } else {
+            window_levels8<FMT>(q, p.quiet_lsb, loud);
+            wide = false;
         }
-        const int L = p.quiet_lsb;
-        const bool loud = !(mx.x < L && mx.y < L && mn.x > -L && mn.y > -L);
         const bool quiet = (!fout && __ballot(loud) == 0) || (p.mfma_debug & 1u);
-        const bool wide = __ballot(mx.x > 2047 || mx.y > 2047 || mn.x < -2048 || mn.y < -2048) != 0;
 
         uint64_t tile_n = 0;
         bool more = false, pre = false;
@@ -806,16 +955,16 @@ void fir2_mfma_kernel(const FrontParams p) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
             f4x are, aim;
-            if (!wide) {
-                f2_convert(q, 0xffffffffu, tid, pl_re, pl_im);
+            if (FMT != (int)kFmtSc16 || !wide) {
+                f2_convert<FMT>(q, 0xffffffffu, tid, pl_re, pl_im);
                 more = mfma_take_ticket(c, tid, tile_n);
                 pre = more && f2_interior(c, tile_n);
                 if (pre) f2_issue_loads(c, tile_n, tid, q);
                 f2_ksteps<true>(a_img, pl_re, pl_im, tid, are, aim);
-            } else {
-                f2_convert(q, 0xffe0ffe0u, tid, pl_re, pl_im);
+            } else if constexpr (FMT == (int)kFmtSc16) {
+                f2_convert<FMT>(q, 0xffe0ffe0u, tid, pl_re, pl_im);
                 f2_ksteps<true>(a_img, pl_re, pl_im, tid, are, aim);
-                f2_convert(q, 0x001f001fu, tid, pl_re, pl_im);
+                f2_convert<FMT>(q, 0x001f001fu, tid, pl_re, pl_im);
                 more = mfma_take_ticket(c, tid, tile_n);
                 pre = more && f2_interior(c, tile_n);
                 if (pre) f2_issue_loads(c, tile_n, tid, q);
@@ -1104,7 +1253,9 @@ hipError_t launch_front_mfma2(const FrontParams &p, uint32_t num_captures, hipSt
     if (pp.mfma_g == 0) pp.mfma_g = 1;
     pp.mfma_xcd_span = (p.mfma_xcd & 2u) && cnt % 8 == 0 && cnt / 8 <= 0xffffffffull ? (uint32_t)(cnt / 8) : 0u;
     const uint64_t grid = (cnt + (uint64_t)pp.mfma_g * kF2Waves - 1) / ((uint64_t)pp.mfma_g * kF2Waves);
-    const void *fn = reinterpret_cast<const void *>(&fir2_mfma_kernel);
+    const void *fn = p.sample_fmt == kFmtCs8   ? reinterpret_cast<const void *>(&fir2_mfma_kernel<(int)kFmtCs8>)
+                     : p.sample_fmt == kFmtCu8 ? reinterpret_cast<const void *>(&fir2_mfma_kernel<(int)kFmtCu8>)
+                                               : reinterpret_cast<const void *>(&fir2_mfma_kernel<(int)kFmtSc16>);
     hipError_t e = ensure_dynamic_lds(fn, kF2LdsBytes);
     if (e != hipSuccess) return e;
     void *args[] = {&pp};
@@ -1115,7 +1266,9 @@ hipError_t launch_front_mfma2(const FrontParams &p, uint32_t num_captures, hipSt
 template <int KS>
 static hipError_t launch_mfma_ks(FrontParams &pp, uint32_t num_captures, uint64_t grid, hipStream_t stream,
                                  hipEvent_t t0, hipEvent_t t1) {
-    const void *fn = reinterpret_cast<const void *>(&fir1_mfma_kernel<KS>);
+    const void *fn = pp.sample_fmt == kFmtCs8   ? reinterpret_cast<const void *>(&fir1_mfma_kernel<KS, (int)kFmtCs8>)
+                     : pp.sample_fmt == kFmtCu8 ? reinterpret_cast<const void *>(&fir1_mfma_kernel<KS, (int)kFmtCu8>)
+                                                : reinterpret_cast<const void *>(&fir1_mfma_kernel<KS, (int)kFmtSc16>);
     const size_t lds = mfma_lds_bytes<KS>();
     hipError_t e = ensure_dynamic_lds(fn, lds);
     if (e != hipSuccess) return e;

@@ -19,6 +19,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -777,29 +778,62 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(const FrontParams p, u
 // ---------------------------------------------------------------------------
 // One wavefront = 1024 samples (16 per lane, four 16 B loads issued up
 // front), same tile / tile-info convention as the 1-stage FIR kernel.
+// FMT (kFmt*): the 8-bit formats read their 16 samples as two 16 B loads and widen them in registers.
+template <int FMT>
+__device__ __forceinline__ uint32_t fetch_raw8(const FrontParams &p, const uint16_t *src, int64_t n) {
+    if (n < 0) {
+        const int64_t h = (int64_t)p.halo_len + n;
+        if (h < 0 || !p.halo) return 0u;
+        return widen8<FMT>(reinterpret_cast<const uint16_t *>(p.halo)[h]);
+    }
+    if ((uint64_t)n >= p.n_valid) return 0u;
+    return widen8<FMT>(src[n]);
+}
+
+template <int FMT>
 __global__ __launch_bounds__(64) void nofir_bits_kernel(const FrontParams p) {
     const uint32_t tid = threadIdx.x;
     const uint32_t cap = blockIdx.y;
     const uint64_t t0 = ((uint64_t)blockIdx.x + p.tile_base) * kWaveTile;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(p.iq) + (uint64_t)cap * p.cap_stride;
+    typedef typename std::conditional<FMT == (int)kFmtSc16, uint32_t, uint16_t>::type raw_t;
+    const raw_t *src = reinterpret_cast<const raw_t *>(p.iq) + (uint64_t)cap * p.cap_stride;
     uint64_t *words = p.bits + (uint64_t)cap * p.words_per_cap;
     float2 *fout = p.fir_out ? reinterpret_cast<float2 *>(p.fir_out) + (uint64_t)cap * p.n_out : nullptr;
     const bool aligned16 = ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
     const uint64_t o0 = t0 + 16ull * tid;          // lane owns samples o0 .. o0+15
     uint32_t raw[16];
-    if (aligned16 && t0 + kWaveTile <= p.n_valid) {
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src + o0);
+    if constexpr (FMT == (int)kFmtSc16) {
+        if (aligned16 && t0 + kWaveTile <= p.n_valid) {
+            const uint4 *s4 = reinterpret_cast<const uint4 *>(src + o0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint4 q = s4[i];
-            raw[4 * i] = q.x;
-            raw[4 * i + 1] = q.y;
-            raw[4 * i + 2] = q.z;
-            raw[4 * i + 3] = q.w;
+            for (int i = 0; i < 4; ++i) {
+                const uint4 q = s4[i];
+                raw[4 * i] = q.x;
+                raw[4 * i + 1] = q.y;
+                raw[4 * i + 2] = q.z;
+                raw[4 * i + 3] = q.w;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) raw[i] = fetch_raw(p, src, (int64_t)(o0 + i));
         }
     } else {
+        if (aligned16 && t0 + kWaveTile <= p.n_valid) {
+            const uint4 *s4 = reinterpret_cast<const uint4 *>(src + o0);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) raw[i] = fetch_raw(p, src, (int64_t)(o0 + i));
+            for (int i = 0; i < 2; ++i) {
+                const uint4 q = s4[i];
+                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    raw[8 * i + 2 * k] = widen8<FMT>(w[k] & 0xffffu);
+                    raw[8 * i + 2 * k + 1] = widen8<FMT>(w[k] >> 16);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) raw[i] = fetch_raw8<FMT>(p, src, (int64_t)(o0 + i));
+        }
     }
     uint32_t mask = 0;
 #pragma unroll
@@ -833,10 +867,36 @@ __global__ __launch_bounds__(64) void nofir_bits_kernel(const FrontParams p) {
 // ---------------------------------------------------------------------------
 // unpack only (SDR backend rx: complexf.h:68-77 on the GPU)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void unpack_kernel(const uint32_t *iq, float2 *out, uint64_t n) {
+// (8-bit formats: v / 128.0f = the unpacked widened sample, exactly)
+template <int FMT>
+__global__ __launch_bounds__(256) void unpack_kernel(const void *iq, float2 *out, uint64_t n) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        out[i] = unpack_iq(iq[i]);
+        if constexpr (FMT == (int)kFmtSc16) out[i] = unpack_iq(static_cast<const uint32_t *>(iq)[i]);
+        else out[i] = unpack_iq(widen8<FMT>(static_cast<const uint16_t *>(iq)[i]));
+    }
+}
+
+// ---------------------------------------------------------------------------
+// 8-bit capture -> SC16Q11 staging copy, for the forms that have no fused 8-bit kernel (packed-VALU, exact,
+// generic: test and fallback paths).  Four samples per lane and turn: one 8 B load, one 16 B store where both
+// are aligned, sample by sample otherwise.
+// ---------------------------------------------------------------------------
+template <int FMT>
+__global__ __launch_bounds__(256) void widen_kernel(const uint16_t *src, uint32_t *dst, uint64_t n, uint64_t src_stride,
+                                                    uint64_t dst_stride) {
+    const uint16_t *s = src + (uint64_t)blockIdx.y * src_stride;
+    uint32_t *d = dst + (uint64_t)blockIdx.y * dst_stride;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(s) & 7u) | (reinterpret_cast<uintptr_t>(d) & 15u)) == 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 4;
+    for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+        if (aligned && i + 4 <= n) {
+            const uint2 q = *reinterpret_cast<const uint2 *>(s + i);
+            *reinterpret_cast<uint4 *>(d + i) = make_uint4(widen8<FMT>(q.x & 0xffffu), widen8<FMT>(q.x >> 16),
+                                                           widen8<FMT>(q.y & 0xffffu), widen8<FMT>(q.y >> 16));
+        } else {
+            for (uint64_t k = i; k < n && k < i + 4; ++k) d[k] = widen8<FMT>(s[k]);
+        }
     }
 }
 
@@ -992,14 +1052,17 @@ static bool use_fir2(const FrontParams &p) {
            p.stage[0].ntaps <= Fir2Dec4::T1 && p.stage[1].ntaps <= Fir2Dec4::T2 && p.origin % 4 == 0;
 }
 
+// (8-bit formats: the three *_8 forms read the capture as it is; any other number means the 16-bit kernel of that
+//  number, on a widened copy)
 uint32_t front_form(const FrontParams &p, bool exact) {
-    if (p.num_stages == 0) return OOKD_FRONT_NO_FILTER;
+    const bool s8 = p.sample_fmt != kFmtSc16;
+    if (p.num_stages == 0) return s8 ? OOKD_FRONT_NO_FILTER_8 : OOKD_FRONT_NO_FILTER;
     if (use_fir1(p)) {
-        if (front_uses_mfma(p) && !exact) return OOKD_FRONT_FIR1_MFMA;
+        if (front_uses_mfma(p) && !exact) return s8 ? OOKD_FRONT_FIR1_MFMA_8 : OOKD_FRONT_FIR1_MFMA;
         return exact ? OOKD_FRONT_FIR1_VALU_EXACT : OOKD_FRONT_FIR1_VALU;
     }
     if (use_fir2(p)) {
-        if (front_uses_mfma2(p) && !exact) return OOKD_FRONT_FIR2_MFMA;
+        if (front_uses_mfma2(p) && !exact) return s8 ? OOKD_FRONT_FIR2_MFMA_8 : OOKD_FRONT_FIR2_MFMA;
         return exact ? OOKD_FRONT_FIR2_VALU_EXACT : OOKD_FRONT_FIR2_VALU;
     }
     return OOKD_FRONT_GENERIC;
@@ -1043,15 +1106,22 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
     void *args[] = {&pp};
     uint64_t grid = 0;
     const uint32_t form = front_form(p, exact);
-    if (form == OOKD_FRONT_NO_FILTER) {
+    if (p.sample_fmt != kFmtSc16 && form != OOKD_FRONT_NO_FILTER_8 && form != OOKD_FRONT_FIR1_MFMA_8 &&
+        form != OOKD_FRONT_FIR2_MFMA_8) {
+        return hipErrorInvalidValue;        // no 8-bit kernel of this form: the caller widens first
+    }
+    if (form == OOKD_FRONT_NO_FILTER || form == OOKD_FRONT_NO_FILTER_8) {
         // whole 4096-sample blocks, so every bit word of the capture is written
         range((p.n_out + kFirTile - 1) / kFirTile * kFirWaves, grid, pp);
         if (grid == 0) return hipSuccess;
-        const hipError_t e = hipExtLaunchKernel(reinterpret_cast<const void *>(&nofir_bits_kernel),
+        const void *fn = p.sample_fmt == kFmtCs8   ? reinterpret_cast<const void *>(&nofir_bits_kernel<(int)kFmtCs8>)
+                         : p.sample_fmt == kFmtCu8 ? reinterpret_cast<const void *>(&nofir_bits_kernel<(int)kFmtCu8>)
+                                                   : reinterpret_cast<const void *>(&nofir_bits_kernel<(int)kFmtSc16>);
+        const hipError_t e = hipExtLaunchKernel(fn,
                                                 dim3((uint32_t)grid, num_captures), dim3(64), args, 0, stream, t0, t1, 0);
         return e != hipSuccess ? e : hipGetLastError();
     }
-    if (form == OOKD_FRONT_FIR1_MFMA) {
+    if (form == OOKD_FRONT_FIR1_MFMA || form == OOKD_FRONT_FIR1_MFMA_8) {
         return launch_front_mfma(p, num_captures, stream, t0, t1, tile_begin, tile_count);
     }
     if (form == OOKD_FRONT_FIR1_VALU || form == OOKD_FRONT_FIR1_VALU_EXACT) {
@@ -1075,7 +1145,7 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
         e = hipExtLaunchKernel(fn, dim3((uint32_t)grid, num_captures), dim3(64 * kFirWgWaves), args, lds_req, stream, t0, t1, 0);
         return e != hipSuccess ? e : hipGetLastError();
     }
-    if (form == OOKD_FRONT_FIR2_MFMA) {
+    if (form == OOKD_FRONT_FIR2_MFMA || form == OOKD_FRONT_FIR2_MFMA_8) {
         return launch_front_mfma2(p, num_captures, stream, t0, t1, tile_begin, tile_count);
     }
     if (form == OOKD_FRONT_FIR2_VALU || form == OOKD_FRONT_FIR2_VALU_EXACT) {
@@ -1145,12 +1215,32 @@ hipError_t launch_clear_tiles(uint32_t *tile_info, uint64_t *bits, uint64_t ntil
     return hipGetLastError();
 }
 
-hipError_t launch_unpack(const int16_t *iq, float *out, uint64_t n, hipStream_t stream) {
+hipError_t launch_unpack(const void *iq, uint32_t fmt, float *out, uint64_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     uint64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(unpack_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream,
-                       reinterpret_cast<const uint32_t *>(iq), reinterpret_cast<float2 *>(out), n);
+    float2 *o = reinterpret_cast<float2 *>(out);
+    if (fmt == kFmtCs8) hipLaunchKernelGGL(unpack_kernel<(int)kFmtCs8>, dim3((uint32_t)blocks), dim3(256), 0, stream, iq, o, n);
+    else if (fmt == kFmtCu8) hipLaunchKernelGGL(unpack_kernel<(int)kFmtCu8>, dim3((uint32_t)blocks), dim3(256), 0, stream, iq, o, n);
+    else hipLaunchKernelGGL(unpack_kernel<(int)kFmtSc16>, dim3((uint32_t)blocks), dim3(256), 0, stream, iq, o, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_widen(const void *src, uint32_t fmt, int16_t *dst, uint64_t n, uint32_t num_captures,
+                        uint64_t src_stride, uint64_t dst_stride, hipStream_t stream) {
+    if (n == 0 || num_captures == 0) return hipSuccess;
+    if (fmt != kFmtCs8 && fmt != kFmtCu8) return hipErrorInvalidValue;
+    uint64_t blocks = (n / 4 + 256) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const uint16_t *s = static_cast<const uint16_t *>(src);
+    uint32_t *d = reinterpret_cast<uint32_t *>(dst);
+    if (fmt == kFmtCs8) {
+        hipLaunchKernelGGL(widen_kernel<(int)kFmtCs8>, dim3((uint32_t)blocks, num_captures), dim3(256), 0, stream, s, d, n,
+                           src_stride, dst_stride);
+    } else {
+        hipLaunchKernelGGL(widen_kernel<(int)kFmtCu8>, dim3((uint32_t)blocks, num_captures), dim3(256), 0, stream, s, d, n,
+                           src_stride, dst_stride);
+    }
     return hipGetLastError();
 }
 

@@ -78,7 +78,35 @@ struct FrontParams {
     uint32_t mfma_xcd_span;     // (set by the launchers: tiles per XCD of this launch, 0 = positions are tiles)
     uint64_t tile_end;          // first wave tile past this launch (set by launch_front_mfma)
     uint32_t mfma_debug;        // experiments (OOKD_MFMA_DEBUG): bit 0 = every tile takes the quiet exit (timing only)
+    uint32_t sample_fmt;        // kFmt*: what iq and halo hold.  The 8-bit formats are 2 bytes per sample (I, Q) and
+                                // only run on the forms front_form() numbers OOKD_FRONT_*_8; for every other form
+                                // the context widens the capture first and passes kFmtSc16 (rx.cpp: widen_for_form)
 };
+
+// Sample formats.  An 8-bit sample IS the SC16Q11 sample of 16 times its value: CS8 v (int8) = 16 v, CU8 u (uint8) =
+// 16 (u - 128), so that the unpacked float v / 128 = (16 v) / 2048 exactly, every sample is a nominal one
+// (|x| <= 2048) and an 8-bit run computes, bit for bit, what the 16-bit run on the widened capture computes.
+enum : uint32_t { kFmtSc16 = 0, kFmtCs8 = 1, kFmtCu8 = 2 };
+constexpr uint32_t sample_bytes(uint32_t fmt) { return fmt == kFmtSc16 ? 4u : 2u; }
+
+#ifdef __HIPCC__
+// one 2-byte sample (I | Q << 8) -> the SC16Q11 dword of the same value (I | Q << 16)
+template <int FMT>
+__device__ __forceinline__ uint32_t widen8(uint32_t s) {
+    int i = (int)(s & 0xffu), q = (int)((s >> 8) & 0xffu);
+    if (FMT == (int)kFmtCu8) {
+        i -= 128;
+        q -= 128;
+    } else {
+        i = (int)(int8_t)i;
+        q = (int)(int8_t)q;
+    }
+    return ((uint32_t)(i * 16) & 0xffffu) | ((uint32_t)(q * 16) << 16);
+}
+// value 0 of the format as a raw 2-byte sample (zero padding, bladeRF_file.c:113-117 pads the unpacked zero)
+template <int FMT>
+__device__ __forceinline__ uint32_t zero8() { return FMT == (int)kFmtCu8 ? 0x8080u : 0u; }
+#endif
 
 // A tile info word:  level changes inside the tile (10 bits: tiles hold at most 1024 outputs; the change between the
 // tile's first bit and the tile before is NOT in it) | which of the tile's 64-bit words holds the first of them
@@ -432,7 +460,12 @@ __device__ __forceinline__ uint32_t wg_inclusive_sum(uint32_t v, uint32_t *wtot,
 #endif
 
 // ---- unpack (backend rx) ----------------------------------------------------
-hipError_t launch_unpack(const int16_t *iq, float *out, uint64_t n, hipStream_t stream);
+// (fmt: kFmt*, n samples of sample_bytes(fmt) each)
+hipError_t launch_unpack(const void *iq, uint32_t fmt, float *out, uint64_t n, hipStream_t stream);
+// ---- 8-bit capture -> SC16Q11 (the forms without a fused 8-bit kernel) -----------------
+// capture c: n samples at src + 2 c src_stride bytes -> dst + 4 c dst_stride bytes
+hipError_t launch_widen(const void *src, uint32_t fmt, int16_t *dst, uint64_t n, uint32_t num_captures,
+                        uint64_t src_stride, uint64_t dst_stride, hipStream_t stream);
 // ---- pack (post-filter recorder) ----------------------------------------------
 hipError_t launch_pack(const float *in, int16_t *iq, uint64_t n, hipStream_t stream);
 

@@ -475,6 +475,10 @@ struct ookd_rx : RxHandles {
     uint32_t scan_fin_cap = 0;
     uint32_t scan_stamp = 0;        // stamps the finish kernel's block aggregates, never 0
     DevBuf<int16_t> d_stage_in;     // process_host staging (lazy)
+    uint32_t sample_fmt = kFmtSc16; // what captures and halos hold (OOKD_RX_SAMPLES_*)
+    // 8-bit contexts, forms without a fused 8-bit kernel: the capture and the halo widened to SC16Q11
+    // (allocated by the first run that takes such a form: widen_for_form)
+    DevBuf<int16_t> d_widen, d_halo_w;
 
     ResultHeader *h_hdr_dev = nullptr;      // the same two through the device's mapping
     MsgDev *h_msgs_dev = nullptr;
@@ -545,6 +549,7 @@ struct ookd_rx : RxHandles {
         p.tiles_per_cap = tile_bits ? (uint32_t)(run_words * 64 / tile_bits) : 0;
         p.sparse = sparse ? 1u : 0u;
         p.stamp_bits = tile_stamp << kTileStampShift;
+        p.sample_fmt = sample_fmt;
         return p;
     }
 
@@ -634,6 +639,7 @@ struct ookd_rx : RxHandles {
     bool plan_chunks();
     int run_pipelined(const void *d_iq);
     int prepare_front(FrontParams &fp);
+    int widen_for_form(FrontParams &fp, uint32_t form);
     int run_state_machine(const FsmStateDev *first, bool fresh);
     FsmScanArgs scan_args() const;
     int fsm_scan(const FsmStateDev *first);
@@ -653,6 +659,33 @@ struct ookd_rx : RxHandles {
 // alone -- whatever they hold carries an older stamp and reads as quiet -- so nothing is zeroed between
 // runs, except when the geometry changes (rare; keeps "a zero info means zero words" simple to reason
 // about) or the 16-bit stamp wraps (every 2^16 - 1 runs): then every tile the buffer may hold is zeroed.
+// An 8-bit context about to run a form that only exists for SC16Q11 (anything but the OOKD_FRONT_*_8 numbers):
+// the run's captures and halo go through the widening kernel into staging buffers, and the front end is
+// pointed at those.  Test and fallback paths: the fused forms never come here and never pay for the buffer.
+int ookd_rx::widen_for_form(FrontParams &fp, uint32_t form) {
+    if (fp.sample_fmt == kFmtSc16 || form == OOKD_FRONT_NO_FILTER_8 || form == OOKD_FRONT_FIR1_MFMA_8 ||
+        form == OOKD_FRONT_FIR2_MFMA_8) {
+        return OOKD_OK;
+    }
+    if (!d_widen.p) {
+        const int rc = d_widen.alloc(2 * (size_t)max_samples * max_captures + 8);
+        if (rc != OOKD_OK) return rc;
+    }
+    HIPCHK(launch_widen(fp.iq, fp.sample_fmt, d_widen.p, run_n_valid, run_caps, fp.cap_stride, run_n_valid, stream));
+    fp.iq = d_widen.p;
+    fp.cap_stride = run_n_valid;
+    if (fp.halo && fp.halo_len) {
+        if (!d_halo_w.p) {
+            const int rc = d_halo_w.alloc(2 * (halo_needed + 4));
+            if (rc != OOKD_OK) return rc;
+        }
+        HIPCHK(launch_widen(fp.halo, fp.sample_fmt, d_halo_w.p, fp.halo_len, 1, 0, 0, stream));
+        fp.halo = d_halo_w.p;
+    }
+    fp.sample_fmt = kFmtSc16;
+    return OOKD_OK;
+}
+
 int ookd_rx::prepare_front(FrontParams &fp) {
     if (!tile_bits) return OOKD_OK;
     if (sparse) {
@@ -762,7 +795,8 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     FrontParams fp = front_params(d_iq, run_n_valid);
     run_form = front_form(fp, exact);
     {
-        const int rc = prepare_front(fp);
+        int rc = widen_for_form(fp, run_form);
+        if (rc == OOKD_OK) rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
     }
     HIPCHK(hipEventRecord(ev_start, stream));
@@ -846,7 +880,8 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
     fp.halo_len = halo_len;
     run_form = front_form(fp, exact);
     {
-        const int rc = prepare_front(fp);
+        int rc = widen_for_form(fp, run_form);
+        if (rc == OOKD_OK) rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
     }
     // The tuned kernels go out as several grid launches of front_launch_tiles wave tiles: while a
@@ -1843,6 +1878,11 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
         }
     }
     rx->exact = (cfg->flags & OOKD_RX_EXACT_FIR) != 0;
+    if ((cfg->flags & OOKD_RX_SAMPLES_CS8) && (cfg->flags & OOKD_RX_SAMPLES_CU8)) {
+        set_error("ookd_rx_create: OOKD_RX_SAMPLES_CS8 and OOKD_RX_SAMPLES_CU8 are both set: a context has one sample format");
+        return nullptr;
+    }
+    rx->sample_fmt = (cfg->flags & OOKD_RX_SAMPLES_CS8) ? kFmtCs8 : (cfg->flags & OOKD_RX_SAMPLES_CU8) ? kFmtCu8 : kFmtSc16;
     rx->max_captures = cfg->max_captures ? cfg->max_captures : 1;
     rx->max_samples = cfg->max_samples;
 
@@ -1863,6 +1903,8 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
 }
 
 void ookd_rx_destroy(ookd_rx *rx) { delete rx; }
+
+uint32_t ookd_rx_sample_bytes(const ookd_rx *rx) { return rx ? sample_bytes(rx->sample_fmt) : 0u; }
 
 ookd_rx_gate *ookd_rx_gate_create(void) { return new (std::nothrow) ookd_rx_gate(); }
 
@@ -1956,10 +1998,10 @@ int ookd_rx_process_host(ookd_rx *rx, const int16_t *iq, uint64_t num_samples) {
     }
     HIPCHK(hipSetDevice(rx->dev));
     if (!rx->d_stage_in.p) {
-        int rc = rx->d_stage_in.alloc(2 * rx->max_samples + 8);
+        int rc = rx->d_stage_in.alloc(rx->max_samples * (sample_bytes(rx->sample_fmt) / 2) + 8);
         if (rc != OOKD_OK) return rc;
     }
-    if (num_samples && rx->ingest.from_host(iq, rx->d_stage_in.p, num_samples * 4) < 0) return OOKD_ERR_HIP;
+    if (num_samples && rx->ingest.from_host(iq, rx->d_stage_in.p, num_samples * sample_bytes(rx->sample_fmt)) < 0) return OOKD_ERR_HIP;
     return ookd_rx_process_device(rx, rx->d_stage_in.p, 1, num_samples, num_samples);
 }
 
@@ -2108,7 +2150,8 @@ int ookd_rx_shard_begin(ookd_rx *rx, const void *d_iq, uint64_t num_samples, con
         hl = (uint32_t)rx->halo_needed;
         // hipMemcpyDefault: the halo may be a host array or a device buffer an
         // RCCL recv landed in
-        HIPCHK(hipMemcpyAsync(rx->d_halo.p, halo + 2 * (halo_samples - hl), (size_t)hl * 4,
+        const size_t sb = sample_bytes(rx->sample_fmt);
+        HIPCHK(hipMemcpyAsync(rx->d_halo.p, reinterpret_cast<const char *>(halo) + sb * (halo_samples - hl), (size_t)hl * sb,
                               hipMemcpyDefault, rx->stream));
     }
     rx->run_caps = 1;
