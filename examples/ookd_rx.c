@@ -10,7 +10,13 @@
  *   gcc -std=c99 -Wall -Iinclude examples/ookd_rx.c -o ookd_rx \
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
- * ookd_rx <capture.sc16q11> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]
+ * ookd_rx [--threshold <value>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate>
+ *         [csv|pretty] [dig.csv]
+ *
+ * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
+ * it is; `auto` surveys the capture's envelope levels first (ookd_survey_*, ookd_suggest_threshold), reports
+ * the two levels and the threshold between them on stderr and decodes with that -- or, when the capture does
+ * not show two levels, says so and exits non-zero without decoding.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,9 +32,26 @@ static int fail(const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc < 5) {
-        fprintf(stderr, "usage: %s <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> "
-                        "[csv|pretty] [dig.csv]\n", argv[0]);
+    /* --threshold <value>|auto is taken out of argv; what is left is positional, as before */
+    float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
+    int threshold_auto = 0, bad_option = 0;
+    int kept = 1;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "--threshold")) {
+            char *end = NULL;
+            if (++i >= argc) { bad_option = 1; break; }
+            if (!strcmp(argv[i], "auto")) { threshold_auto = 1; continue; }
+            threshold_auto = 0;
+            threshold = strtof(argv[i], &end);
+            if (end == argv[i] || *end != '\0') { bad_option = 1; break; }
+        } else {
+            argv[kept++] = argv[i];
+        }
+    }
+    argc = kept;
+    if (argc < 5 || bad_option) {
+        fprintf(stderr, "usage: %s [--threshold <value>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> "
+                        "<filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const int fmt = (argc > 5 && !strcmp(argv[5], "csv")) ? OOKD_RX_FMT_CSV : OOKD_RX_FMT_PRETTY;
@@ -41,13 +64,14 @@ int main(int argc, char **argv)
     cfg.direction = 0;
     cfg.sdr_args = argv[1];
     cfg.samplerate = rate;
-    cfg.rx_threshold = 0.1f;                /* ookiedokie_cfg.h defaults */
+    cfg.rx_threshold = threshold;
     cfg.samples_per_buffer = 8192;
 
     ookd_filter *filter = NULL;
     ookd_device *device = NULL;
     ookd_formatter *formatter = NULL;
     ookd_rx *rx = NULL;
+    ookd_survey *survey = NULL;
     char *text = NULL;
 
     void *sdr = sdr_hip_file_init((const struct ookiedokie_cfg *)&cfg);   /* same layout: see ookd_host_cfg */
@@ -66,6 +90,26 @@ int main(int argc, char **argv)
     if (!device) { fail("ookd_device_load"); goto out; }
     formatter = ookd_formatter_create(device);
     if (!formatter) { fail("ookd_formatter_create"); goto out; }
+
+    if (threshold_auto) {                   /* the capture is in HBM already: one pass over it */
+        ookd_level_hist hist;
+        ookd_threshold_suggestion sug;
+        survey = ookd_survey_create(0, filter, (uint32_t) sdr_hip_file_sample_flags(sdr), 1, NULL);
+        if (!survey) { fail("ookd_survey_create"); goto out; }
+        if (ookd_survey_device(survey, d_iq, 1, n, n) != 0) { fail("ookd_survey_device"); goto out; }
+        if (ookd_survey_get_hist(survey, 0, &hist) != 0) { fail("ookd_survey_get_hist"); goto out; }
+        if (ookd_suggest_threshold(&hist, &sug) != 0) { fail("ookd_suggest_threshold"); goto out; }
+        if (!sug.found) {
+            fprintf(stderr, "threshold auto: no two envelope levels in %llu samples (bins %u and %u, %.1f %% above "
+                            "the split): nothing decoded\n", (unsigned long long) hist.samples, sug.off_bin,
+                    sug.on_bin, 100.0 * sug.on_fraction);
+            goto out;
+        }
+        fprintf(stderr, "threshold auto: %.6g (off level %.6g, on level %.6g, %.1f %% on, survey %.3f ms)\n",
+                sug.threshold, sug.off_level, sug.on_level, 100.0 * sug.on_fraction,
+                ookd_survey_kernel_ms(survey));
+        cfg.rx_threshold = sug.threshold;
+    }
 
     ookd_rx_config rc;
     memset(&rc, 0, sizeof(rc));
@@ -103,6 +147,7 @@ int main(int argc, char **argv)
 out:
     free(text);
     ookd_rx_destroy(rx);
+    ookd_survey_destroy(survey);
     ookd_formatter_free(formatter);
     ookd_device_free(device);
     ookd_filter_free(filter);

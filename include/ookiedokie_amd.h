@@ -437,6 +437,115 @@ int ookd_rx_get_fir_sc16q11(const ookd_rx *rx, uint32_t capture, int16_t *out,
 int ookd_rx_record_fir(const ookd_rx *rx, uint32_t capture, const char *path);
 
 /* ------------------------------------------------------------------------
+ * Envelope survey: which threshold does this capture want?  One pass over
+ * captures resident in HBM counts the post-filter power -- the quantity the
+ * slicer compares, complexf_power (src/complexf.h:43-46) of the output of
+ * fir_filter_and_decimate (src/fir.c:355-395) -- into a histogram per
+ * capture; ookd_suggest_threshold (host only) turns a histogram into a value
+ * for ookd_rx_config.threshold.  A separate object beside the rx context:
+ * nothing an ookd_rx does changes.
+ *
+ * Arithmetic: unpack and filter are the reference's, bit for bit (taps newest
+ * first, separate multiply and add, stages chained as fir.c chains them: what
+ * OOKD_RX_EXACT_FIR computes), so a histogram is an exact integer function of
+ * the capture.
+ * Bins: four per octave of power (0.75 dB of amplitude on average), cut from
+ * the float's own bits -- exponent and the two leading mantissa bits --,
+ *     b = clamp((bits(p) >> 21) - ((127 - 40) << 2) + 1, 0, 255):
+ * bin 0 holds everything below 2^-40 (zeros and denormals included), bin
+ * b >= 1 starts at power 2^(-40 + (b - 1) div 4) * (1 + ((b - 1) mod 4) / 4),
+ * i.e. at 1, 1.25, 1.5 and 1.75 times each power of two, bin 255 holds
+ * everything from 1.5 * 2^23 up (inf, NaN and anything with the sign bit set
+ * included; a power is never negative).
+ * Counted: per capture the first floor(n / D) filter outputs from zero
+ * history, n = samples in the capture, D = total decimation; with no filter
+ * the samples themselves.  No zero padding is counted (an rx context pads a
+ * capture to whole buffers; that is buffering, not signal).
+ * ---------------------------------------------------------------------- */
+#define OOKD_LEVEL_BINS 256
+typedef struct ookd_level_hist {
+    uint64_t samples;               /* floor(n / D) = the sum of bins[]       */
+    uint64_t bins[OOKD_LEVEL_BINS];
+} ookd_level_hist;
+
+typedef struct ookd_survey ookd_survey;
+
+/* filter may be NULL (no filter).  sample_flags: 0 (SC16Q11), OOKD_RX_SAMPLES_CS8
+ * or OOKD_RX_SAMPLES_CU8 (read in place, 2 bytes per sample); both, or any
+ * other bit, fails.  stream: hipStream_t to launch on, NULL = own. */
+ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter,
+                                uint32_t sample_flags, uint32_t max_captures,
+                                void *stream);
+void ookd_survey_destroy(ookd_survey *s);
+/* Survey `num_captures` (<= max_captures) captures of `samples_per_capture`
+ * samples each, resident in HBM, capture c at sample c * capture_stride_samples
+ * of d_iq (samples of the survey's format, as ookd_rx_process_device takes
+ * them).  Blocks until the histograms are in host memory; they replace those
+ * of the run before.  0 samples is a valid (empty) survey. */
+int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures,
+                       uint64_t samples_per_capture, uint64_t capture_stride_samples);
+/* Same over one host capture: staged to HBM first (PCIe-bound). */
+int ookd_survey_host(ookd_survey *s, const void *iq, uint64_t num_samples);
+int ookd_survey_get_hist(const ookd_survey *s, uint32_t capture, ookd_level_hist *out);
+/* HIP-event time of the last run's histogram kernel (0 before any run). */
+float ookd_survey_kernel_ms(const ookd_survey *s);
+
+/* The bin rule above and its inverse, pure host code (no GPU needed).
+ * ookd_level_bin_lower: the power at which bin `bin` starts (0 for bin 0;
+ * bins beyond 255 continue the series: 256 gives the upper edge of the
+ * geometric cell that stands for bin 255). */
+uint32_t ookd_level_bin(float power);
+float ookd_level_bin_lower(uint32_t bin);
+
+/* Suggested threshold.  The rule, a contract:
+ *   1. Split.  Over the BIN INDEX (the log domain) find the k in 0..254 with both
+ *      sides non-empty -- "off" = bins 0..k, "on" = bins k+1..255 -- that
+ *      maximises Otsu's between-class variance
+ *          (n * sum_{i<=k} i h[i]  -  a * sum_i i h[i])^2 / (a * (n - a)),
+ *      a = sum_{i<=k} h[i], n = sum_i h[i], compared in exact integer
+ *      arithmetic.  Several k with the same maximum: the split is
+ *      (first + last) / 2 of them, rounded down.
+ *   2. Levels.  off_bin / on_bin are the median bins of the two sides: the
+ *      first bin at which the side's running count reaches (count + 1) / 2.
+ *      The amplitude of bin b is the fourth root of the product of its two
+ *      power edges, (lower(b) * lower(b + 1))^(1/4); off_level is 0 when
+ *      off_bin is 0.
+ *   3. threshold = (off_level + on_level) / 2, the amplitude midpoint: the
+ *      slicer level that moves the two flanks of a pulse by the same amount
+ *      on a symmetric filter ramp, so pulse widths are distorted least.  (The
+ *      split of step 1 itself is NOT a usable threshold: in the log domain it
+ *      sits some 15 dB under the on level, inside the noise's skirt.)
+ *   4. found = 1 only if on_bin - off_bin >= OOKD_LEVEL_MIN_SEPARATION and
+ *      both sides hold at least OOKD_LEVEL_MIN_SIDE samples; otherwise 0
+ *      (noise only, empty, silence, or always on) and threshold is 0 -- the
+ *      other members still say what was seen.  No split at all (fewer than
+ *      two occupied bins): everything 0 but the bin of the one level in
+ *      off_bin = on_bin.
+ * OOKD_LEVEL_MIN_SEPARATION, 18 bins = 13.5 dB: measured on the golden
+ * captures through fs32_fs4 with +-40 LSB of uniform noise, noise alone
+ * splits into halves whose medians lie 11..12 bins apart whatever its level
+ * (+-5 .. +-1000 LSB: 10..11), while the quietest capture that still decodes
+ * (1/16 of nominal level) shows 26; 18 leaves 6 bins to the one and 8 to the
+ * other.
+ * OOKD_LEVEL_MIN_SIDE, 512 samples: a level held for less is a transient --
+ * the start-up ramp of a carrier that is always on (11 outputs through
+ * fs32_fs4, at most the tap count) --, while one message holds thousands.
+ * Limits: two levels only (the strongest of several transmitters sets the on
+ * level); a capture of tiny integer noise without a filter has a share of
+ * samples exactly zero (bin 0) far from the rest and reads as two levels. */
+#define OOKD_LEVEL_MIN_SEPARATION 18
+#define OOKD_LEVEL_MIN_SIDE 512
+typedef struct ookd_threshold_suggestion {
+    int found;                      /* 0: no two levels                        */
+    float threshold;                /* amplitude: ookd_rx_config.threshold     */
+    float off_level, on_level;      /* amplitudes of the two levels            */
+    uint32_t split_bin, off_bin, on_bin;    /* split_bin: the k of step 1      */
+    double on_fraction;             /* share of samples above the split        */
+} ookd_threshold_suggestion;
+/* 0, or OOKD_ERR_ARG for a NULL argument.  n is the sum of h->bins; h->samples is not read. */
+int ookd_suggest_threshold(const ookd_level_hist *h, ookd_threshold_suggestion *out);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

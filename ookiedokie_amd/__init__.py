@@ -14,6 +14,8 @@ here                              reference (OOKiedokie ``src/``)
 ``StreamFir.filter_and_decimate`` ``fir_filter_and_decimate`` (fir.h:68-81)
 ``HipFileBackend``                ``sdr_<name>_{init,deinit,rx,tx,flush}``
                                   (sdr/supported_devices.h:32-48)
+``Survey`` / ``suggest_threshold`` nothing: picks ``--rx-threshold``
+                                  (ookiedokie_cfg.c:27) from the capture
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -61,6 +63,9 @@ FRONT_FIR2_MFMA = 8
 FRONT_NO_FILTER_8 = 9                   # the fused forms of an 8-bit context
 FRONT_FIR1_MFMA_8 = 10
 FRONT_FIR2_MFMA_8 = 11
+LEVEL_BINS = 256                        # OOKD_LEVEL_BINS: envelope survey, four bins per octave of power
+LEVEL_MIN_SEPARATION = 18               # OOKD_LEVEL_MIN_SEPARATION
+LEVEL_MIN_SIDE = 512                    # OOKD_LEVEL_MIN_SIDE
 DEFAULT_THRESHOLD = 0.1                 # ookiedokie_cfg.c:27
 DEFAULT_RATE = 3000000                  # ookiedokie_cfg.c:32
 DEFAULT_SAMPLES_PER_BUF = 8192          # ookiedokie_cfg.c:34
@@ -147,6 +152,16 @@ class SynthConfig(C.Structure):
         ("noise", C.c_uint32), ("gap_min_us", C.c_uint32), ("gap_max_us", C.c_uint32),
         ("glitch_every", C.c_uint32), ("random_phase", C.c_uint32),
     ]
+
+
+class LevelHist(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("bins", C.c_uint64 * LEVEL_BINS)]
+
+
+class ThresholdSuggestion(C.Structure):
+    _fields_ = [("found", C.c_int), ("threshold", C.c_float), ("off_level", C.c_float), ("on_level", C.c_float),
+                ("split_bin", C.c_uint32), ("off_bin", C.c_uint32), ("on_bin", C.c_uint32),
+                ("on_fraction", C.c_double)]
 
 
 class HostCfg(C.Structure):
@@ -239,6 +254,15 @@ _PROTOTYPES = {
                                          C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]),
     "ookd_rx_gate_create": (C.c_void_p, []),
     "ookd_rx_gate_destroy": (None, [C.c_void_p]),
+    "ookd_survey_create": (C.c_void_p, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "ookd_survey_destroy": (None, [C.c_void_p]),
+    "ookd_survey_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "ookd_survey_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "ookd_survey_get_hist": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(LevelHist)]),
+    "ookd_survey_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_level_bin": (C.c_uint32, [C.c_float]),
+    "ookd_level_bin_lower": (C.c_float, [C.c_uint32]),
+    "ookd_suggest_threshold": (C.c_int, [C.POINTER(LevelHist), C.POINTER(ThresholdSuggestion)]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
     "sdr_hip_file_deinit": (None, [C.c_void_p]),
     "sdr_hip_file_rx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
@@ -765,6 +789,88 @@ class Receiver:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_rx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# --------------------------------------------------------------------------
+# envelope survey
+# --------------------------------------------------------------------------
+
+def level_bin(power: float) -> int:
+    """The histogram bin of a post-filter power (ookd_level_bin): four bins per octave, bin 0 below 2^-40."""
+    return int(lib().ookd_level_bin(C.c_float(power)))
+
+
+def level_bin_lower(bin: int) -> float:
+    """The power at which a bin starts (ookd_level_bin_lower)."""
+    return float(lib().ookd_level_bin_lower(bin))
+
+
+def suggest_threshold(hist) -> dict:
+    """ookd_suggest_threshold over 256 counts: found, threshold, off_level, on_level, split_bin, off_bin, on_bin,
+    on_fraction (the rule is stated in the header).  Pure host code."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    if h.size != LEVEL_BINS:
+        raise ValueError("a level histogram has %d bins, not %d" % (LEVEL_BINS, h.size))
+    lh = LevelHist()
+    lh.samples = int(h.sum(dtype=np.uint64))
+    C.memmove(lh.bins, h.ctypes.data, h.nbytes)
+    out = ThresholdSuggestion()
+    _check(lib().ookd_suggest_threshold(C.byref(lh), C.byref(out)))
+    return {name: getattr(out, name) for name, _ in ThresholdSuggestion._fields_}
+
+
+class Survey:
+    """Histogram of the post-filter power of whole captures in HBM (ookd_survey_*): what `Receiver`'s slicer
+    will compare against `threshold`, counted before a threshold is chosen."""
+
+    def __init__(self, filt: Optional[Filter], *, hip_device: int = 0, max_captures: int = 1, stream: int = 0,
+                 sample_format: str = "sc16q11"):
+        if sample_format not in SAMPLE_FORMATS:
+            raise ValueError("sample_format must be one of %s" % ", ".join(sorted(SAMPLE_FORMATS)))
+        self.sample_format = sample_format
+        fmt_flag, self._sample_dtype = SAMPLE_FORMATS[sample_format]
+        self._filter = filt
+        self.total_decimation = filt.total_decimation if filt else 1
+        self._h = lib().ookd_survey_create(hip_device, filt._h if filt else None, fmt_flag, max_captures, stream)
+        if not self._h:
+            raise OokdError(-4, last_error())
+
+    def survey_device(self, d_iq_ptr: int, samples_per_capture: int, num_captures: int = 1,
+                      stride: Optional[int] = None) -> None:
+        """Captures already resident in HBM (I,Q interleaved, in the survey's sample format)."""
+        _check(lib().ookd_survey_device(self._h, d_iq_ptr, num_captures, samples_per_capture,
+                                        stride if stride is not None else samples_per_capture))
+
+    def survey(self, iq: np.ndarray) -> np.ndarray:
+        """One host capture (staged over PCIe first), same arrays as `Receiver.rx` takes; returns its histogram."""
+        if self.sample_format != "sc16q11" and np.asarray(iq).dtype != self._sample_dtype:
+            raise TypeError("this Survey takes %s samples as %s, not %s"
+                            % (self.sample_format, np.dtype(self._sample_dtype).name, np.asarray(iq).dtype.name))
+        iq = np.ascontiguousarray(iq, dtype=self._sample_dtype).reshape(-1)
+        _check(lib().ookd_survey_host(self._h, iq.ctypes.data, iq.size // 2))
+        return self.hist(0)
+
+    def hist(self, capture: int = 0) -> np.ndarray:
+        """The 256 counts of one capture of the last run (uint64); they sum to `samples`."""
+        lh = LevelHist()
+        _check(lib().ookd_survey_get_hist(self._h, capture, C.byref(lh)))
+        self.samples = int(lh.samples)
+        return np.frombuffer(bytes(lh.bins), dtype=np.uint64).copy()
+
+    @property
+    def kernel_ms(self) -> float:
+        return float(lib().ookd_survey_kernel_ms(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().ookd_survey_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -469,6 +469,40 @@ hipError_t launch_widen(const void *src, uint32_t fmt, int16_t *dst, uint64_t n,
 // ---- pack (post-filter recorder) ----------------------------------------------
 hipError_t launch_pack(const float *in, int16_t *iq, uint64_t n, hipStream_t stream);
 
+// ---- envelope survey (survey.hip) ---------------------------------------------
+// Histogram of the post-filter power of every capture, reference-order arithmetic (what fir_generic_kernel
+// computes), no halo, no padding: outputs 0 .. n_out - 1 of the filter started from zero history.
+constexpr int kLevelBins = 256;         // OOKD_LEVEL_BINS
+constexpr uint32_t kLevelBinBase = ((127u - 40u) << 2) - 1u;    // bits(p) >> 21 of the first power of bin 1, less one
+
+__host__ __device__ __forceinline__ uint32_t level_bin_of_bits(uint32_t power_bits) {
+    const uint32_t e = power_bits >> 21;
+    if (e <= kLevelBinBase) return 0u;
+    const uint32_t b = e - kLevelBinBase;
+    return b > (uint32_t)(kLevelBins - 1) ? (uint32_t)(kLevelBins - 1) : b;
+}
+
+struct SurveyParams {
+    const void *iq;             // captures in `sample_fmt`
+    uint32_t sample_fmt;        // kFmt*
+    uint64_t cap_stride;        // samples between consecutive captures
+    uint64_t n_out;             // outputs counted per capture: floor(n / D)
+    uint32_t num_stages;        // 0 = no filter
+    FirStageDev stage[kMaxStages];
+    const float *taps;          // all stages, unpadded
+    uint32_t tile;              // final outputs per tile (survey_tile())
+    uint64_t num_tiles;         // ceil(n_out / tile)
+    uint32_t lds_b_off;         // float2 offset of the second level buffer
+    uint32_t lds_hist_off;      // byte offset of the per-wave histograms
+    uint32_t lds_taps_off;      // byte offset of the workgroup's copy of the taps
+    uint32_t num_taps;          // taps of all stages together
+    unsigned long long *hist;   // [captures][kLevelBins], zero at launch
+};
+// Largest power-of-two tile (<= 1024 outputs) whose level buffers fit the LDS budget, 0 = none does; fills the
+// LDS offsets of `p` and returns the dynamic LDS size through *lds_bytes.
+uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes);
+hipError_t launch_survey(const SurveyParams &p, uint32_t num_captures, size_t lds_bytes, hipStream_t stream);
+
 // ---- synthetic generator ------------------------------------------------------
 
 struct SynthRun {               // one constant-envelope run of the capture
