@@ -10,13 +10,18 @@
  *   gcc -std=c99 -Wall -Iinclude examples/ookd_rx.c -o ookd_rx \
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
- * ookd_rx [--threshold <value>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate>
- *         [csv|pretty] [dig.csv]
+ * ookd_rx [--threshold <value>|auto] [--tune <hz>] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none>
+ *         <samplerate> [csv|pretty] [dig.csv]
  *
  * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
  * it is; `auto` surveys the capture's envelope levels first (ookd_survey_*, ookd_suggest_threshold), reports
  * the two levels and the threshold between them on stderr and decodes with that -- or, when the capture does
  * not show two levels, says so and exits non-zero without decoding.
+ *
+ * --tune <hz>: the carrier sits <hz> beside the capture's centre (a receiver tuned next to the transmitter to keep
+ * its DC spike out of the way): the context filters with taps tuned to hz / samplerate cycles per sample
+ * (ookd_rx_create_tuned).  Not together with `--threshold auto`: the survey filters with the real taps around
+ * 0 Hz and would measure the DC term, not the carrier.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,6 +40,7 @@ int main(int argc, char **argv)
     /* --threshold <value>|auto is taken out of argv; what is left is positional, as before */
     float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
     int threshold_auto = 0, bad_option = 0;
+    double tune_hz = 0.0;
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--threshold")) {
@@ -44,14 +50,25 @@ int main(int argc, char **argv)
             threshold_auto = 0;
             threshold = strtof(argv[i], &end);
             if (end == argv[i] || *end != '\0') { bad_option = 1; break; }
+        } else if (!strcmp(argv[i], "--tune")) {
+            char *end = NULL;
+            if (++i >= argc) { bad_option = 1; break; }
+            tune_hz = strtod(argv[i], &end);
+            if (end == argv[i] || *end != '\0') { bad_option = 1; break; }
         } else {
             argv[kept++] = argv[i];
         }
     }
     argc = kept;
     if (argc < 5 || bad_option) {
-        fprintf(stderr, "usage: %s [--threshold <value>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> "
+        fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>] <capture.sc16q11|.cs8|.cu8> <device.json> "
                         "<filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n", argv[0]);
+        return EXIT_FAILURE;
+    }
+    if (threshold_auto && tune_hz != 0.0) {
+        fprintf(stderr, "%s: --threshold auto cannot be combined with --tune: the survey filters with the real taps "
+                        "around 0 Hz and would measure the DC term, not the carrier at %g Hz; give a threshold\n",
+                argv[0], tune_hz);
         return EXIT_FAILURE;
     }
     const int fmt = (argc > 5 && !strcmp(argv[5], "csv")) ? OOKD_RX_FMT_CSV : OOKD_RX_FMT_PRETTY;
@@ -117,8 +134,11 @@ int main(int argc, char **argv)
     rc.samples_per_buffer = cfg.samples_per_buffer;
     rc.max_samples = n ? n : 1;
     rc.flags = (uint32_t) sdr_hip_file_sample_flags(sdr);   /* a .cs8 / .cu8 capture: an 8-bit context */
-    rx = ookd_rx_create(&rc, filter, device);
-    if (!rx) { fail("ookd_rx_create"); goto out; }
+    ookd_tune tune;
+    memset(&tune, 0, sizeof(tune));
+    tune.nu = rate ? tune_hz / (double) rate : 0.0;     /* cycles per input sample; 0 = ookd_rx_create */
+    rx = ookd_rx_create_tuned(&rc, filter, device, &tune);
+    if (!rx) { fail("ookd_rx_create_tuned"); goto out; }
 
     if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }
 

@@ -84,6 +84,39 @@ int ookd_filter_stage(const ookd_filter *f, uint32_t stage,
                       const float **taps);
 
 /* ------------------------------------------------------------------------
+ * Frequency-tuned taps: decode a carrier that is NOT at 0 Hz (a zero-IF
+ * receiver tuned beside the transmitter to keep its DC spike out of the way;
+ * one of several transmitters in a wide capture) with the low-pass filters as
+ * they are.  The slicer only looks at |y|, and
+ *   | sum_k h[k] x[n-k] e^{-j 2 pi nu (n-k)} | = | sum_k (h[k] e^{+j 2 pi nu k}) x[n-k] |,
+ * so "mix down by nu, then low-pass with h" has the envelope of ONE FIR with
+ * complex taps c[k] = h[k] e^{j 2 pi nu k} on the raw samples: no oscillator,
+ * no phase state -- a capture, a chunk or a shard may start anywhere.
+ *
+ * nu = carrier offset in cycles per INPUT sample (offset_hz / sample_rate),
+ * |nu| <= 0.5.  The contract, taps (pure host code, no GPU): for stage s with
+ * P_s = the product of the decimations before it, tap k:
+ *     t = nu * (P_s k) (double; P_s k is an integer),  r = t - rint(t),
+ *     re[k] = (float)(h[k] * cos(2 pi r)),   im[k] = (float)(h[k] * sin(2 pi r)),
+ * evaluated for |nu| with the sign of nu put on im afterwards, and a sine that
+ * is exactly 0 giving im = 0 of that sign.  So nu = 0 gives re == h bitwise and
+ * im == +0; -nu gives the same re and the bitwise negated im, also on the taps
+ * whose phase is a whole turn.  re / im receive num_taps of that stage each.
+ * OOKD_ERR_ARG for NaN, |nu| > 0.5, NULL, a stage the filter does not have.
+ *
+ * The contract, one stage output: all float32, UNFUSED, taps newest sample
+ * first (k = 0 multiplies the newest sample, as fir.c does), accumulators
+ * from +0, four statements per tap in this order:
+ *     ar = ar + re[k]*xr;   ar = ar - im[k]*xi;
+ *     ai = ai + re[k]*xi;   ai = ai + im[k]*xr;
+ * Stages chain, decimate and start from zero history exactly as the untuned
+ * path; the power is ar*ar + ai*ai against the same threshold.  With im == 0
+ * every extra term is +-0, so nu = 0 is the reference's result bit for bit.
+ * ---------------------------------------------------------------------- */
+int ookd_filter_tuned_taps(const ookd_filter *f, double nu, uint32_t stage,
+                           float *re, float *im);
+
+/* ------------------------------------------------------------------------
  * Device: replaces device_init / device_deinit (src/device.h:47-91, loader
  * src/device.c:76-632) for the rx direction.  `sample_rate` is the rate the
  * state machine sees, i.e. samplerate / total decimation (src/main.c:683).
@@ -304,7 +337,16 @@ enum {
      * generic shapes); the staging buffer is allocated on the first such run. */
     OOKD_FRONT_NO_FILTER_8 = 9,
     OOKD_FRONT_FIR1_MFMA_8 = 10,
-    OOKD_FRONT_FIR2_MFMA_8 = 11
+    OOKD_FRONT_FIR2_MFMA_8 = 11,
+    /* Tuned contexts (ookd_rx_create_tuned, nu != 0): complex taps on the raw
+     * samples.  Both read SC16Q11; an 8-bit tuned context runs them on a widened
+     * staging copy of the capture, like the non-fused forms above. */
+    OOKD_FRONT_TUNED_GENERIC = 12,  /* any shape, the contract's order throughout
+                                       (also what OOKD_RX_EXACT_FIR selects):
+                                       KEEP_FIR floats are the contract's       */
+    OOKD_FRONT_TUNED_FIR1 = 13      /* 1 stage, decimation 1, <= 256 taps:
+                                       packed-VALU FMA (four per sample-tap) +
+                                       guard band, recompute in contract order  */
 };
 
 /* The front end a context settled on at create time, and the forward error
@@ -316,17 +358,38 @@ typedef struct ookd_front_info {
     uint32_t form;                  /* OOKD_FRONT_* of a run started now       */
     uint32_t mfma_ksteps;           /* K-steps of the matrix-core product (0 = none prepared) */
     float p_star;                   /* smallest power whose sqrtf >= threshold */
-    float p_lo, p_hi;               /* the packed-VALU kernels' band           */
+    float p_lo, p_hi;               /* the packed-VALU kernels' band (tuned
+                                       context: OOKD_FRONT_TUNED_FIR1's)       */
     float mfma_c;                   /* matrix-core accumulator -> output scale */
     double err_nominal;             /* matrix-core form, samples in [-2048, 2047] */
     double err_wide;                /* matrix-core form, any int16 samples     */
-    double err_valu;                /* packed-VALU form, any int16 samples     */
+    double err_valu;                /* packed-VALU form, any int16 samples
+                                       (tuned context: OOKD_FRONT_TUNED_FIR1
+                                       against the contract's order)           */
     double mfma_delta;              /* sum |h - (h1 + h2)|: what the two fp16
                                        tap pieces do not carry                 */
 } ookd_front_info;
 
 ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
                         const ookd_device *device);
+/* A context tuned to a carrier at nu cycles per input sample (see
+ * ookd_filter_tuned_taps for the contract).  tune == NULL or nu == 0 IS
+ * ookd_rx_create: same kernels, same front_form.  Otherwise the front end is
+ * one of the OOKD_FRONT_TUNED_* forms; bit words, edges, state machine,
+ * recorders, batches, shards and ookd_rx_halo_samples are what they were, and
+ * every run entry point below works.  OOKD_RX_FIR_VALU is accepted and changes
+ * nothing.  Fails for NaN or |nu| > 0.5, and for nu != 0 without a filter:
+ * |x| of the unfiltered samples does not depend on nu, there is nothing to tune.
+ * Not tuned (yet): the matrix-core forms, the folded decimate-by-4 kernel (a
+ * tuned fs128_fs16_dec4 runs OOKD_FRONT_TUNED_GENERIC), ookd_survey_*,
+ * ookd_fir_*. */
+typedef struct ookd_tune {
+    double nu;                      /* cycles per input sample, |nu| <= 0.5     */
+    uint64_t reserved[3];           /* zero                                     */
+} ookd_tune;
+ookd_rx *ookd_rx_create_tuned(const ookd_rx_config *cfg, const ookd_filter *filter,
+                              const ookd_device *device, const ookd_tune *tune);
+double ookd_rx_tune(const ookd_rx *rx);    /* nu of the context, 0 for an untuned one */
 void ookd_rx_destroy(ookd_rx *rx);
 /* Bytes per input sample of this context: 4 (SC16Q11) or 2 (CS8 / CU8).  Everywhere below a sample
  * count, stride or halo length counts samples of that size, and a pointer to samples is a pointer

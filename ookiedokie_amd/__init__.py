@@ -63,6 +63,8 @@ FRONT_FIR2_MFMA = 8
 FRONT_NO_FILTER_8 = 9                   # the fused forms of an 8-bit context
 FRONT_FIR1_MFMA_8 = 10
 FRONT_FIR2_MFMA_8 = 11
+FRONT_TUNED_GENERIC = 12                # a tuned context (Receiver(tune=...)): any shape, the contract's order
+FRONT_TUNED_FIR1 = 13                   # ... 1 stage, decimation 1, <= 256 taps: packed FMAs + guard band
 LEVEL_BINS = 256                        # OOKD_LEVEL_BINS: envelope survey, four bins per octave of power
 LEVEL_MIN_SEPARATION = 18               # OOKD_LEVEL_MIN_SEPARATION
 LEVEL_MIN_SIDE = 512                    # OOKD_LEVEL_MIN_SIDE
@@ -146,6 +148,10 @@ class FrontInfo(C.Structure):
     ]
 
 
+class Tune(C.Structure):
+    _fields_ = [("nu", C.c_double), ("reserved", C.c_uint64 * 3)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("seed", C.c_uint64), ("sample_rate", C.c_uint32), ("amplitude", C.c_uint32),
@@ -196,6 +202,7 @@ _PROTOTYPES = {
     "ookd_filter_num_stages": (C.c_uint32, [C.c_void_p]),
     "ookd_filter_stage": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_float))]),
+    "ookd_filter_tuned_taps": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
     "ookd_device_load": (C.c_void_p, [C.c_char_p, C.c_uint32]),
     "ookd_device_create": (C.c_void_p, [C.POINTER(FsmTables)]),
     "ookd_device_free": (None, [C.c_void_p]),
@@ -204,6 +211,8 @@ _PROTOTYPES = {
     "ookd_device_state_name": (C.c_char_p, [C.c_void_p, C.c_uint32]),
     "ookd_device_tables": (C.c_int, [C.c_void_p, C.POINTER(FsmTables)]),
     "ookd_rx_create": (C.c_void_p, [C.POINTER(RxConfig), C.c_void_p, C.c_void_p]),
+    "ookd_rx_create_tuned": (C.c_void_p, [C.POINTER(RxConfig), C.c_void_p, C.c_void_p, C.POINTER(Tune)]),
+    "ookd_rx_tune": (C.c_double, [C.c_void_p]),
     "ookd_rx_destroy": (None, [C.c_void_p]),
     "ookd_rx_sample_bytes": (C.c_uint32, [C.c_void_p]),
     "ookd_rx_process_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
@@ -337,6 +346,16 @@ class Filter:
         p = C.POINTER(C.c_float)()
         _check(lib().ookd_filter_stage(self._h, s, C.byref(d), C.byref(n), C.byref(p)))
         return int(d.value), np.ctypeslib.as_array(p, shape=(n.value,)).copy()
+
+    def tuned_taps(self, nu: float, stage: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The complex taps (re, im: float32) a context tuned to `nu` cycles per input sample runs stage `stage`
+        with (ookd_filter_tuned_taps; pure host code)."""
+        if not 0 <= stage < self.num_stages:
+            raise OokdError(-1, "filter has no stage %d" % stage)
+        n = self.stage(stage)[1].size
+        re, im = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        _check(lib().ookd_filter_tuned_taps(self._h, float(nu), stage, re.ctypes.data, im.ctypes.data))
+        return re, im
 
     def close(self) -> None:
         if self._h:
@@ -594,7 +613,20 @@ class Receiver:
                  quiet_skip: bool = True, count_quiet: bool = False, scan_sims: bool = False,
                  pipeline: bool = True, pipeline_chunk_samples: int = 0,
                  front_gate: Optional["FrontGate"] = None, fir_valu: bool = False,
-                 scan_tables: bool = False, sample_format: str = "sc16q11"):
+                 scan_tables: bool = False, sample_format: str = "sc16q11",
+                 tune: Optional[float] = None, tune_hz: Optional[float] = None,
+                 sample_rate: Optional[float] = None):
+        """tune: carrier offset in cycles per input sample (|tune| <= 0.5), or tune_hz with sample_rate -- one
+        of the two forms.  The context then filters with the taps `Filter.tuned_taps` returns (ookd_rx_create_tuned);
+        0 is an untuned context."""
+        if tune is not None and (tune_hz is not None or sample_rate is not None):
+            raise ValueError("give either tune (cycles per sample) or tune_hz with sample_rate, not both")
+        if (tune_hz is None) != (sample_rate is None):
+            raise ValueError("tune_hz and sample_rate go together")
+        if tune_hz is not None:
+            if not sample_rate > 0:
+                raise ValueError("sample_rate must be positive")
+            tune = float(tune_hz) / float(sample_rate)
         if sample_format not in SAMPLE_FORMATS:
             raise ValueError("sample_format must be one of %s" % ", ".join(sorted(SAMPLE_FORMATS)))
         self.sample_format = sample_format
@@ -621,10 +653,21 @@ class Receiver:
         self._filter, self._device = filt, device
         self.payload_bytes = device.payload_bytes if device else 0
         self.total_decimation = filt.total_decimation if filt else 1
-        self._h = lib().ookd_rx_create(C.byref(cfg), filt._h if filt else None,
-                                       device._h if device else None)
+        if tune is None:
+            self._h = lib().ookd_rx_create(C.byref(cfg), filt._h if filt else None,
+                                           device._h if device else None)
+        else:
+            t = Tune()
+            t.nu = float(tune)
+            self._h = lib().ookd_rx_create_tuned(C.byref(cfg), filt._h if filt else None,
+                                                 device._h if device else None, C.byref(t))
         if not self._h:
             raise OokdError(-4, last_error())
+
+    @property
+    def tune(self) -> float:
+        """Carrier offset this context is tuned to, cycles per input sample (0: untuned)."""
+        return float(lib().ookd_rx_tune(self._h))
 
     # -- runs ---------------------------------------------------------------
     def rx_device(self, d_iq_ptr: int, samples_per_capture: int, num_captures: int = 1,

@@ -76,4 +76,7 @@ struct ookd_device {
 namespace ookd {
 // Fills the integer tables from the *_us fields; false + error on failure.
 bool build_count_tables(ookd_device &d);
+// Complex taps of a tuned context for one stage (loaders.cpp; the rule is in the header at ookd_filter_tuned_taps):
+// re / im receive h.size() floats each.  before = product of the decimations in front of the stage.
+void tuned_stage_taps(const std::vector<float> &h, double nu, uint64_t before, float *re, float *im);
 }

@@ -1,0 +1,206 @@
+// front_dev.hpp -- device code shared by the front-end kernel files (kernels.hip, fir_tuned.hip): sample
+// unpacking, the 1-stage kernels' LDS window layout, and everything behind a tile's accumulators (threshold,
+// guard band, bit packing, tile info).  Compiled with -ffp-contract=off: every a*b+c is a separately rounded
+// multiply and add; fused multiply-adds are written explicitly.
+#pragma once
+
+#include "kernels.hpp"
+
+#include <hip/hip_runtime.h>
+
+#pragma clang fp contract(off)
+
+namespace ookd {
+
+__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
+
+// complexf.h:68-77: (float)v * (1.0f/2048.0f), exact.
+__device__ __forceinline__ float2 unpack_iq(uint32_t w) {
+    const float s = 1.0f / 2048.0f;
+    float2 r;
+    r.x = (float)(int16_t)(w & 0xffffu) * s;
+    r.y = (float)(int16_t)(w >> 16) * s;
+    return r;
+}
+
+// One input sample of a capture as float2, honouring halo (index < 0) and
+// zero padding (index >= n_valid; bladeRF_file.c:113-117).
+__device__ __forceinline__ float2 fetch_sample(const FrontParams &p, const uint32_t *src,
+                                               const float2 *srcf, int64_t n) {
+    if (n < 0) {
+        const int64_t h = (int64_t)p.halo_len + n;
+        if (h < 0) return make_float2(0.0f, 0.0f);
+        if (p.halo_f32) return reinterpret_cast<const float2 *>(p.halo_f32)[h];
+        if (p.halo) return unpack_iq(reinterpret_cast<const uint32_t *>(p.halo)[h]);
+        return make_float2(0.0f, 0.0f);
+    }
+    if ((uint64_t)n >= p.n_valid) return make_float2(0.0f, 0.0f);
+    if (srcf) return srcf[n];
+    return unpack_iq(src[n]);
+}
+
+// ookiedokie.c:171-179: bit = sqrtf(re*re + im*im) >= thr.  sqrtf is
+// correctly rounded and monotone, so this equals power >= P*, P* being the
+// smallest float whose sqrtf is >= thr (host computes it).  The power keeps
+// the reference's three roundings (complexf.h:45).
+__device__ __forceinline__ float power_ref(float re, float im) {
+    const float rr = re * re;
+    const float ii = im * im;
+    return rr + ii;
+}
+
+// ---- LDS window of the 1-stage kernels ----------------------------------------
+// sample j lives at slot j + (j / R): one pad slot per R samples (R = outputs per lane, a power of two)
+// makes the lane stride R + 1 float2, which is conflict free for ds_read_b64 (32-lane halves, 64 banks),
+// and keeps every read of the unrolled MAC bodies at  lane_base + compile-time immediate.
+template <int R>
+__host__ __device__ __forceinline__ uint32_t slot(uint32_t j) { return j + j / (uint32_t)R; }
+
+// float2 slots of one wavefront's private window (kept a multiple of 2 = 16 B)
+template <int R>
+__host__ __device__ __forceinline__ uint32_t fir1_wave_slots(uint32_t Tp) {
+    return (slot<R>(64u * R + Tp) + 2u) & ~1u;
+}
+
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v8f __attribute__((ext_vector_type(8)));
+typedef short v2s __attribute__((ext_vector_type(2)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+// non-temporal 16 B load: the capture is streamed through once (tools/stream_bw.hip: +7 % over plain loads)
+__device__ __forceinline__ uint4 ld_nt4(const uint4 *p) {
+    const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ v2s as_v2s(uint32_t w) { return __builtin_bit_cast(v2s, w); }
+
+// Everything behind the accumulators of one wave tile of a 1-stage kernel (lane `tid` holds outputs
+// t0 + R tid .. + R - 1 in acc): threshold + guard band, bit packing, optional float output.  `exact(r)`
+// recomputes the lane's output r in the reference's (the contract's) unfused order.  Stores the tile's bit
+// words and returns the tile info word (level changes inside the tile | first bit << 30 | last bit << 31).
+// (fir1_bits_kernel keeps its own inlined copy of this text in fir1_tile_compute, kernels.hip: routed through this
+// function its register allocation moved, and its instruction stream is pinned by measurements.)
+template <bool EXACT, int R, typename Exact>
+__device__ __forceinline__ uint32_t fir1_tile_finish(const FrontParams &p, const v2f *acc, uint64_t t0, uint32_t tid,
+                                                     uint32_t cap, uint64_t *words, Exact exact) {
+    uint32_t info = 0;
+    // ---- threshold, guard band, pack -----------------------------------------
+    // Per output: power (packed square + add), one compare per bound whose
+    // wave-wide result lands in an SGPR pair, and the lane's own bit shifted
+    // into `mask` through the carry (r runs downwards so bit r ends at position
+    // r).  The "inside the guard band" masks are OR-ed on the scalar unit.
+    const uint64_t o0 = t0 + (uint64_t)tid * R;
+    uint32_t mask = 0;
+    uint64_t any_unsure = 0;
+#pragma unroll
+    for (int r = R - 1; r >= 0; --r) {
+        float pw;
+        if (EXACT) {
+            pw = power_ref(acc[r].x, acc[r].y);
+        } else {
+            v2f sq;
+            asm("v_pk_mul_f32 %0, %1, %1" : "=v"(sq) : "v"(acc[r]));
+            pw = sq.x + sq.y;
+        }
+        const uint64_t ge_hi = __ballot(pw >= (EXACT ? p.p_star : p.p_hi));
+        asm("v_addc_co_u32_e64 %0, vcc, %0, %0, %1" : "+v"(mask) : "s"(ge_hi) : "vcc");
+        if (!EXACT) any_unsure |= __ballot(pw >= p.p_lo) & ~ge_hi;
+    }
+    if (!EXACT && any_unsure != 0) {
+        // some lane of this wave has a sample inside the band: those lanes redo
+        // their borderline samples in the reference's exact order
+        uint32_t todo = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            v2f sq;
+            asm("v_pk_mul_f32 %0, %1, %1" : "=v"(sq) : "v"(acc[r]));
+            const float pf = sq.x + sq.y;
+            if (pf >= p.p_lo && !(pf >= p.p_hi) && o0 + r < p.n_out) todo |= 1u << r;
+        }
+        const uint32_t redo = (uint32_t)__popc(todo);
+        while (todo) {                          // one copy of the recompute, whichever outputs need it
+            const uint32_t r = (uint32_t)__ffs((int)todo) - 1u;
+            todo &= todo - 1u;
+            const float2 y = exact(r);
+            const float pe = power_ref(y.x, y.y);
+            mask = (mask & ~(1u << r)) | ((pe >= p.p_star ? 1u : 0u) << r);
+        }
+        if (redo && p.recompute_count) atomicAdd(p.recompute_count, (unsigned long long)redo);
+    }
+    // outputs past the end of the (padded) capture do not exist
+    if (o0 + R > p.n_out) {
+        const uint32_t keep = o0 >= p.n_out ? 0u : (uint32_t)(p.n_out - o0);
+        mask &= (keep >= 32 ? 0xffffffffu : ((1u << keep) - 1u));
+    }
+
+    if (p.fir_out) {
+        float2 *out = reinterpret_cast<float2 *>(p.fir_out) + (uint64_t)cap * p.n_out;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (o0 + r < p.n_out) out[o0 + r] = make_float2(acc[r].x, acc[r].y);
+        }
+    }
+
+    // level changes inside the tile (what edge_count would find in these 1024 bits,
+    // minus the comparison of the tile's first bit with the tile before)
+    {
+        const uint32_t keep = o0 >= p.n_out ? 0u : (o0 + R <= p.n_out ? (uint32_t)R : (uint32_t)(p.n_out - o0));
+        const uint32_t prev_top = __shfl_up(mask >> (R - 1), 1);       // bit 15 of the lane before
+        uint32_t ch = (mask ^ (mask << 1)) & ((1u << R) - 2u);
+        if (tid != 0) ch |= (mask ^ prev_top) & 1u;
+        ch &= keep >= 32 ? 0xffffffffu : ((1u << keep) - 1u);
+        uint32_t cnt = __popc(ch);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(mask & 1u));
+        const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)((mask >> (R - 1)) & 1u), 63);
+        // the word that holds the first change: lane l holds bits R l .. R l + R - 1 of the tile
+        const uint64_t chl = __ballot(ch != 0);
+        const uint32_t widx = chl ? ((uint32_t)__builtin_ctzll(chl) * (uint32_t)R) >> 6 : 0u;
+        info = cnt | (widx << kTileWordShift) | (first << 30) | (last << 31) | p.stamp_bits;
+    }
+
+    // 64 / R lanes x R bits -> one 64-bit word
+    constexpr uint32_t kLanesPerWord = 64u / R;
+    uint64_t w64 = (uint64_t)mask << (R * (tid % kLanesPerWord));
+#pragma unroll
+    for (uint32_t d = 1; d < kLanesPerWord; d <<= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)w64, (int)d), hi = __shfl_xor((uint32_t)(w64 >> 32), (int)d);
+        w64 |= (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    if (tid % kLanesPerWord == 0) words[(t0 >> 6) + tid / kLanesPerWord] = w64;
+    return info;
+}
+
+// ---- generic kernels: the slice of every level one tile of final outputs needs ----------
+// Level 0 is the unpacked input, level s+1 the output of stage s.  Stage output J (global) reads
+// level-s inputs D*(J+1)-1-k (fir.c:290: the countdown starts at D, so the first output is at
+// input index D-1).
+struct GenLevel {
+    int64_t a;          // first local index needed at this level
+    uint32_t len;       // samples needed
+};
+
+__device__ __forceinline__ void gen_levels(const FrontParams &p, int64_t j0, uint32_t L,
+                                           GenLevel *lv, int64_t *off) {
+    // global origin of each level: g_{s+1} = floor(g_s / D_s)
+    uint64_t g = p.origin;
+    const int S = (int)p.num_stages;
+    for (int s = 0; s < S; ++s) {
+        const uint64_t D = p.stage[s].decim;
+        const uint64_t gn = g / D;
+        off[s] = (int64_t)(D * gn + D - 1) - (int64_t)g;    // = D-1-(g mod D)
+        g = gn;
+    }
+    lv[S].a = j0;
+    lv[S].len = L;
+    for (int s = S - 1; s >= 0; --s) {
+        const int64_t D = p.stage[s].decim;
+        const int64_t T = p.stage[s].ntaps;
+        lv[s].a = D * lv[s + 1].a + off[s] - (T - 1);
+        lv[s].len = (uint32_t)(D * ((int64_t)lv[s + 1].len - 1) + T);
+    }
+}
+
+}  // namespace ookd

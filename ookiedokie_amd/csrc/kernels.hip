@@ -15,6 +15,7 @@
 // multiply-adds are written explicitly with __builtin_fmaf.
 #include "kernels.hpp"
 #include "common.hpp"
+#include "front_dev.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -28,37 +29,10 @@
 namespace ookd {
 
 // ---------------------------------------------------------------------------
-// small helpers
+// small helpers (the ones shared with fir_tuned.hip: front_dev.hpp)
 // ---------------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-// complexf.h:68-77: (float)v * (1.0f/2048.0f), exact.
-__device__ __forceinline__ float2 unpack_iq(uint32_t w) {
-    const float s = 1.0f / 2048.0f;
-    float2 r;
-    r.x = (float)(int16_t)(w & 0xffffu) * s;
-    r.y = (float)(int16_t)(w >> 16) * s;
-    return r;
-}
-
-// One input sample of a capture as float2, honouring halo (index < 0) and
-// zero padding (index >= n_valid; bladeRF_file.c:113-117).
-__device__ __forceinline__ float2 fetch_sample(const FrontParams &p, const uint32_t *src,
-                                               const float2 *srcf, int64_t n) {
-    if (n < 0) {
-        const int64_t h = (int64_t)p.halo_len + n;
-        if (h < 0) return make_float2(0.0f, 0.0f);
-        if (p.halo_f32) return reinterpret_cast<const float2 *>(p.halo_f32)[h];
-        if (p.halo) return unpack_iq(reinterpret_cast<const uint32_t *>(p.halo)[h]);
-        return make_float2(0.0f, 0.0f);
-    }
-    if ((uint64_t)n >= p.n_valid) return make_float2(0.0f, 0.0f);
-    if (srcf) return srcf[n];
-    return unpack_iq(src[n]);
-}
-
-// Same for int16 inputs, returned raw (packed I | Q << 16).
+// fetch_sample for int16 inputs, returned raw (packed I | Q << 16).
 __device__ __forceinline__ uint32_t fetch_raw(const FrontParams &p, const uint32_t *src, int64_t n) {
     if (n < 0) {
         const int64_t h = (int64_t)p.halo_len + n;
@@ -67,16 +41,6 @@ __device__ __forceinline__ uint32_t fetch_raw(const FrontParams &p, const uint32
     }
     if ((uint64_t)n >= p.n_valid) return 0u;
     return src[n];
-}
-
-// ookiedokie.c:171-179: bit = sqrtf(re*re + im*im) >= thr.  sqrtf is
-// correctly rounded and monotone, so this equals power >= P*, P* being the
-// smallest float whose sqrtf is >= thr (host computes it).  The power keeps
-// the reference's three roundings (complexf.h:45).
-__device__ __forceinline__ float power_ref(float re, float im) {
-    const float rr = re * re;
-    const float ii = im * im;
-    return rr + ii;
 }
 
 // ---------------------------------------------------------------------------
@@ -94,20 +58,10 @@ __device__ __forceinline__ float power_ref(float re, float im) {
 // accumulators -- so every output sees its taps in the reference order
 // (tap 0 / newest sample first, fir.c:313-318).
 //
-// LDS layout: sample j lives at slot j + (j >> 4): one pad slot per 16
+// LDS layout (slot<R>, front_dev.hpp): sample j lives at slot j + (j >> 4): one pad slot per 16
 // samples makes the lane stride 17 float2 = 34 dwords, which is conflict
 // free for ds_read_b64 (32-lane halves, 64 banks), and keeps every read of
 // the unrolled body at  lane_base + compile-time immediate.
-
-// one pad slot per R samples (R = outputs per lane, a power of two)
-template <int R>
-__host__ __device__ __forceinline__ uint32_t slot(uint32_t j) { return j + j / (uint32_t)R; }
-
-// float2 slots of one wavefront's private window (kept a multiple of 2 = 16 B)
-template <int R>
-__host__ __device__ __forceinline__ uint32_t fir1_wave_slots(uint32_t Tp) {
-    return (slot<R>(64u * R + Tp) + 2u) & ~1u;
-}
 
 // Sequential, unfused recomputation of one output (guard-band path).
 template <int R>
@@ -124,9 +78,6 @@ __device__ __noinline__ float2 fir1_exact_output(const float2 *lds, uint32_t j_o
     }
     return make_float2(re, im);
 }
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v8f __attribute__((ext_vector_type(8)));
 
 // One complex multiply-accumulate acc(re,im) += tap * x(re,im) as a packed
 // fp32 instruction with the tap read from an SGPR pair: `tp` holds two
@@ -173,17 +124,6 @@ __device__ __forceinline__ void fir1_chunk(v2f *acc, const v2f *tpair, const v2f
                                            std::integer_sequence<int, Ws...>) {
     (fir1_wstep<EXACT, R, R - 1 - Ws>(acc, tpair, base, std::make_integer_sequence<int, R>{}), ...);
 }
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-// non-temporal 16 B load: the capture is streamed through once (tools/stream_bw.hip: +7 % over plain loads)
-__device__ __forceinline__ uint4 ld_nt4(const uint4 *p) {
-    const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ v2s as_v2s(uint32_t w) { return __builtin_bit_cast(v2s, w); }
 
 // Everything behind the staged window of one wave tile: packed MACs over the
 // tap chunks, threshold + guard band, bit packing, optional float output.
@@ -677,33 +617,7 @@ typedef Fir2Geom<2, 1, 2, 2, 4> Fir2Dec4;      // fs128_fs16_dec4: (D 2, 16 taps
 // level s+1 the output of stage s; the slice of every level the tile needs
 // is produced in LDS, ping-ponging between two buffers.  Stage output J
 // (global) reads level-s inputs D*(J+1)-1-k (fir.c:290: the countdown starts
-// at D, so the first output is at input index D-1).
-
-struct GenLevel {
-    int64_t a;          // first local index needed at this level
-    uint32_t len;       // samples needed
-};
-
-__device__ __forceinline__ void gen_levels(const FrontParams &p, int64_t j0, uint32_t L,
-                                           GenLevel *lv, int64_t *off) {
-    // global origin of each level: g_{s+1} = floor(g_s / D_s)
-    uint64_t g = p.origin;
-    const int S = (int)p.num_stages;
-    for (int s = 0; s < S; ++s) {
-        const uint64_t D = p.stage[s].decim;
-        const uint64_t gn = g / D;
-        off[s] = (int64_t)(D * gn + D - 1) - (int64_t)g;    // = D-1-(g mod D)
-        g = gn;
-    }
-    lv[S].a = j0;
-    lv[S].len = L;
-    for (int s = S - 1; s >= 0; --s) {
-        const int64_t D = p.stage[s].decim;
-        const int64_t T = p.stage[s].ntaps;
-        lv[s].a = D * lv[s + 1].a + off[s] - (T - 1);
-        lv[s].len = (uint32_t)(D * ((int64_t)lv[s + 1].len - 1) + T);
-    }
-}
+// at D, so the first output is at input index D-1): gen_levels, front_dev.hpp.
 
 template <bool F32IN>
 __global__ __launch_bounds__(256) void fir_generic_kernel(const FrontParams p, uint32_t lds_b_off) {
@@ -1056,6 +970,8 @@ static bool use_fir2(const FrontParams &p) {
 //  number, on a widened copy)
 uint32_t front_form(const FrontParams &p, bool exact) {
     const bool s8 = p.sample_fmt != kFmtSc16;
+    // a tuned context (fir_tuned.hip): its two forms, both on SC16Q11 samples (8-bit captures are widened first)
+    if (p.tune && p.num_stages) return front_uses_tuned_fir1(p) && !exact ? OOKD_FRONT_TUNED_FIR1 : OOKD_FRONT_TUNED_GENERIC;
     if (p.num_stages == 0) return s8 ? OOKD_FRONT_NO_FILTER_8 : OOKD_FRONT_NO_FILTER;
     if (use_fir1(p)) {
         if (front_uses_mfma(p) && !exact) return s8 ? OOKD_FRONT_FIR1_MFMA_8 : OOKD_FRONT_FIR1_MFMA;
@@ -1069,6 +985,9 @@ uint32_t front_form(const FrontParams &p, bool exact) {
 }
 
 uint64_t front_wave_tiles(const FrontParams &p) {
+    if (p.tune && p.num_stages) {
+        return front_uses_tuned_fir1(p) ? ((p.n_out + kFirTile - 1) / kFirTile) * (kFirTile / tuned_fir1_tile_bits(p)) : 0;
+    }
     if (p.num_stages == 0) return ((p.n_out + kFirTile - 1) / kFirTile) * (kFirTile / kWaveTile);
     if (use_fir1(p)) return ((p.n_out + kFirTile - 1) / kFirTile) * (kFirTile / (64 * fir1_R(p)));
     if (use_fir2(p)) {
@@ -1079,6 +998,7 @@ uint64_t front_wave_tiles(const FrontParams &p) {
 }
 
 uint32_t front_tile_bits(const FrontParams &p) {
+    if (p.tune && p.num_stages) return front_uses_tuned_fir1(p) ? tuned_fir1_tile_bits(p) : 0;
     if (p.num_stages == 0) return kWaveTile;
     if (use_fir1(p)) return 64 * fir1_R(p);
     if (use_fir2(p)) return Fir2Dec4::F;
@@ -1109,6 +1029,15 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
     if (p.sample_fmt != kFmtSc16 && form != OOKD_FRONT_NO_FILTER_8 && form != OOKD_FRONT_FIR1_MFMA_8 &&
         form != OOKD_FRONT_FIR2_MFMA_8) {
         return hipErrorInvalidValue;        // no 8-bit kernel of this form: the caller widens first
+    }
+    if (form == OOKD_FRONT_TUNED_FIR1) return launch_front_tuned_fir1(p, num_captures, stream, t0, t1, tile_begin, tile_count);
+    if (form == OOKD_FRONT_TUNED_GENERIC) {
+        if (tile_begin != 0 || tile_count != ~0ull) return hipErrorInvalidValue;     // whole captures only
+        if (t0 && hipEventRecord(t0, stream) != hipSuccess) return hipGetLastError();
+        const hipError_t e = launch_front_tuned_generic(p, num_captures, stream);
+        if (e != hipSuccess) return e;
+        if (t1 && hipEventRecord(t1, stream) != hipSuccess) return hipGetLastError();
+        return hipSuccess;
     }
     if (form == OOKD_FRONT_NO_FILTER || form == OOKD_FRONT_NO_FILTER_8) {
         // whole 4096-sample blocks, so every bit word of the capture is written
@@ -1170,6 +1099,7 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
 bool front_sparse_capable(const FrontParams &p) {
     // (round 3: the two-stage kernels too -- their quiet tiles stored 36 bytes each, 150 MB of small stores per
     //  16 GiB capture beside the read stream: the backend default filter ran 15 % behind the 1-stage one for it)
+    if (p.tune && p.num_stages) return front_uses_tuned_fir1(p) && p.quiet_lsb > 0 && !p.fir_out;
     return (use_fir1(p) || use_fir2(p)) && p.quiet_lsb > 0 && !p.fir_out;
 }
 

@@ -81,6 +81,12 @@ struct FrontParams {
     uint32_t sample_fmt;        // kFmt*: what iq and halo hold.  The 8-bit formats are 2 bytes per sample (I, Q) and
                                 // only run on the forms front_form() numbers OOKD_FRONT_*_8; for every other form
                                 // the context widens the capture first and passes kFmtSc16 (rx.cpp: widen_for_form)
+    // frequency-tuned front end (fir_tuned.hip): complex taps c[k] = h[k] e^{j 2 pi nu P_s k} on the raw samples
+    uint32_t tune;              // 0: real taps (everything above); 1: tuned; 2: tuned, the contract's order for every
+                                // shape (OOKD_RX_EXACT_FIR): the generic tuned kernel
+    const float *ctaps;         // (re, im) pairs, stage s at ctaps + 2 * tap_off, zero padded to ntaps_pad pairs
+    float quiet_a, quiet_b;     // tuned quiet test (quiet_lsb > 0): a window with component ranges up to `a` and
+                                // |min + max| up to `b` (raw LSB) is quiet when a * quiet_a + b * quiet_b < 1
 };
 
 // Sample formats.  An 8-bit sample IS the SC16Q11 sample of 16 times its value: CS8 v (int8) = 16 v, CU8 u (uint8) =
@@ -174,6 +180,13 @@ uint32_t front_form(const FrontParams &p, bool exact);
 uint64_t front_wave_tiles(const FrontParams &p);
 // bits per wave tile of the tuned kernel that serves this shape (0 = generic)
 uint32_t front_tile_bits(const FrontParams &p);
+// ---- frequency-tuned front end (fir_tuned.hip) --------------------------------------------
+// 1 stage, decimation 1, <= 256 taps and not forced to the contract's order: the packed-VALU kernel
+bool front_uses_tuned_fir1(const FrontParams &p);
+uint32_t tuned_fir1_tile_bits(const FrontParams &p);
+hipError_t launch_front_tuned_fir1(const FrontParams &p, uint32_t num_captures, hipStream_t stream, hipEvent_t t0,
+                                   hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count);
+hipError_t launch_front_tuned_generic(const FrontParams &p, uint32_t num_captures, hipStream_t stream);
 // Generic multi-stage kernel regardless of shape (cross-check / streaming FIR).
 hipError_t launch_front_generic(const FrontParams &p, uint32_t num_captures,
                                 hipStream_t stream);

@@ -19,6 +19,22 @@
 
 namespace ookd {
 
+// The tap rule of the tuned contract (include/ookiedokie_amd.h): stage taps h, decimation product `before`.
+// Evaluated for |nu| and the imaginary parts negated afterwards, a zero sine giving +0: so nu = 0 yields
+// im == +0 whatever the taps' signs, and -nu the bitwise negated im of nu also where the phase is a whole turn.
+void tuned_stage_taps(const std::vector<float> &h, double nu, uint64_t before, float *re, float *im) {
+    const double a = std::fabs(nu);
+    const bool neg = nu < 0.0;
+    for (size_t k = 0; k < h.size(); ++k) {
+        const double t = a * (double)(before * (uint64_t)k);
+        const double r = t - std::rint(t);
+        const double c = std::cos(2.0 * M_PI * r), s = std::sin(2.0 * M_PI * r);
+        re[k] = (float)((double)h[k] * c);
+        const float v = s == 0.0 ? 0.0f : (float)((double)h[k] * s);
+        im[k] = neg ? -v : v;
+    }
+}
+
 static thread_local std::string g_error;
 
 void set_error(const char *fmt, ...) {
@@ -645,6 +661,18 @@ int ookd_filter_stage(const ookd_filter *f, uint32_t stage, uint32_t *decimation
     if (decimation) *decimation = f->stages[stage].decimation;
     if (num_taps) *num_taps = (uint32_t)f->stages[stage].taps.size();
     if (taps) *taps = f->stages[stage].taps.data();
+    return OOKD_OK;
+}
+
+int ookd_filter_tuned_taps(const ookd_filter *f, double nu, uint32_t stage, float *re, float *im) {
+    clear_error();
+    if (!f || !re || !im || stage >= f->stages.size() || !(std::fabs(nu) <= 0.5)) {
+        set_error("ookd_filter_tuned_taps: needs a filter, one of its stages, two outputs and |nu| <= 0.5");
+        return OOKD_ERR_ARG;
+    }
+    uint64_t before = 1;
+    for (uint32_t s = 0; s < stage; ++s) before *= f->stages[s].decimation;
+    tuned_stage_taps(f->stages[stage].taps, nu, before, re, im);
     return OOKD_OK;
 }
 

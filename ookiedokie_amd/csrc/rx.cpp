@@ -369,6 +369,11 @@ struct ookd_rx : RxHandles {
     uint32_t mfma_ksteps = 0;
     uint32_t run_form = 0;          // OOKD_FRONT_* the last run launched (front_form)
     int quiet_lsb = 0;              // 0 = the quiet shortcut never applies
+    // tuned context (ookd_rx_create_tuned with nu != 0; fir_tuned.hip): complex taps as (re, im) pairs, stage s at
+    // 2 * tap_off, zero padded like d_taps; the tuned quiet test's two weights (FrontParams::quiet_a / quiet_b)
+    double tune_nu = 0.0;
+    DevBuf<float> d_ctaps;
+    float quiet_a = 0, quiet_b = 0;
     uint32_t tile_bits = 0;         // bits per wave tile of the front-end kernel (front_tile_bits), 0 = generic kernel
     bool exact = false;
     bool count_quiet = false;
@@ -550,6 +555,10 @@ struct ookd_rx : RxHandles {
         p.sparse = sparse ? 1u : 0u;
         p.stamp_bits = tile_stamp << kTileStampShift;
         p.sample_fmt = sample_fmt;
+        p.tune = tune_nu != 0.0 ? (exact ? 2u : 1u) : 0u;
+        p.ctaps = d_ctaps.p;
+        p.quiet_a = quiet_a;
+        p.quiet_b = quiet_b;
         return p;
     }
 
@@ -1533,6 +1542,91 @@ void setup_quiet_skip(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_conf
     }
 }
 
+// A tuned context's front end (fir_tuned.hip): the complex taps on the device, the guard band of the packed-FMA
+// kernel and its quiet test.  Replaces setup_front_form / setup_quiet_skip; setup_filter has run.
+//
+// Guard band.  One component of an output is a sum of 2T products (T taps, a real and an imaginary tap part
+// each), sum_k |terms| <= S x_max with S = sum_k (|re[k]| + |im[k]|) and x_max = 16 (32768 / 2048).  The fused
+// chain rounds once per step, the contract's chain twice (product, sum): both stay within gamma_{2T} resp.
+// gamma_{2T+1} of the exact sum times sum|terms| (gamma_n = n u / (1 - n u), u = 2^-24), so they differ by at most
+// (4T + 1) u S x_max (1 + O(T u)) <= 2.2 (2T + 1) u S x_max -- guard_error's form with twice the roundings per
+// tap and both tap parts in S; the 2^-140 term covers products and sums that round in the subnormals.
+// band_from_error turns it into [p_lo, p_hi) as for the real-tap kernels.  Several stages: as guard_error (each
+// stage amplifies what it is handed by at most its S and adds its own term); the generic tuned kernel computes in
+// the contract's order and needs no band, the figure is reported all the same.
+double tuned_guard_error(const std::vector<std::vector<float>> &re, const std::vector<std::vector<float>> &im, double x_max) {
+    const double u = std::ldexp(1.0, -24);
+    double S = 1.0, T = 0.0, Tsum = 0.0;
+    for (size_t s = 0; s < re.size(); ++s) {
+        double ss = 0.0;
+        for (size_t k = 0; k < re[s].size(); ++k) ss += std::fabs((double)re[s][k]) + std::fabs((double)im[s][k]);
+        S *= std::max(ss, 1.0);
+        T += 2.0 * (double)re[s].size() + 1.0;
+        Tsum += 2.0 * (double)re[s].size();
+    }
+    return 2.2 * T * u * S * x_max * (re.size() > 1 ? 1.01 : 1.0) + Tsum * std::ldexp(1.0, -140);
+}
+
+// Quiet test of fir1_tuned_kernel.  For any constant d:  y = sum_k c[k] (x[n-k] - d) + d sum_k c[k], so
+//     |y| <= A max|x - d| + G |d|,   A = sum_k |c[k]|,  G = |sum_k c[k]|  (the rounded taps' response at 0 Hz).
+// The kernel takes d = the midpoint of the window's component ranges: with a = the larger range and b = the
+// larger |min + max| (raw LSB), max|x - d| <= sqrt(2) a / 2 and |d| <= sqrt(2) b / 2.  The contract's float chain
+// is within gamma_{2T+1} S x_max of y per component (S as above, x_max <= (a + b) / 2 LSB), sqrt(2) times that in
+// magnitude.  So the computed |y| stays below the threshold when
+//     sqrt(2) / (2 * 2048) * ((A + e) a + (G + e) b) < 0.999 thr,      e = 1.01 (2T + 1) u S,
+// the 0.1 % covering the power's own three roundings and this test's float evaluation.  Only interior windows
+// are tested (every sample a capture sample), and only the 1-stage kernel has the test.
+void setup_tuned_quiet(ookd_rx &rx, const std::vector<float> &re, const std::vector<float> &im, const ookd_rx_config &cfg) {
+    if (!(cfg.threshold > 0.0f) || !std::isfinite(cfg.threshold) || (cfg.flags & OOKD_RX_NO_QUIET_SKIP)) return;
+    double A = 0.0, S = 0.0, gr = 0.0, gi = 0.0;
+    for (size_t k = 0; k < re.size(); ++k) {
+        A += std::hypot((double)re[k], (double)im[k]);
+        S += std::fabs((double)re[k]) + std::fabs((double)im[k]);
+        gr += (double)re[k];
+        gi += (double)im[k];
+    }
+    if (!(A > 0.0)) return;
+    const double G = std::hypot(gr, gi) + 1e-12 * S;        // (the double sums' own rounding)
+    const double e = 1.01 * (2.0 * (double)re.size() + 1.0) * std::ldexp(1.0, -24) * S;
+    const double scale = 1.41421356237309515 / (2.0 * 2048.0) / (0.999 * (double)cfg.threshold);
+    const double qa = (A + e) * scale, qb = (G + e) * scale;
+    if (!(qa < 1e30) || !(qb < 1e30)) return;
+    rx.quiet_a = nextafterf((float)qa, INFINITY);
+    rx.quiet_b = nextafterf((float)qb, INFINITY);
+    rx.quiet_lsb = 1;       // "the shortcut applies": the tuned kernel tests with quiet_a / quiet_b
+}
+
+bool setup_tuned(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg) {
+    std::vector<std::vector<float>> re, im;
+    std::vector<float> dev;
+    uint64_t before = 1;
+    for (uint32_t s = 0; s < rx.num_stages; ++s) {
+        const std::vector<float> &h = filter.stages[s].taps;
+        re.emplace_back(h.size());
+        im.emplace_back(h.size());
+        tuned_stage_taps(h, rx.tune_nu, before, re[s].data(), im[s].data());
+        before *= filter.stages[s].decimation;
+        // zero padding keeps sums bit-identical, as in setup_filter
+        dev.resize(2 * (size_t)(rx.stage[s].tap_off + rx.stage[s].ntaps_pad), 0.0f);
+        for (size_t k = 0; k < h.size(); ++k) {
+            dev[2 * (rx.stage[s].tap_off + k)] = re[s][k];
+            dev[2 * (rx.stage[s].tap_off + k) + 1] = im[s][k];
+        }
+    }
+    if (rx.d_ctaps.alloc(dev.size()) != OOKD_OK) return false;
+    if (hipMemcpy(rx.d_ctaps.p, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("tuned tap upload failed");
+        return false;
+    }
+    if (!rx.exact) {
+        rx.err_valu = tuned_guard_error(re, im, 16.0);
+        band_from_error(rx.err_valu, rx.p_star, rx.p_lo, rx.p_hi);
+        // (the shape front_uses_tuned_fir1 takes: the only tuned kernel with a quiet test)
+        if (rx.num_stages == 1 && rx.stage[0].decim == 1 && rx.stage[0].ntaps_pad <= 256u) setup_tuned_quiet(rx, re[0], im[0], cfg);
+    }
+    return true;
+}
+
 // The state machine's tables on the device
 bool setup_device_tables(ookd_rx &rx, const ookd_device &device) {
     const size_t ns = device.state_duration_us.size();
@@ -1841,7 +1935,23 @@ extern "C" {
 
 ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
                         const ookd_device *device) {
+    return ookd_rx_create_tuned(cfg, filter, device, nullptr);
+}
+
+double ookd_rx_tune(const ookd_rx *rx) { return rx ? rx->tune_nu : 0.0; }
+
+ookd_rx *ookd_rx_create_tuned(const ookd_rx_config *cfg, const ookd_filter *filter,
+                              const ookd_device *device, const ookd_tune *tune) {
     clear_error();
+    const double nu = tune ? tune->nu : 0.0;
+    if (!(std::fabs(nu) <= 0.5)) {
+        set_error("ookd_rx_create_tuned: nu must be within [-0.5, 0.5] cycles per sample");
+        return nullptr;
+    }
+    if (nu != 0.0 && !filter) {
+        set_error("ookd_rx_create_tuned: nu != 0 needs a filter: without one the slicer sees |x|, which does not depend on nu");
+        return nullptr;
+    }
     if (!cfg || cfg->samples_per_buffer == 0 || cfg->max_samples == 0) {
         set_error("ookd_rx_create: samples_per_buffer and max_samples must be non-zero");
         return nullptr;
@@ -1889,8 +1999,13 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
     if (filter && !setup_filter(*rx, *filter)) return nullptr;
     rx->p_star = power_threshold(cfg->threshold);
     rx->p_lo = rx->p_hi = rx->p_star;
-    if (filter && !rx->exact && !setup_front_form(*rx, *filter, cfg->flags)) return nullptr;
-    if (filter) setup_quiet_skip(*rx, *filter, *cfg);
+    rx->tune_nu = nu == 0.0 ? 0.0 : nu;
+    if (rx->tune_nu != 0.0) {
+        if (!setup_tuned(*rx, *filter, *cfg)) return nullptr;
+    } else {
+        if (filter && !rx->exact && !setup_front_form(*rx, *filter, cfg->flags)) return nullptr;
+        if (filter) setup_quiet_skip(*rx, *filter, *cfg);
+    }
     if (device && !setup_device_tables(*rx, *device)) return nullptr;
     if (!setup_run_buffers(*rx, *cfg)) return nullptr;
     if (rx->have_fsm && !setup_scan(*rx, *device, *cfg)) return nullptr;
