@@ -10,7 +10,7 @@
  *   gcc -std=c99 -Wall -Iinclude examples/ookd_rx.c -o ookd_rx \
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
- * ookd_rx [--threshold <value>|auto] [--tune <hz>] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none>
+ * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none>
  *         <samplerate> [csv|pretty] [dig.csv]
  *
  * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
@@ -22,6 +22,10 @@
  * its DC spike out of the way): the context filters with taps tuned to hz / samplerate cycles per sample
  * (ookd_rx_create_tuned).  Not together with `--threshold auto`: the survey filters with the real taps around
  * 0 Hz and would measure the DC term, not the carrier.
+ *
+ * --tune auto: one spectrum pass over the capture finds the carriers (ookd_spectrum_*, ookd_suggest_carriers);
+ * every one is reported on stderr and the context is tuned to the strongest that is not the peak at DC.  Without
+ * such a carrier a line says so and the decode is untuned.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -39,7 +43,7 @@ int main(int argc, char **argv)
 {
     /* --threshold <value>|auto is taken out of argv; what is left is positional, as before */
     float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
-    int threshold_auto = 0, bad_option = 0;
+    int threshold_auto = 0, tune_auto = 0, bad_option = 0;
     double tune_hz = 0.0;
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
@@ -53,6 +57,8 @@ int main(int argc, char **argv)
         } else if (!strcmp(argv[i], "--tune")) {
             char *end = NULL;
             if (++i >= argc) { bad_option = 1; break; }
+            if (!strcmp(argv[i], "auto")) { tune_auto = 1; tune_hz = 0.0; continue; }
+            tune_auto = 0;
             tune_hz = strtod(argv[i], &end);
             if (end == argv[i] || *end != '\0') { bad_option = 1; break; }
         } else {
@@ -61,14 +67,17 @@ int main(int argc, char **argv)
     }
     argc = kept;
     if (argc < 5 || bad_option) {
-        fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>] <capture.sc16q11|.cs8|.cu8> <device.json> "
+        fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> "
                         "<filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n", argv[0]);
         return EXIT_FAILURE;
     }
-    if (threshold_auto && tune_hz != 0.0) {
+    if (threshold_auto && (tune_auto || tune_hz != 0.0)) {
+        char where[48];
+        if (tune_auto) snprintf(where, sizeof where, "that --tune auto finds");
+        else snprintf(where, sizeof where, "at %g Hz", tune_hz);
         fprintf(stderr, "%s: --threshold auto cannot be combined with --tune: the survey filters with the real taps "
-                        "around 0 Hz and would measure the DC term, not the carrier at %g Hz; give a threshold\n",
-                argv[0], tune_hz);
+                        "around 0 Hz and would measure the DC term, not the carrier %s; give a threshold\n",
+                argv[0], where);
         return EXIT_FAILURE;
     }
     const int fmt = (argc > 5 && !strcmp(argv[5], "csv")) ? OOKD_RX_FMT_CSV : OOKD_RX_FMT_PRETTY;
@@ -89,6 +98,7 @@ int main(int argc, char **argv)
     ookd_formatter *formatter = NULL;
     ookd_rx *rx = NULL;
     ookd_survey *survey = NULL;
+    ookd_spectrum *spectrum = NULL;
     char *text = NULL;
 
     void *sdr = sdr_hip_file_init((const struct ookiedokie_cfg *)&cfg);   /* same layout: see ookd_host_cfg */
@@ -126,6 +136,33 @@ int main(int argc, char **argv)
                 sug.threshold, sug.off_level, sug.on_level, 100.0 * sug.on_fraction,
                 ookd_survey_kernel_ms(survey));
         cfg.rx_threshold = sug.threshold;
+    }
+
+    if (tune_auto) {                        /* the capture is in HBM already: one pass over it */
+        static ookd_spectrum_result sp;
+        ookd_carrier found[16];
+        uint32_t nfound = 0, chosen = 0;
+        double noise_floor = 0.0;
+        spectrum = ookd_spectrum_create(0, (uint32_t) sdr_hip_file_sample_flags(sdr), 1, NULL);
+        if (!spectrum) { fail("ookd_spectrum_create"); goto out; }
+        if (ookd_spectrum_device(spectrum, d_iq, 1, n, n) != 0) { fail("ookd_spectrum_device"); goto out; }
+        if (ookd_spectrum_get(spectrum, 0, &sp) != 0) { fail("ookd_spectrum_get"); goto out; }
+        if (ookd_suggest_carriers(&sp, 0.0, 0, found, 16, &nfound, &noise_floor) != 0) {
+            fail("ookd_suggest_carriers");
+            goto out;
+        }
+        for (uint32_t i = 0; i < nfound; ++i)
+            fprintf(stderr, "tune auto: carrier at %.6g Hz, %.4g x the floor%s\n", found[i].nu * (double) rate,
+                    found[i].ratio, found[i].at_dc ? ", at DC" : "");
+        while (chosen < nfound && found[chosen].at_dc) ++chosen;
+        if (chosen < nfound) {
+            tune_hz = found[chosen].nu * (double) rate;
+            fprintf(stderr, "tune auto: tuned to %.6g Hz (%llu frames, spectrum %.3f ms)\n", tune_hz,
+                    (unsigned long long) sp.frames, ookd_spectrum_kernel_ms(spectrum));
+        } else {
+            fprintf(stderr, "tune auto: no carrier beside DC in %llu frames (spectrum %.3f ms): decoding untuned\n",
+                    (unsigned long long) sp.frames, ookd_spectrum_kernel_ms(spectrum));
+        }
     }
 
     ookd_rx_config rc;
@@ -168,6 +205,7 @@ out:
     free(text);
     ookd_rx_destroy(rx);
     ookd_survey_destroy(survey);
+    ookd_spectrum_destroy(spectrum);
     ookd_formatter_free(formatter);
     ookd_device_free(device);
     ookd_filter_free(filter);

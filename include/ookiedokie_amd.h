@@ -609,6 +609,117 @@ typedef struct ookd_threshold_suggestion {
 int ookd_suggest_threshold(const ookd_level_hist *h, ookd_threshold_suggestion *out);
 
 /* ------------------------------------------------------------------------
+ * Carrier survey: which ookd_tune.nu does this capture want?  One pass over
+ * captures resident in HBM sums a Welch power spectrum per capture;
+ * ookd_suggest_carriers (host only) turns a spectrum into a list of carriers.
+ * A separate object beside the rx context and the envelope survey: nothing an
+ * ookd_rx or an ookd_survey does changes.
+ *
+ * The spectrum, a contract:
+ *   - frame f of a capture is samples [1024 f, 1024 f + 1024); only whole
+ *     frames count, nothing is padded (as in the envelope survey);
+ *   - samples are unpacked as the reference unpacks them, v / 2048
+ *     (complexf.h:68-77; an 8-bit sample is 16 v first);
+ *   - the window is the periodic Hann w[n] = 0.5 - 0.5 cos(2 pi n / 1024);
+ *   - X_f[k] = sum_n w[n] x[1024 f + n] e^{-j 2 pi k n / 1024};
+ *   - power[k] = sum_f |X_f[k]|^2, k = 0 .. 1023 in FFT order;
+ *   - bin k is the carrier at ookd_spectrum_bin_nu(k) cycles per input sample,
+ *     the sign convention of ookd_tune.nu: a capture moved to +600 kHz at
+ *     3 MHz peaks at bin 205.
+ * Arithmetic is fp32 inside a frame and double across frames, so the contract
+ * is an error bound, not bit equality.  With S[k] the value in exact (float64)
+ * arithmetic and E = sum_k S[k]:
+ *     |power[k] - S[k]| <= 2 EPS sqrt(S[k] E) + EPS^2 E + EPS S[k],
+ *     EPS = OOKD_SPECTRUM_EPS = 12 log2(1024) 2^-24.
+ * Derivation.  Higham's normwise bound for an FFT is
+ * ||X^ - X||_2 <= log2(N) eta ||X||_2; with twiddles rounded from double
+ * eta ~ 8 u (u = 2^-24), and another 4 u per level, taken as log2(N) 4 u,
+ * covers the rounding of the window product: the factor 12.  A single bin's
+ * error is bounded by the norm, |X^_f[k] - X_f[k]| <= EPS ||X_f||_2, so
+ * | |X^_f[k]|^2 - |X_f[k]|^2 | <= 2 EPS |X_f[k]| ||X_f|| + EPS^2 ||X_f||^2, and
+ * Cauchy-Schwarz over the frames gives the first two terms.  The third is the
+ * budget for re^2 + im^2 and for adding per-frame powers in fp32 before they
+ * are folded into a double: 120 u allows a lane to sum at most 32 frames in
+ * fp32 between folds.
+ * Results are reproducible: two runs of one context over the same capture give
+ * bitwise identical power[] (no floating-point atomics: every workgroup writes
+ * its partial sums and a second kernel adds them in a fixed order).
+ * ---------------------------------------------------------------------- */
+#define OOKD_SPECTRUM_BINS 1024
+#define OOKD_SPECTRUM_EPS (12.0 * 10.0 / 16777216.0)   /* 12 * log2(1024) * 2^-24 */
+typedef struct ookd_spectrum_result {
+    uint64_t frames;                       /* floor(n / 1024) whole frames summed */
+    double power[OOKD_SPECTRUM_BINS];      /* sum over frames of |X_f[k]|^2, FFT order */
+} ookd_spectrum_result;
+
+typedef struct ookd_spectrum ookd_spectrum;
+
+/* sample_flags: 0 (SC16Q11), OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8 (read in
+ * place, 2 bytes per sample); both, or any other bit, fails.  stream:
+ * hipStream_t to launch on, NULL = own. */
+ookd_spectrum *ookd_spectrum_create(int32_t hip_device, uint32_t sample_flags,
+                                    uint32_t max_captures, void *stream);
+void ookd_spectrum_destroy(ookd_spectrum *s);
+/* Captures are addressed as ookd_rx_process_device addresses them: capture c at
+ * sample c * capture_stride_samples of d_iq.  Blocks until the spectra are in
+ * host memory; they replace those of the run before.  Fewer than 1024 samples
+ * (0 included) is a valid run with frames = 0 and all-zero power.  Captures
+ * that start on 16-byte boundaries are read with vector loads, others sample
+ * by sample. */
+int ookd_spectrum_device(ookd_spectrum *s, const void *d_iq, uint32_t num_captures,
+                         uint64_t samples_per_capture, uint64_t capture_stride_samples);
+/* Same over one host capture: staged to HBM first (PCIe-bound), in a buffer
+ * the context keeps and grows to the largest capture it has seen. */
+int ookd_spectrum_host(ookd_spectrum *s, const void *iq, uint64_t num_samples);
+int ookd_spectrum_get(const ookd_spectrum *s, uint32_t capture, ookd_spectrum_result *out);
+/* HIP-event time of the last run's two kernels (0 before any run). */
+float ookd_spectrum_kernel_ms(const ookd_spectrum *s);
+/* k / 1024 for k < 512, (k - 1024) / 1024 otherwise (k taken mod 1024); host only. */
+double ookd_spectrum_bin_nu(uint32_t bin);
+
+/* Suggested carriers, pure host code (no GPU needed).  The rule, a contract:
+ *   1. floor = the median of the 1024 powers: the mean of the 512th and 513th
+ *      smallest.
+ *   2. frames == 0: no carriers.
+ *   3. All bins start live.
+ *   4. Repeat: take the live bin of largest power, ties going to the lowest k.
+ *      Stop when that power is not > 0, is < min_ratio * floor, or `capacity`
+ *      carriers have been emitted.  Otherwise emit it and kill every bin within
+ *      circular distance <= min_spacing_bins of it (1023 and 0 are neighbours).
+ *   5. Output is in decreasing power.  nu is the bin centre, not interpolated:
+ *      decoding the golden captures at one bin either side of the true offset
+ *      gives the same messages, 1/1024 is far inside the filters' pass band.
+ *   6. at_dc (|bin| <= 1) is only a flag: the receiver's own DC term, or a
+ *      carrier at 0 Hz.  The caller decides what to do with that peak.
+ * OOKD_CARRIER_MIN_RATIO, 64: a bin of one frame of white noise is
+ * exponentially distributed, P(S > r median) = 2^-r, so 64 leaves 1024 * 2^-64
+ * false peaks per frame; more frames only thin the tail (worst max / median of
+ * noise alone over 50 trials: 15.6 with one frame, 5.0 with four, 1.5 with 100).
+ * OOKD_CARRIER_MIN_SPACING, 32 bins = 1/32 cycle per sample: the pass band of
+ * fs32_fs4 and of the backend's default filter.  Two carriers closer than that
+ * cannot be separated by those filters anyway, and the sidebands of the on-off
+ * keying fall inside it and are not reported as carriers.
+ * Limits: with floor == 0 (a noiseless synthetic capture) rounding residue can
+ * qualify as a peak (its ratio is infinite), and a carrier within 32 bins of a
+ * stronger DC term is hidden by it. */
+typedef struct ookd_carrier {
+    double nu;          /* bin centre, cycles per input sample: pass to ookd_tune.nu */
+    int32_t bin;        /* -512 .. 511 */
+    uint32_t at_dc;     /* |bin| <= 1: the receiver's own DC term, or a carrier at 0 Hz */
+    double power;       /* power[k] */
+    double ratio;       /* power / floor */
+} ookd_carrier;
+#define OOKD_CARRIER_MIN_RATIO 64.0
+#define OOKD_CARRIER_MIN_SPACING 32
+/* 0, or OOKD_ERR_ARG for NULL sp or count, NULL out with capacity > 0, or a
+ * negative or NaN min_ratio.  min_ratio 0 / min_spacing_bins 0 = the defaults
+ * above.  *count receives the number of carriers written to out[]; floor may
+ * be NULL. */
+int ookd_suggest_carriers(const ookd_spectrum_result *sp, double min_ratio /* 0 = default */,
+                          uint32_t min_spacing_bins /* 0 = default */,
+                          ookd_carrier *out, uint32_t capacity, uint32_t *count, double *floor);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

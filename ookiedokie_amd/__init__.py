@@ -16,6 +16,8 @@ here                              reference (OOKiedokie ``src/``)
                                   (sdr/supported_devices.h:32-48)
 ``Survey`` / ``suggest_threshold`` nothing: picks ``--rx-threshold``
                                   (ookiedokie_cfg.c:27) from the capture
+``Spectrum`` / ``suggest_carriers`` nothing: finds the carriers' offsets
+                                  (``Receiver(tune=...)``) in the capture
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -68,6 +70,10 @@ FRONT_TUNED_FIR1 = 13                   # ... 1 stage, decimation 1, <= 256 taps
 LEVEL_BINS = 256                        # OOKD_LEVEL_BINS: envelope survey, four bins per octave of power
 LEVEL_MIN_SEPARATION = 18               # OOKD_LEVEL_MIN_SEPARATION
 LEVEL_MIN_SIDE = 512                    # OOKD_LEVEL_MIN_SIDE
+SPECTRUM_BINS = 1024                    # OOKD_SPECTRUM_BINS: carrier survey, 1024-sample Hann frames
+SPECTRUM_EPS = 12.0 * 10.0 / 16777216.0 # OOKD_SPECTRUM_EPS: the error bound's constant, 12 log2(1024) 2^-24
+CARRIER_MIN_RATIO = 64.0                # OOKD_CARRIER_MIN_RATIO
+CARRIER_MIN_SPACING = 32                # OOKD_CARRIER_MIN_SPACING
 DEFAULT_THRESHOLD = 0.1                 # ookiedokie_cfg.c:27
 DEFAULT_RATE = 3000000                  # ookiedokie_cfg.c:32
 DEFAULT_SAMPLES_PER_BUF = 8192          # ookiedokie_cfg.c:34
@@ -168,6 +174,15 @@ class ThresholdSuggestion(C.Structure):
     _fields_ = [("found", C.c_int), ("threshold", C.c_float), ("off_level", C.c_float), ("on_level", C.c_float),
                 ("split_bin", C.c_uint32), ("off_bin", C.c_uint32), ("on_bin", C.c_uint32),
                 ("on_fraction", C.c_double)]
+
+
+class SpectrumResult(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("power", C.c_double * SPECTRUM_BINS)]
+
+
+class CarrierStruct(C.Structure):
+    _fields_ = [("nu", C.c_double), ("bin", C.c_int32), ("at_dc", C.c_uint32), ("power", C.c_double),
+                ("ratio", C.c_double)]
 
 
 class HostCfg(C.Structure):
@@ -272,6 +287,16 @@ _PROTOTYPES = {
     "ookd_level_bin": (C.c_uint32, [C.c_float]),
     "ookd_level_bin_lower": (C.c_float, [C.c_uint32]),
     "ookd_suggest_threshold": (C.c_int, [C.POINTER(LevelHist), C.POINTER(ThresholdSuggestion)]),
+    "ookd_spectrum_create": (C.c_void_p, [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "ookd_spectrum_destroy": (None, [C.c_void_p]),
+    "ookd_spectrum_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "ookd_spectrum_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "ookd_spectrum_get": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SpectrumResult)]),
+    "ookd_spectrum_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_spectrum_bin_nu": (C.c_double, [C.c_uint32]),
+    "ookd_suggest_carriers": (C.c_int, [C.POINTER(SpectrumResult), C.c_double, C.c_uint32,
+                                        C.POINTER(CarrierStruct), C.c_uint32, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_double)]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
     "sdr_hip_file_deinit": (None, [C.c_void_p]),
     "sdr_hip_file_rx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
@@ -914,6 +939,97 @@ class Survey:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_survey_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# --------------------------------------------------------------------------
+# carrier survey
+# --------------------------------------------------------------------------
+
+def spectrum_bin_nu(bin: int) -> float:
+    """The carrier offset of a spectrum bin in cycles per input sample (ookd_spectrum_bin_nu)."""
+    return float(lib().ookd_spectrum_bin_nu(int(bin) % SPECTRUM_BINS))
+
+
+@dataclass
+class Carrier:
+    nu: float           # bin centre, cycles per input sample: Receiver(tune=nu)
+    bin: int            # -512 .. 511
+    at_dc: bool         # |bin| <= 1
+    power: float
+    ratio: float        # power / floor
+
+
+def suggest_carriers(power_or_result, min_ratio: float = 0.0, min_spacing_bins: int = 0,
+                     max_carriers: int = 16, frames: Optional[int] = None) -> Tuple[List[Carrier], float]:
+    """ookd_suggest_carriers over 1024 powers, or over the (frames, power) pair `Spectrum.result` returns:
+    (carriers in decreasing power, floor).  The rule is stated in the header.  Pure host code.  A bare power
+    array counts as one frame unless `frames` says otherwise."""
+    if isinstance(power_or_result, tuple):
+        if frames is None:
+            frames = int(power_or_result[0])
+        power_or_result = power_or_result[1]
+    pw = np.ascontiguousarray(power_or_result, dtype=np.float64).reshape(-1)
+    if pw.size != SPECTRUM_BINS:
+        raise ValueError("a spectrum has %d bins, not %d" % (SPECTRUM_BINS, pw.size))
+    sp = SpectrumResult()
+    sp.frames = 1 if frames is None else int(frames)
+    C.memmove(sp.power, pw.ctypes.data, pw.nbytes)
+    out = (CarrierStruct * max(1, max_carriers))()
+    count, floor = C.c_uint32(0), C.c_double(0.0)
+    _check(lib().ookd_suggest_carriers(C.byref(sp), float(min_ratio), int(min_spacing_bins), out,
+                                       int(max_carriers), C.byref(count), C.byref(floor)))
+    return ([Carrier(c.nu, c.bin, bool(c.at_dc), c.power, c.ratio) for c in out[:count.value]], floor.value)
+
+
+class Spectrum:
+    """Welch power spectrum of whole captures in HBM (ookd_spectrum_*): 1024-sample periodic-Hann frames summed
+    per bin, the input of `suggest_carriers`."""
+
+    def __init__(self, *, sample_format: str = "sc16q11", max_captures: int = 1, hip_device: int = 0,
+                 stream: int = 0):
+        if sample_format not in SAMPLE_FORMATS:
+            raise ValueError("sample_format must be one of %s" % ", ".join(sorted(SAMPLE_FORMATS)))
+        self.sample_format = sample_format
+        fmt_flag, self._sample_dtype = SAMPLE_FORMATS[sample_format]
+        self._h = lib().ookd_spectrum_create(hip_device, fmt_flag, max_captures, stream)
+        if not self._h:
+            raise OokdError(-4, last_error())
+
+    def spectrum_device(self, d_iq_ptr: int, samples_per_capture: int, num_captures: int = 1,
+                        stride: Optional[int] = None) -> None:
+        """Captures already resident in HBM (I,Q interleaved, in the context's sample format)."""
+        _check(lib().ookd_spectrum_device(self._h, d_iq_ptr, num_captures, samples_per_capture,
+                                          stride if stride is not None else samples_per_capture))
+
+    def spectrum(self, iq: np.ndarray) -> Tuple[int, np.ndarray]:
+        """One host capture (staged over PCIe first), same arrays as `Receiver.rx` takes; returns its result."""
+        if self.sample_format != "sc16q11" and np.asarray(iq).dtype != self._sample_dtype:
+            raise TypeError("this Spectrum takes %s samples as %s, not %s"
+                            % (self.sample_format, np.dtype(self._sample_dtype).name, np.asarray(iq).dtype.name))
+        iq = np.ascontiguousarray(iq, dtype=self._sample_dtype).reshape(-1)
+        _check(lib().ookd_spectrum_host(self._h, iq.ctypes.data, iq.size // 2))
+        return self.result(0)
+
+    def result(self, capture: int = 0) -> Tuple[int, np.ndarray]:
+        """(whole frames summed, power[1024] float64 in FFT order) of one capture of the last run."""
+        r = SpectrumResult()
+        _check(lib().ookd_spectrum_get(self._h, capture, C.byref(r)))
+        return int(r.frames), np.frombuffer(bytes(r.power), dtype=np.float64).copy()
+
+    @property
+    def kernel_ms(self) -> float:
+        return float(lib().ookd_spectrum_kernel_ms(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().ookd_spectrum_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -516,6 +516,32 @@ struct SurveyParams {
 uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes);
 hipError_t launch_survey(const SurveyParams &p, uint32_t num_captures, size_t lds_bytes, hipStream_t stream);
 
+// ---- carrier survey (spectrum.hip) ----------------------------------------------
+// Welch power spectrum of every capture: whole 1024-sample periodic-Hann frames, fp32 inside a frame, double
+// across frames, no padding; the contract is in the header at ookd_spectrum_*.
+constexpr int kSpecBins = 1024;         // OOKD_SPECTRUM_BINS: frame length = bins
+constexpr int kSpecThreads = 256;
+constexpr int kSpecWaves = kSpecThreads / 64;   // one frame per wave at a time
+constexpr int kSpecFold = 32;           // frames a lane sums in fp32 before it folds them into doubles
+constexpr int kSpecGroupsPerCu = 3;     // 46 KiB of LDS per workgroup
+
+struct SpectrumParams {
+    const void *iq;             // captures in `sample_fmt`
+    uint32_t sample_fmt;        // kFmt*
+    uint32_t aligned;           // every capture starts on a 16-byte boundary: vector loads
+    uint64_t cap_stride;        // samples between consecutive captures
+    uint64_t frames;            // whole frames per capture: floor(n / 1024)
+    const float2 *twiddle;      // [1024], rounded from double, in the lanes' read order: step A's
+                                // W1024^((4 L + i) kj) at (kj - 1) * 256 + i * 64 + L (kj = 1..3), then step B's
+                                // W256^(s kt) at 768 + 16 kt + s (W = e^{-j 2 pi / .})
+    const float *window;        // [1024] periodic Hann, rounded from double
+    double *partial;            // [captures][groups][1024], every element written by the run
+    double *power;              // [captures][1024]
+};
+// workgroups per capture for a run (0 when there is nothing to do): fills the device once
+uint32_t spectrum_groups(uint64_t frames, uint32_t num_captures, int cus);
+hipError_t launch_spectrum(const SpectrumParams &p, uint32_t num_captures, uint32_t groups, hipStream_t stream);
+
 // ---- synthetic generator ------------------------------------------------------
 
 struct SynthRun {               // one constant-envelope run of the capture
