@@ -1,0 +1,183 @@
+/*
+ * ookd_scan.c -- a C99 host on top of libookiedokie_amd.so that uses the whole chain on one capture whose
+ * carriers are NOT at its centre:
+ *     spectrum (ookd_spectrum_*, ookd_suggest_carriers)        which carriers are there
+ *  -> per carrier a tuned envelope survey (ookd_survey_create_tuned, ookd_suggest_threshold)
+ *                                                              which threshold does this carrier want
+ *  -> per carrier and device a tuned context (ookd_rx_create_tuned) at that threshold
+ *  -> formatter / rx_print text on stdout.
+ * The capture is loaded once and stays in HBM; every pass reads it there.
+ *
+ * Build:
+ *   gcc -std=c99 -Wall -Werror -Iinclude examples/ookd_scan.c -o ookd_scan \
+ *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
+ *
+ * ookd_scan <capture.sc16q11|.cs8|.cu8> <samplerate> <filter.json> <device.json> [<device.json> ...] [csv|pretty]
+ *
+ * stderr: one line per carrier -- the peak at DC (the receiver's own) is reported and skipped, every other one
+ * with its threshold and the two envelope levels, or "no two envelope levels" --, and one line per carrier and
+ * device that decoded messages.  stdout: those messages, block by block as ookd_rx prints them (a CSV block
+ * starts with its device's heading).  Without a carrier beside DC a
+ * line says so, stdout stays empty and the exit status is 0.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "ookiedokie_amd.h"
+
+#define MAX_CARRIERS 8
+#define MAX_DEVICES 16
+
+static int fail(const char *what)
+{
+    fprintf(stderr, "%s: %s\n", what, ookd_last_error());
+    return EXIT_FAILURE;
+}
+
+int main(int argc, char **argv)
+{
+    int fmt = OOKD_RX_FMT_PRETTY;
+    if (argc > 1 && (!strcmp(argv[argc - 1], "csv") || !strcmp(argv[argc - 1], "pretty"))) {
+        fmt = !strcmp(argv[argc - 1], "csv") ? OOKD_RX_FMT_CSV : OOKD_RX_FMT_PRETTY;
+        --argc;
+    }
+    const unsigned rate = argc > 2 ? (unsigned) strtoul(argv[2], NULL, 0) : 0;
+    const int ndev = argc - 4;
+    if (argc < 5 || ndev > MAX_DEVICES || rate == 0) {
+        fprintf(stderr, "usage: %s <capture.sc16q11|.cs8|.cu8> <samplerate> <filter.json> <device.json> "
+                        "[<device.json> ... up to %d] [csv|pretty]\n", argv[0], MAX_DEVICES);
+        return EXIT_FAILURE;
+    }
+    int status = EXIT_FAILURE;
+
+    ookd_host_cfg cfg;                      /* struct ookiedokie_cfg, field for field */
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.sdr_type = "hip_file";
+    cfg.direction = 0;
+    cfg.sdr_args = argv[1];
+    cfg.samplerate = rate;
+    cfg.rx_threshold = 0.1f;
+    cfg.samples_per_buffer = 8192;
+
+    ookd_filter *filter = NULL;
+    ookd_device *device[MAX_DEVICES] = { NULL };
+    ookd_formatter *formatter[MAX_DEVICES] = { NULL };
+    ookd_spectrum *spectrum = NULL;
+    ookd_survey *survey = NULL;
+    ookd_rx *rx = NULL;
+    char *text = NULL;
+
+    void *sdr = sdr_hip_file_init((const struct ookiedokie_cfg *)&cfg);   /* same layout: see ookd_host_cfg */
+    if (!sdr) return fail("sdr_hip_file_init");
+    const uint32_t sample_flags = (uint32_t) sdr_hip_file_sample_flags(sdr);
+
+    const void *d_iq = NULL;
+    uint64_t n = 0;
+    if (sdr_hip_file_capture(sdr, &d_iq, &n) != 0) { fail("sdr_hip_file_capture"); goto out; }
+
+    filter = ookd_filter_load(argv[3]);
+    if (!filter) { fail("ookd_filter_load"); goto out; }
+    const unsigned decimation = ookd_filter_total_decimation(filter);
+    for (int d = 0; d < ndev; ++d) {
+        device[d] = ookd_device_load(argv[4 + d], rate / decimation);   /* main.c:683 */
+        if (!device[d]) { fail("ookd_device_load"); goto out; }
+        formatter[d] = ookd_formatter_create(device[d]);
+        if (!formatter[d]) { fail("ookd_formatter_create"); goto out; }
+    }
+
+    /* 1. which carriers */
+    static ookd_spectrum_result sp;
+    ookd_carrier found[MAX_CARRIERS];
+    uint32_t nfound = 0, beside = 0;
+    spectrum = ookd_spectrum_create(0, sample_flags, 1, NULL);
+    if (!spectrum) { fail("ookd_spectrum_create"); goto out; }
+    if (ookd_spectrum_device(spectrum, d_iq, 1, n, n) != 0) { fail("ookd_spectrum_device"); goto out; }
+    if (ookd_spectrum_get(spectrum, 0, &sp) != 0) { fail("ookd_spectrum_get"); goto out; }
+    if (ookd_suggest_carriers(&sp, 0.0, 0, found, MAX_CARRIERS, &nfound, NULL) != 0) {
+        fail("ookd_suggest_carriers");
+        goto out;
+    }
+    for (uint32_t c = 0; c < nfound; ++c) {
+        if (found[c].at_dc)
+            fprintf(stderr, "carrier %+.6g Hz: at DC, skipped\n", found[c].nu * (double) rate);
+        else
+            ++beside;
+    }
+    if (!beside) {
+        fprintf(stderr, "no carrier beside DC in %llu frames: nothing decoded\n", (unsigned long long) sp.frames);
+        status = EXIT_SUCCESS;
+        goto out;
+    }
+
+    for (uint32_t c = 0; c < nfound; ++c) {
+        if (found[c].at_dc) continue;
+        const double hz = found[c].nu * (double) rate;
+        ookd_tune tune;
+        memset(&tune, 0, sizeof(tune));
+        tune.nu = found[c].nu;
+
+        /* 2. which threshold: the envelope this carrier has behind the filter tuned to it */
+        ookd_level_hist hist;
+        ookd_threshold_suggestion sug;
+        survey = ookd_survey_create_tuned(0, filter, sample_flags, 1, NULL, &tune);
+        if (!survey) { fail("ookd_survey_create_tuned"); goto out; }
+        if (ookd_survey_device(survey, d_iq, 1, n, n) != 0) { fail("ookd_survey_device"); goto out; }
+        if (ookd_survey_get_hist(survey, 0, &hist) != 0) { fail("ookd_survey_get_hist"); goto out; }
+        if (ookd_suggest_threshold(&hist, &sug) != 0) { fail("ookd_suggest_threshold"); goto out; }
+        ookd_survey_destroy(survey);
+        survey = NULL;
+        if (!sug.found) {
+            fprintf(stderr, "carrier %+.6g Hz: no two envelope levels\n", hz);
+            continue;
+        }
+        fprintf(stderr, "carrier %+.6g Hz: threshold %.6g (off %.6g, on %.6g)\n", hz, sug.threshold, sug.off_level,
+                sug.on_level);
+
+        /* 3. decode, once per device */
+        for (int d = 0; d < ndev; ++d) {
+            ookd_rx_config rc;
+            memset(&rc, 0, sizeof(rc));
+            rc.threshold = sug.threshold;
+            rc.samples_per_buffer = cfg.samples_per_buffer;
+            rc.max_samples = n ? n : 1;
+            rc.flags = sample_flags;
+            rx = ookd_rx_create_tuned(&rc, filter, device[d], &tune);
+            if (!rx) { fail("ookd_rx_create_tuned"); goto out; }
+            if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }
+            const uint64_t nmsg = ookd_rx_num_messages(rx);
+            if (nmsg) {
+                const ookd_message *msgs = ookd_rx_messages(rx);
+                int fp = 1;                 /* every block has its device's own CSV heading, as ookd_rx prints it */
+                const size_t len = ookd_print_messages(formatter[d], fmt, &fp, msgs, nmsg, cfg.samples_per_buffer,
+                                                       decimation, NULL, 0);
+                text = malloc(len + 1);
+                if (!text) goto out;
+                fp = 1;
+                ookd_print_messages(formatter[d], fmt, &fp, msgs, nmsg, cfg.samples_per_buffer, decimation,
+                                    text, len + 1);
+                fprintf(stderr, "carrier %+.6g Hz, %s: %llu messages\n", hz, ookd_device_name(device[d]),
+                        (unsigned long long) nmsg);
+                fputs(text, stdout);
+                free(text);
+                text = NULL;
+            }
+            ookd_rx_destroy(rx);
+            rx = NULL;
+        }
+    }
+    status = EXIT_SUCCESS;
+
+out:
+    free(text);
+    ookd_rx_destroy(rx);
+    ookd_survey_destroy(survey);
+    ookd_spectrum_destroy(spectrum);
+    for (int d = 0; d < MAX_DEVICES; ++d) {
+        ookd_formatter_free(formatter[d]);
+        ookd_device_free(device[d]);
+    }
+    ookd_filter_free(filter);
+    sdr_hip_file_deinit(sdr);
+    return status;
+}

@@ -381,8 +381,8 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
  * nothing.  Fails for NaN or |nu| > 0.5, and for nu != 0 without a filter:
  * |x| of the unfiltered samples does not depend on nu, there is nothing to tune.
  * Not tuned (yet): the matrix-core forms, the folded decimate-by-4 kernel (a
- * tuned fs128_fs16_dec4 runs OOKD_FRONT_TUNED_GENERIC), ookd_survey_*,
- * ookd_fir_*. */
+ * tuned fs128_fs16_dec4 runs OOKD_FRONT_TUNED_GENERIC), ookd_fir_*.  (The
+ * envelope survey has its own tuned entry point: ookd_survey_create_tuned.) */
 typedef struct ookd_tune {
     double nu;                      /* cycles per input sample, |nu| <= 0.5     */
     uint64_t reserved[3];           /* zero                                     */
@@ -552,6 +552,56 @@ int ookd_survey_host(ookd_survey *s, const void *iq, uint64_t num_samples);
 int ookd_survey_get_hist(const ookd_survey *s, uint32_t capture, ookd_level_hist *out);
 /* HIP-event time of the last run's histogram kernel (0 before any run). */
 float ookd_survey_kernel_ms(const ookd_survey *s);
+
+/* Tuned survey: the threshold for a carrier that is NOT at 0 Hz.  The survey
+ * above filters with the real taps around 0 Hz; on a capture whose carrier sits
+ * beside the centre it measures the receiver's DC term.  A tuned survey counts
+ * what a context made by ookd_rx_create_tuned with the same nu slices.
+ *
+ * The contract: the histogram is the one defined above with the filter output
+ * replaced by the tuned contract's (at ookd_filter_tuned_taps):
+ *   - the taps of stage s are ookd_filter_tuned_taps(f, nu, s, re, im);
+ *   - each stage output is the four unfused float32 statements per tap, in the
+ *     order stated there, tap 0 on the newest sample, accumulators from +0;
+ *     stages chain and decimate from zero history;
+ *   - p = ar*ar + ai*ai: two products and a sum, each rounded;
+ *   - the bin rule is unchanged;
+ *   - per capture the first floor(n / D) outputs are counted; nothing is padded
+ *     and no input at or beyond n is read.
+ * It stays an exact integer function of the capture: no guard band, no fused
+ * multiply-add, no matrix cores (an output one ulp off falls into the
+ * neighbouring bin).  x - y is x + (-y) bit for bit, so an implementation may
+ * hold -im; what matters is the order of the roundings per component: ar gets
+ * re*xr first and im*xi second, ai gets re*xi first and im*xr second.
+ *
+ * flags: the sample-format bits as ookd_survey_create takes them, plus
+ * OOKD_RX_EXACT_FIR; any other bit fails.  tune == NULL or nu == 0 IS
+ * ookd_survey_create: same kernel, form OOKD_SURVEY_GENERIC, OOKD_RX_EXACT_FIR
+ * accepted and ignored.  Otherwise a run takes one of two forms with the same
+ * histogram: OOKD_SURVEY_TUNED_FIR1 for 1 stage, decimation 1 and <= 256 taps,
+ * OOKD_SURVEY_TUNED_GENERIC for every other shape -- and for every shape with
+ * OOKD_RX_EXACT_FIR, which exists so that the two can be run against each other
+ * (as the flag does on a tuned rx context).  Fails for NaN, |nu| > 0.5,
+ * non-zero ookd_tune.reserved, and nu != 0 without a filter; the argument
+ * checks come before any HIP call.
+ * 8-bit captures are read in place by all forms (nothing is widened first).
+ * Alignment: OOKD_SURVEY_TUNED_FIR1 reads a capture whose first sample lies on
+ * a 16-byte boundary with 16-byte loads; any other capture of a batch (an odd
+ * stride, an 8-bit capture at an odd sample) is read sample by sample BY THE
+ * SAME KERNEL: the form stays OOKD_SURVEY_TUNED_FIR1 and the histogram is the
+ * same.
+ * ookd_survey_destroy / _device / _host / _get_hist / _kernel_ms and
+ * ookd_suggest_threshold serve both kinds of survey. */
+enum {
+    OOKD_SURVEY_GENERIC = 1,        /* survey_kernel: what ookd_survey_create runs       */
+    OOKD_SURVEY_TUNED_GENERIC = 2,  /* any shape, the tuned contract's order throughout  */
+    OOKD_SURVEY_TUNED_FIR1 = 3      /* 1 stage, decimation 1, <= 256 taps: register-blocked */
+};
+ookd_survey *ookd_survey_create_tuned(int32_t hip_device, const ookd_filter *filter,
+                                      uint32_t flags, uint32_t max_captures,
+                                      void *stream, const ookd_tune *tune);
+double ookd_survey_tune(const ookd_survey *s);     /* 0 for an untuned one, 0 for NULL */
+uint32_t ookd_survey_form(const ookd_survey *s);   /* the form a run takes / took; 0 for NULL */
 
 /* The bin rule above and its inverse, pure host code (no GPU needed).
  * ookd_level_bin_lower: the power at which bin `bin` starts (0 for bin 0;

@@ -67,6 +67,9 @@ FRONT_FIR1_MFMA_8 = 10
 FRONT_FIR2_MFMA_8 = 11
 FRONT_TUNED_GENERIC = 12                # a tuned context (Receiver(tune=...)): any shape, the contract's order
 FRONT_TUNED_FIR1 = 13                   # ... 1 stage, decimation 1, <= 256 taps: packed FMAs + guard band
+SURVEY_GENERIC = 1                      # survey forms (Survey.form): OOKD_SURVEY_*; what an untuned Survey runs
+SURVEY_TUNED_GENERIC = 2                # a tuned Survey (Survey(tune=...)): any shape, the contract's order
+SURVEY_TUNED_FIR1 = 3                   # ... 1 stage, decimation 1, <= 256 taps: register-blocked, same histogram
 LEVEL_BINS = 256                        # OOKD_LEVEL_BINS: envelope survey, four bins per octave of power
 LEVEL_MIN_SEPARATION = 18               # OOKD_LEVEL_MIN_SEPARATION
 LEVEL_MIN_SIDE = 512                    # OOKD_LEVEL_MIN_SIDE
@@ -279,6 +282,10 @@ _PROTOTYPES = {
     "ookd_rx_gate_create": (C.c_void_p, []),
     "ookd_rx_gate_destroy": (None, [C.c_void_p]),
     "ookd_survey_create": (C.c_void_p, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "ookd_survey_create_tuned": (C.c_void_p, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.POINTER(Tune)]),
+    "ookd_survey_tune": (C.c_double, [C.c_void_p]),
+    "ookd_survey_form": (C.c_uint32, [C.c_void_p]),
     "ookd_survey_destroy": (None, [C.c_void_p]),
     "ookd_survey_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "ookd_survey_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -896,19 +903,51 @@ def suggest_threshold(hist) -> dict:
 
 class Survey:
     """Histogram of the post-filter power of whole captures in HBM (ookd_survey_*): what `Receiver`'s slicer
-    will compare against `threshold`, counted before a threshold is chosen."""
+    will compare against `threshold`, counted before a threshold is chosen.
+
+    tune / tune_hz with sample_rate: as `Receiver` takes them -- the survey of a carrier beside the capture's
+    centre, counted through the taps `Filter.tuned_taps` returns (ookd_survey_create_tuned).  exact=True runs the
+    tuned survey's generic form for every shape (same histogram; for cross-checks)."""
 
     def __init__(self, filt: Optional[Filter], *, hip_device: int = 0, max_captures: int = 1, stream: int = 0,
-                 sample_format: str = "sc16q11"):
+                 sample_format: str = "sc16q11", tune: Optional[float] = None, tune_hz: Optional[float] = None,
+                 sample_rate: Optional[float] = None, exact: bool = False):
+        if tune is not None and (tune_hz is not None or sample_rate is not None):
+            raise ValueError("give either tune (cycles per sample) or tune_hz with sample_rate, not both")
+        if (tune_hz is None) != (sample_rate is None):
+            raise ValueError("tune_hz and sample_rate go together")
+        if tune_hz is not None:
+            if not sample_rate > 0:
+                raise ValueError("sample_rate must be positive")
+            tune = float(tune_hz) / float(sample_rate)
         if sample_format not in SAMPLE_FORMATS:
             raise ValueError("sample_format must be one of %s" % ", ".join(sorted(SAMPLE_FORMATS)))
         self.sample_format = sample_format
         fmt_flag, self._sample_dtype = SAMPLE_FORMATS[sample_format]
         self._filter = filt
         self.total_decimation = filt.total_decimation if filt else 1
-        self._h = lib().ookd_survey_create(hip_device, filt._h if filt else None, fmt_flag, max_captures, stream)
+        if tune is None and not exact:
+            self._h = lib().ookd_survey_create(hip_device, filt._h if filt else None, fmt_flag, max_captures, stream)
+        else:
+            t = None                                            # exact alone: tune = NULL, the untuned survey
+            if tune is not None:
+                t = Tune()
+                t.nu = float(tune)
+            self._h = lib().ookd_survey_create_tuned(hip_device, filt._h if filt else None,
+                                                     fmt_flag | (RX_EXACT_FIR if exact else 0), max_captures, stream,
+                                                     C.byref(t) if t is not None else None)
         if not self._h:
             raise OokdError(-4, last_error())
+
+    @property
+    def tune(self) -> float:
+        """Carrier offset this survey is tuned to, cycles per input sample (0: untuned)."""
+        return float(lib().ookd_survey_tune(self._h))
+
+    @property
+    def form(self) -> int:
+        """The kernel form a run takes: SURVEY_GENERIC, SURVEY_TUNED_GENERIC or SURVEY_TUNED_FIR1."""
+        return int(lib().ookd_survey_form(self._h))
 
     def survey_device(self, d_iq_ptr: int, samples_per_capture: int, num_captures: int = 1,
                       stride: Optional[int] = None) -> None:

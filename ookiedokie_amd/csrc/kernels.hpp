@@ -512,9 +512,28 @@ struct SurveyParams {
     unsigned long long *hist;   // [captures][kLevelBins], zero at launch
 };
 // Largest power-of-two tile (<= 1024 outputs) whose level buffers fit the LDS budget, 0 = none does; fills the
-// LDS offsets of `p` and returns the dynamic LDS size through *lds_bytes.
-uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes);
+// LDS offsets of `p` and returns the dynamic LDS size through *lds_bytes.  tap_floats: floats per tap in the
+// workgroup's LDS copy of the taps (2 for the tuned survey's pairs).
+uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes, uint32_t tap_floats = 1);
 hipError_t launch_survey(const SurveyParams &p, uint32_t num_captures, size_t lds_bytes, hipStream_t stream);
+
+// ---- tuned envelope survey (survey_tuned.hip) ------------------------------------
+// The histogram of the tuned contract's power (ookd_filter_tuned_taps): exact order, no guard band.  SurveyParams
+// is the untuned survey's, unchanged; the complex taps travel beside it: ctaps = (re, im) pairs, stage s at
+// ctaps + 2 * tap_off, and behind the last stage's taps zero pairs up to a multiple of 16 (the register-blocked
+// form reads whole chunks).
+//   generic : survey_kernel's structure with the four statements per tap, any shape (tile and LDS offsets from
+//             survey_tile(p, &lds, 2))
+//   fir1    : 1 stage, decimation 1, <= 256 taps: register-blocked, one wave = one tile of 64 R outputs,
+//             persistent workgroups of `waves` waves; p.tile = 64 R, p.stage[0].ntaps_pad a multiple of 16
+constexpr int kSurveyTunedChunk = 16;           // complex taps per chunk of the register-blocked form: 32 SGPRs
+constexpr int kSurveyFir1R = 8;                 // outputs per lane       } chosen by measurement: DESIGN.md 4.13
+constexpr int kSurveyFir1Waves = 4;             // waves per workgroup    }
+bool survey_tuned_fir1_shape(uint32_t R, uint32_t waves);      // a shape the kernel is instantiated for
+hipError_t launch_survey_tuned_generic(const SurveyParams &p, const float *ctaps, uint32_t num_captures,
+                                       size_t lds_bytes, hipStream_t stream);
+hipError_t launch_survey_tuned_fir1(const SurveyParams &p, const float *ctaps, uint32_t num_captures, uint32_t R,
+                                    uint32_t waves, hipStream_t stream);
 
 // ---- carrier survey (spectrum.hip) ----------------------------------------------
 // Welch power spectrum of every capture: whole 1024-sample periodic-Hann frames, fp32 inside a frame, double

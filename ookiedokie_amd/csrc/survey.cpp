@@ -21,6 +21,12 @@ struct ookd_survey {
     SurveyParams params{};          // stages, taps, tile geometry
     size_t lds_bytes = 0;
     float *d_taps = nullptr;
+    // tuned survey (ookd_survey_create_tuned with nu != 0): the form its runs take, the complex taps as (re, im)
+    // pairs, and the register-blocked form's shape
+    uint32_t form = OOKD_SURVEY_GENERIC;
+    double tune_nu = 0.0;
+    float *d_ctaps = nullptr;
+    uint32_t fir1_R = kSurveyFir1R, fir1_waves = kSurveyFir1Waves;
     unsigned long long *d_hist = nullptr;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     float kernel_ms = 0.0f;
@@ -31,6 +37,7 @@ struct ookd_survey {
     ~ookd_survey() {
         (void)hipSetDevice(dev);
         if (d_taps) (void)hipFree(d_taps);
+        if (d_ctaps) (void)hipFree(d_ctaps);
         if (d_hist) (void)hipFree(d_hist);
         if (t0) (void)hipEventDestroy(t0);
         if (t1) (void)hipEventDestroy(t1);
@@ -183,20 +190,16 @@ int ookd_suggest_threshold(const ookd_level_hist *h, ookd_threshold_suggestion *
     return OOKD_OK;
 }
 
-ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter, uint32_t sample_flags,
-                                uint32_t max_captures, void *stream) {
-    clear_error();
-    const uint32_t both = OOKD_RX_SAMPLES_CS8 | OOKD_RX_SAMPLES_CU8;
-    if ((sample_flags & ~both) || (sample_flags & both) == both) {
-        set_error("ookd_survey_create: sample_flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8");
-        return nullptr;
-    }
+// One implementation behind both entry points; `who` names the caller in the messages.  nu == 0 is the untuned
+// survey whatever `exact` says.
+static ookd_survey *survey_create(const char *who, int32_t hip_device, const ookd_filter *filter,
+                                  uint32_t sample_flags, uint32_t max_captures, void *stream, double nu, bool exact) {
     if (max_captures == 0 || max_captures > 65535u) {
-        set_error("ookd_survey_create: max_captures must be 1 .. 65535");
+        set_error("%s: max_captures must be 1 .. 65535", who);
         return nullptr;
     }
     if (filter && (filter->stages.empty() || filter->stages.size() > (size_t)kMaxStages)) {
-        set_error("ookd_survey_create: filters of 1 .. %d stages are supported", kMaxStages);
+        set_error("%s: filters of 1 .. %d stages are supported", who, kMaxStages);
         return nullptr;
     }
     int ndev = 0;
@@ -208,6 +211,7 @@ ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter, u
     s->dev = hip_device;
     s->max_captures = max_captures;
     s->fmt = (sample_flags & OOKD_RX_SAMPLES_CS8) ? kFmtCs8 : (sample_flags & OOKD_RX_SAMPLES_CU8) ? kFmtCu8 : kFmtSc16;
+    s->tune_nu = nu != 0.0 ? nu : 0.0;
     (void)hipSetDevice(hip_device);
     std::vector<float> taps;
     SurveyParams &p = s->params;
@@ -218,7 +222,7 @@ ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter, u
         for (uint32_t i = 0; i < p.num_stages; ++i) {
             const auto &st = filter->stages[i];
             if (st.taps.empty() || st.decimation == 0) {
-                set_error("ookd_survey_create: stage %u has no taps or no decimation", i);
+                set_error("%s: stage %u has no taps or no decimation", who, i);
                 return nullptr;
             }
             FirStageDev d{};
@@ -229,15 +233,49 @@ ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter, u
             p.stage[i] = d;
         }
     }
-    if (!survey_tile(p, &s->lds_bytes)) {
-        set_error("ookd_survey_create: the filter's history does not fit the kernel's LDS window");
+    std::vector<float> ctaps;           // tuned: (re, im) pairs, stage s at 2 * tap_off
+    if (nu != 0.0) {
+        const bool fir1 = !exact && p.num_stages == 1 && p.stage[0].decim == 1 && p.stage[0].ntaps <= 256u;
+        s->form = fir1 ? OOKD_SURVEY_TUNED_FIR1 : OOKD_SURVEY_TUNED_GENERIC;
+        const size_t pad = (taps.size() + kSurveyTunedChunk - 1) / kSurveyTunedChunk * kSurveyTunedChunk;
+        ctaps.assign(2 * pad, 0.0f);
+        uint64_t before = 1;
+        for (uint32_t i = 0; i < p.num_stages; ++i) {
+            const auto &h = filter->stages[i].taps;
+            std::vector<float> re(h.size()), im(h.size());
+            tuned_stage_taps(h, nu, before, re.data(), im.data());
+            for (size_t k = 0; k < h.size(); ++k) {
+                ctaps[2 * (p.stage[i].tap_off + k)] = re[k];
+                ctaps[2 * (p.stage[i].tap_off + k) + 1] = im[k];
+            }
+            before *= filter->stages[i].decimation;
+        }
+        if (fir1) {
+            // the measured shape; OOKD_SURVEY_TUNED_SHAPE=<R>x<waves> is the experiment hook the
+            // rate tool sweeps with
+            if (const char *e = dev_getenv("OOKD_SURVEY_TUNED_SHAPE")) {
+                unsigned R = 0, w = 0;
+                if (sscanf(e, "%ux%u", &R, &w) != 2 || !survey_tuned_fir1_shape(R, w)) {
+                    set_error("%s: OOKD_SURVEY_TUNED_SHAPE must be 8x1 .. 16x4, not '%s'", who, e);
+                    return nullptr;
+                }
+                s->fir1_R = R;
+                s->fir1_waves = w;
+            }
+            p.stage[0].ntaps_pad = (uint32_t)pad;
+            p.tile = 64u * s->fir1_R;
+        }
+    }
+    if (s->form != OOKD_SURVEY_TUNED_FIR1 &&
+        !survey_tile(p, &s->lds_bytes, s->form == OOKD_SURVEY_TUNED_GENERIC ? 2u : 1u)) {
+        set_error("%s: the filter's history does not fit the kernel's LDS window", who);
         return nullptr;
     }
     if (stream) {
         s->stream = static_cast<hipStream_t>(stream);
     } else {
         if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-            set_error("ookd_survey_create: hipStreamCreate failed: %s", hipGetErrorString(hipGetLastError()));
+            set_error("%s: hipStreamCreate failed: %s", who, hipGetErrorString(hipGetLastError()));
             return nullptr;
         }
         s->own_stream = true;
@@ -248,14 +286,59 @@ ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter, u
                   (size_t)max_captures * kLevelBins * sizeof(unsigned long long)) != hipSuccess ||
         (!taps.empty() &&
          hipMemcpy(s->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ||
+        (!ctaps.empty() &&
+         (hipMalloc(reinterpret_cast<void **>(&s->d_ctaps), ctaps.size() * sizeof(float)) != hipSuccess ||
+          hipMemcpy(s->d_ctaps, ctaps.data(), ctaps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) ||
         hipEventCreate(&s->t0) != hipSuccess || hipEventCreate(&s->t1) != hipSuccess) {
-        set_error("ookd_survey_create: device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        set_error("%s: device allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
         return nullptr;
     }
     p.taps = s->d_taps;
     p.hist = s->d_hist;
     return s.release();
 }
+
+ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter, uint32_t sample_flags,
+                                uint32_t max_captures, void *stream) {
+    clear_error();
+    const uint32_t both = OOKD_RX_SAMPLES_CS8 | OOKD_RX_SAMPLES_CU8;
+    if ((sample_flags & ~both) || (sample_flags & both) == both) {
+        set_error("ookd_survey_create: sample_flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8");
+        return nullptr;
+    }
+    return survey_create("ookd_survey_create", hip_device, filter, sample_flags, max_captures, stream, 0.0, false);
+}
+
+ookd_survey *ookd_survey_create_tuned(int32_t hip_device, const ookd_filter *filter, uint32_t flags,
+                                      uint32_t max_captures, void *stream, const ookd_tune *tune) {
+    clear_error();
+    const uint32_t both = OOKD_RX_SAMPLES_CS8 | OOKD_RX_SAMPLES_CU8;
+    if ((flags & ~(both | OOKD_RX_EXACT_FIR)) || (flags & both) == both) {
+        set_error("ookd_survey_create_tuned: flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8, with or "
+                  "without OOKD_RX_EXACT_FIR");
+        return nullptr;
+    }
+    const double nu = tune ? tune->nu : 0.0;
+    if (!(std::fabs(nu) <= 0.5)) {
+        set_error("ookd_survey_create_tuned: nu must be within [-0.5, 0.5] cycles per sample");
+        return nullptr;
+    }
+    if (tune && (tune->reserved[0] | tune->reserved[1] | tune->reserved[2])) {
+        set_error("ookd_survey_create_tuned: ookd_tune.reserved must be zero");
+        return nullptr;
+    }
+    if (nu != 0.0 && !filter) {
+        set_error("ookd_survey_create_tuned: nu != 0 needs a filter: without one the power is |x|^2, which does not "
+                  "depend on nu");
+        return nullptr;
+    }
+    return survey_create("ookd_survey_create_tuned", hip_device, filter, flags & both, max_captures, stream, nu,
+                         (flags & OOKD_RX_EXACT_FIR) != 0);
+}
+
+double ookd_survey_tune(const ookd_survey *s) { return s ? s->tune_nu : 0.0; }
+
+uint32_t ookd_survey_form(const ookd_survey *s) { return s ? s->form : 0u; }
 
 void ookd_survey_destroy(ookd_survey *s) { delete s; }
 
@@ -285,7 +368,12 @@ int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, 
     s->kernel_ms = 0.0f;
     bool ok = hipMemsetAsync(s->d_hist, 0, hist_bytes, s->stream) == hipSuccess;
     ok = ok && hipEventRecord(s->t0, s->stream) == hipSuccess;
-    ok = ok && launch_survey(p, num_captures, s->lds_bytes, s->stream) == hipSuccess;
+    if (s->form == OOKD_SURVEY_TUNED_FIR1)
+        ok = ok && launch_survey_tuned_fir1(p, s->d_ctaps, num_captures, s->fir1_R, s->fir1_waves, s->stream) == hipSuccess;
+    else if (s->form == OOKD_SURVEY_TUNED_GENERIC)
+        ok = ok && launch_survey_tuned_generic(p, s->d_ctaps, num_captures, s->lds_bytes, s->stream) == hipSuccess;
+    else
+        ok = ok && launch_survey(p, num_captures, s->lds_bytes, s->stream) == hipSuccess;
     ok = ok && hipEventRecord(s->t1, s->stream) == hipSuccess;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "histogram word");
     ok = ok && hipMemcpyAsync(s->hist.data(), s->d_hist, hist_bytes, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
