@@ -7,13 +7,13 @@
 // anywhere.  The taps come from the host (ookd_filter_tuned_taps, the contract in include/ookiedokie_amd.h) as
 // (re, im) pairs; stage s of a decimating chain is tuned to nu times the decimation before it.
 //
-// The contract's arithmetic of one stage output (float32, unfused, tap 0 on the newest sample, from +0):
-//     ar = ar + re[k]*xr;   ar = ar - im[k]*xi;
-//     ai = ai + re[k]*xi;   ai = ai + im[k]*xr;
-// With im == 0 every extra term is +-0: nu = 0 is the reference's result.
+// The contract's arithmetic of one stage output (float32, unfused, tap 0 on the newest sample, from +0) is
+// tuned_step's four statements (front_dev.hpp).  With im == 0 every extra term is +-0: nu = 0 is the reference's
+// result.
 //
-//   fir1_tuned_kernel        : 1 stage, decimation 1, <= 256 taps (OOKD_FRONT_TUNED_FIR1): fused packed FMAs,
-//                              guard band, recompute in the contract's order -- the shape of fir1_bits_kernel
+//   fir1_tuned_kernel        : 1 stage, decimation 1, <= 256 taps (OOKD_FRONT_TUNED_FIR1): fused packed FMAs
+//                              (tuned_chunk<false, R>, front_dev.hpp), guard band and epilogue of fir1_tile_finish,
+//                              recompute in the contract's order
 //   fir_tuned_generic_kernel : the contract for every shape (OOKD_FRONT_TUNED_GENERIC)
 //
 // Compiled with -ffp-contract=off (see kernels.hip).
@@ -23,21 +23,9 @@
 
 #include <hip/hip_ext.h>
 
-#include <utility>
-
 #pragma clang fp contract(off)
 
 namespace ookd {
-
-constexpr int kTunedChunk = 16;         // complex taps per chunk: 32 SGPRs, what the real-tap kernel holds too
-
-// One tap of the contract, four statements in order.
-__device__ __forceinline__ void tuned_step(float &ar, float &ai, float cr, float ci, float2 x) {
-    ar = ar + cr * x.x;
-    ar = ar - ci * x.y;
-    ai = ai + cr * x.y;
-    ai = ai + ci * x.x;
-}
 
 // The contract's value of one output (guard-band path): sequential, unfused.
 template <int R>
@@ -46,31 +34,6 @@ __device__ __noinline__ float2 fir1_tuned_exact_output(const float2 *lds, uint32
     float ar = 0.0f, ai = 0.0f;
     for (uint32_t k = 0; k < ntaps; ++k) tuned_step(ar, ai, ctaps[2 * k], ctaps[2 * k + 1], lds[slot<R>(j_out - k)]);
     return make_float2(ar, ai);
-}
-
-// acc(re, im) += c * x for one complex tap c = tp (re, im) held in an SGPR pair, as two packed FMAs:
-//   (ar, ai) += (cr, cr) * (xr, xi)            op_sel_hi:[0,1,1]: both halves read tp.lo
-//   (ar, ai) += (-ci, ci) * (xi, xr)           both halves read tp.hi, x's halves swapped, the low product negated
-// Four FMAs per sample-tap where the real-tap kernel (cmac, kernels.hip) has two; one rounding per step.
-__device__ __forceinline__ void cmac_tuned(v2f &acc, v2f tp, v2f x) {
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "s"(tp), "v"(x));
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "+v"(acc) : "s"(tp), "v"(x));
-}
-
-// Compile-time unrolled body of one 16-tap chunk.  Window position W (newest first) feeds output r with
-// tap kk = r - W when 0 <= kk < 16, so every output receives its taps in ascending order.
-template <int R, int W, int... Rs>
-__device__ __forceinline__ void tuned_wstep(v2f *acc, const v2f *tpair, const v2f *base,
-                                            std::integer_sequence<int, Rs...>) {
-    constexpr int cp = W + kTunedChunk;                 // 1 .. R + 15
-    const v2f x = base[cp + cp / R];
-    ((void)((Rs - W >= 0 && Rs - W < kTunedChunk) ? (cmac_tuned(acc[Rs], tpair[(Rs - W) & 15], x), 0) : 0), ...);
-}
-
-template <int R, int... Ws>
-__device__ __forceinline__ void tuned_chunk(v2f *acc, const v2f *tpair, const v2f *base,
-                                            std::integer_sequence<int, Ws...>) {
-    (tuned_wstep<R, R - 1 - Ws>(acc, tpair, base, std::make_integer_sequence<int, R>{}), ...);
 }
 
 // One wavefront = one tile of 64 R outputs, working alone, as in fir1_bits_kernel: raw loads -> quiet test ->
@@ -146,11 +109,7 @@ __global__ __launch_bounds__(64) void fir1_tuned_kernel(const FrontParams p) {
         for (int i = 0; i < kRounds; ++i) {
             const uint32_t v = tid + 64u * i;
             if (64u * (i + 1) <= kTile / 4 || v < nvec) {
-                float2 *dst = lds + slot<R>(4 * v);        // 4 slots, never straddle a pad
-                dst[0] = unpack_iq(q[i].x);
-                dst[1] = unpack_iq(q[i].y);
-                dst[2] = unpack_iq(q[i].z);
-                dst[3] = unpack_iq(q[i].w);
+                store_unpacked<(int)kFmtSc16, R>(lds, v, q[i]);
             }
         }
     } else {
@@ -163,9 +122,7 @@ __global__ __launch_bounds__(64) void fir1_tuned_kernel(const FrontParams p) {
         }
     }
     // the window is private to this wavefront and the LDS executes one wave's accesses in order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
 
     // ---- accumulate ----------------------------------------------------------
     v2f acc[R];
@@ -175,30 +132,14 @@ __global__ __launch_bounds__(64) void fir1_tuned_kernel(const FrontParams p) {
     for (uint32_t c = 0; c < nchunks; ++c) {
         // 16 complex taps of this chunk -> 16 SGPR pairs (re, im)
         const float *tp = p.ctaps + 2u * c * kTunedChunk;
-        v8f ta, tb, tc, td;
-        asm volatile("s_load_dwordx8 %0, %4, 0x0\n\t"
-                     "s_load_dwordx8 %1, %4, 0x20\n\t"
-                     "s_load_dwordx8 %2, %4, 0x40\n\t"
-                     "s_load_dwordx8 %3, %4, 0x60\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&s"(ta), "=&s"(tb), "=&s"(tc), "=&s"(td)
-                     : "s"(tp)
-                     : "memory");
-        const v2f tpair[16] = {
-            __builtin_shufflevector(ta, ta, 0, 1), __builtin_shufflevector(ta, ta, 2, 3),
-            __builtin_shufflevector(ta, ta, 4, 5), __builtin_shufflevector(ta, ta, 6, 7),
-            __builtin_shufflevector(tb, tb, 0, 1), __builtin_shufflevector(tb, tb, 2, 3),
-            __builtin_shufflevector(tb, tb, 4, 5), __builtin_shufflevector(tb, tb, 6, 7),
-            __builtin_shufflevector(tc, tc, 0, 1), __builtin_shufflevector(tc, tc, 2, 3),
-            __builtin_shufflevector(tc, tc, 4, 5), __builtin_shufflevector(tc, tc, 6, 7),
-            __builtin_shufflevector(td, td, 0, 1), __builtin_shufflevector(td, td, 2, 3),
-            __builtin_shufflevector(td, td, 4, 5), __builtin_shufflevector(td, td, 6, 7)};
+        v2f tpair[16];
+        load_tap_chunk32(tp, tpair);
         // output r of this lane sits at window index Tp + R*tid + r; tap kc+kk reads
         // Tp + R*tid + r - kc - kk = R*tid + 16*m + (w + 16),  w = r - kk, m = (Tp - kc - 16)/16;
         // R*tid and 16*m are multiples of R (8 or 16), so their pad slots add up separately
         const uint32_t m = nchunks - 1 - c;
         const v2f *base = reinterpret_cast<const v2f *>(lds + (uint32_t)(R + 1) * tid + (16u + 16u / R) * m);
-        tuned_chunk<R>(acc, tpair, base, std::make_integer_sequence<int, R + kTunedChunk - 1>{});
+        tuned_chunk<false, R>(acc, tpair, base, std::make_integer_sequence<int, R + kTunedChunk - 1>{});
     }
 
     const uint32_t info = fir1_tile_finish<false, R>(p, acc, t0, tid, cap, words, [&](uint32_t r) {

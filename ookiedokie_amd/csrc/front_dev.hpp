@@ -1,5 +1,7 @@
-// front_dev.hpp -- device code shared by the front-end kernel files (kernels.hip, fir_tuned.hip): sample
-// unpacking, the 1-stage kernels' LDS window layout, and everything behind a tile's accumulators (threshold,
+// front_dev.hpp -- device code shared by the kernel files with a register-blocked 1-stage FIR (kernels.hip,
+// fir_tuned.hip, survey_tuned.hip) and by the survey's sample fetch (survey_dev.hpp): sample unpacking, the
+// 1-stage kernels' LDS window layout and wave-private fence, the tap-chunk load into SGPR pairs, the tuned
+// contract's tap step and the complex-tap chunk body, and everything behind a tile's accumulators (threshold,
 // guard band, bit packing, tile info).  Compiled with -ffp-contract=off: every a*b+c is a separately rounded
 // multiply and add; fused multiply-adds are written explicitly.
 #pragma once
@@ -7,6 +9,8 @@
 #include "kernels.hpp"
 
 #include <hip/hip_runtime.h>
+
+#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -74,6 +78,115 @@ __device__ __forceinline__ uint4 ld_nt4(const uint4 *p) {
 }
 
 __device__ __forceinline__ v2s as_v2s(uint32_t w) { return __builtin_bit_cast(v2s, w); }
+
+// One 16-byte vector v of an interior window, unpacked into its slots: 4 SC16Q11 samples or 8 8-bit ones.  They
+// never straddle a pad slot (R is 8 or 16).
+template <int FMT, int R>
+__device__ __forceinline__ void store_unpacked(float2 *lds, uint32_t v, uint4 q) {
+    if (FMT == (int)kFmtSc16) {
+        float2 *dst = lds + slot<R>(4u * v);
+        dst[0] = unpack_iq(q.x);
+        dst[1] = unpack_iq(q.y);
+        dst[2] = unpack_iq(q.z);
+        dst[3] = unpack_iq(q.w);
+    } else {
+        float2 *dst = lds + slot<R>(8u * v);
+        dst[0] = unpack_iq(widen8<FMT>(q.x & 0xffffu));
+        dst[1] = unpack_iq(widen8<FMT>(q.x >> 16));
+        dst[2] = unpack_iq(widen8<FMT>(q.y & 0xffffu));
+        dst[3] = unpack_iq(widen8<FMT>(q.y >> 16));
+        dst[4] = unpack_iq(widen8<FMT>(q.z & 0xffffu));
+        dst[5] = unpack_iq(widen8<FMT>(q.z >> 16));
+        dst[6] = unpack_iq(widen8<FMT>(q.w & 0xffffu));
+        dst[7] = unpack_iq(widen8<FMT>(q.w >> 16));
+    }
+}
+
+// Orders a wavefront's LDS writes against its own later reads (or the other way round) where the memory is
+// private to the wave: the LDS executes one wave's accesses in order, so no workgroup barrier is needed -- this
+// only keeps the compiler from moving accesses across it.  Each call site says why its memory is wave-private.
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// 32 floats at tp (wave-uniform, 4-byte aligned) -> 16 SGPR pairs: 32 real taps, or 16 complex ones as (re, im).
+__device__ __forceinline__ void load_tap_chunk32(const float *tp, v2f *tpair) {
+    v8f ta, tb, tc, td;
+    asm volatile("s_load_dwordx8 %0, %4, 0x0\n\t"
+                 "s_load_dwordx8 %1, %4, 0x20\n\t"
+                 "s_load_dwordx8 %2, %4, 0x40\n\t"
+                 "s_load_dwordx8 %3, %4, 0x60\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(ta), "=&s"(tb), "=&s"(tc), "=&s"(td)
+                 : "s"(tp)
+                 : "memory");
+    tpair[0] = __builtin_shufflevector(ta, ta, 0, 1);
+    tpair[1] = __builtin_shufflevector(ta, ta, 2, 3);
+    tpair[2] = __builtin_shufflevector(ta, ta, 4, 5);
+    tpair[3] = __builtin_shufflevector(ta, ta, 6, 7);
+    tpair[4] = __builtin_shufflevector(tb, tb, 0, 1);
+    tpair[5] = __builtin_shufflevector(tb, tb, 2, 3);
+    tpair[6] = __builtin_shufflevector(tb, tb, 4, 5);
+    tpair[7] = __builtin_shufflevector(tb, tb, 6, 7);
+    tpair[8] = __builtin_shufflevector(tc, tc, 0, 1);
+    tpair[9] = __builtin_shufflevector(tc, tc, 2, 3);
+    tpair[10] = __builtin_shufflevector(tc, tc, 4, 5);
+    tpair[11] = __builtin_shufflevector(tc, tc, 6, 7);
+    tpair[12] = __builtin_shufflevector(td, td, 0, 1);
+    tpair[13] = __builtin_shufflevector(td, td, 2, 3);
+    tpair[14] = __builtin_shufflevector(td, td, 4, 5);
+    tpair[15] = __builtin_shufflevector(td, td, 6, 7);
+}
+
+// ---- complex taps: the tuned contract (include/ookiedokie_amd.h at ookd_filter_tuned_taps) --------------------
+// One tap c = (cr, ci) on sample x of one stage output, float32, unfused, tap 0 on the newest sample, the
+// accumulators from +0: the contract's four statements, in its order.  This is the only copy; every kernel that
+// computes the contract's value calls it (the generic tuned front end and survey, the guard-band recompute).
+__device__ __forceinline__ void tuned_step(float &ar, float &ai, float cr, float ci, float2 x) {
+    ar = ar + cr * x.x;
+    ar = ar - ci * x.y;
+    ai = ai + cr * x.y;
+    ai = ai + ci * x.x;
+}
+
+// acc(re, im) += c * x for one complex tap c = tp (re, im) held in an SGPR pair, two components at a time:
+//   (ar, ai) += (cr, cr) * (xr, xi)            op_sel_hi:[0,1(,1)]: both halves read tp.lo
+//   (ar, ai) += (-ci, ci) * (xi, xr)           both halves read tp.hi, x's halves swapped, the low product negated
+//   fused : two v_pk_fma_f32, one rounding per step (four FMAs per sample-tap where cmac, kernels.hip, has two)
+//   exact : v_pk_mul_f32 then v_pk_add_f32 twice, every product and every sum rounded on its own -- tuned_step's
+//           four statements: ar receives cr*xr first and ci*xi second (x + (-y) is x - y bit for bit), ai cr*xi
+//           first and ci*xr second
+template <bool EXACT>
+__device__ __forceinline__ void cmac_tuned(v2f &acc, v2f tp, v2f x) {
+    if (EXACT) {
+        v2f p1, p2;
+        asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(p1) : "s"(tp), "v"(x));
+        asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc) : "v"(p1));
+        asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[1,0]" : "=v"(p2) : "s"(tp), "v"(x));
+        asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc) : "v"(p2));
+    } else {
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "s"(tp), "v"(x));
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "+v"(acc) : "s"(tp), "v"(x));
+    }
+}
+
+// Compile-time unrolled body of one chunk of kTunedChunk = 16 complex taps.  Window position W (newest first)
+// feeds output r with tap kk = r - W when 0 <= kk < 16, so every output receives its taps in ascending order.
+template <bool EXACT, int R, int W, int... Rs>
+__device__ __forceinline__ void tuned_wstep(v2f *acc, const v2f *tpair, const v2f *base,
+                                            std::integer_sequence<int, Rs...>) {
+    constexpr int cp = W + kTunedChunk;                 // 1 .. R + 15
+    const v2f x = base[cp + cp / R];
+    ((void)((Rs - W >= 0 && Rs - W < kTunedChunk) ? (cmac_tuned<EXACT>(acc[Rs], tpair[(Rs - W) & 15], x), 0) : 0), ...);
+}
+
+template <bool EXACT, int R, int... Ws>
+__device__ __forceinline__ void tuned_chunk(v2f *acc, const v2f *tpair, const v2f *base,
+                                            std::integer_sequence<int, Ws...>) {
+    (tuned_wstep<EXACT, R, R - 1 - Ws>(acc, tpair, base, std::make_integer_sequence<int, R>{}), ...);
+}
 
 // Everything behind the accumulators of one wave tile of a 1-stage kernel (lane `tid` holds outputs
 // t0 + R tid .. + R - 1 in acc): threshold + guard band, bit packing, optional float output.  `exact(r)`

@@ -29,7 +29,7 @@
 namespace ookd {
 
 // ---------------------------------------------------------------------------
-// small helpers (the ones shared with fir_tuned.hip: front_dev.hpp)
+// small helpers (the ones shared with fir_tuned.hip and survey_tuned.hip: front_dev.hpp)
 // ---------------------------------------------------------------------------
 
 // fetch_sample for int16 inputs, returned raw (packed I | Q << 16).
@@ -142,24 +142,8 @@ __device__ __forceinline__ uint32_t fir1_tile_compute(const FrontParams &p, floa
     for (uint32_t c = 0; c < nchunks; ++c) {
         // 32 taps of this chunk -> 16 SGPR pairs
         const float *tp = p.taps + c * kTapChunk;
-        v8f ta, tb, tc, td;
-        asm volatile("s_load_dwordx8 %0, %4, 0x0\n\t"
-                     "s_load_dwordx8 %1, %4, 0x20\n\t"
-                     "s_load_dwordx8 %2, %4, 0x40\n\t"
-                     "s_load_dwordx8 %3, %4, 0x60\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&s"(ta), "=&s"(tb), "=&s"(tc), "=&s"(td)
-                     : "s"(tp)
-                     : "memory");
-        const v2f tpair[16] = {
-            __builtin_shufflevector(ta, ta, 0, 1), __builtin_shufflevector(ta, ta, 2, 3),
-            __builtin_shufflevector(ta, ta, 4, 5), __builtin_shufflevector(ta, ta, 6, 7),
-            __builtin_shufflevector(tb, tb, 0, 1), __builtin_shufflevector(tb, tb, 2, 3),
-            __builtin_shufflevector(tb, tb, 4, 5), __builtin_shufflevector(tb, tb, 6, 7),
-            __builtin_shufflevector(tc, tc, 0, 1), __builtin_shufflevector(tc, tc, 2, 3),
-            __builtin_shufflevector(tc, tc, 4, 5), __builtin_shufflevector(tc, tc, 6, 7),
-            __builtin_shufflevector(td, td, 0, 1), __builtin_shufflevector(td, td, 2, 3),
-            __builtin_shufflevector(td, td, 4, 5), __builtin_shufflevector(td, td, 6, 7)};
+        v2f tpair[16];
+        load_tap_chunk32(tp, tpair);
 
         // output r of this lane sits at window index Tp + R*tid + r; tap kc+kk reads
         // Tp + R*tid + r - kc - kk = R*tid + 32*m + (w + 32),  w = r - kk, m = (Tp - kc - 32)/32;
@@ -314,11 +298,7 @@ __global__ __launch_bounds__(64 * kFirWgWaves) void fir1_bits_kernel(const Front
         for (int i = 0; i < kRounds; ++i) {
             const uint32_t v = tid + 64u * i;
             if (64u * (i + 1) <= kTile / 4 || v < nvec) {
-                float2 *dst = lds + slot<R>(4 * v);        // 4 slots, never straddle a pad
-                dst[0] = unpack_iq(q[i].x);
-                dst[1] = unpack_iq(q[i].y);
-                dst[2] = unpack_iq(q[i].z);
-                dst[3] = unpack_iq(q[i].w);
+                store_unpacked<(int)kFmtSc16, R>(lds, v, q[i]);
             }
         }
     } else {
@@ -333,9 +313,7 @@ __global__ __launch_bounds__(64 * kFirWgWaves) void fir1_bits_kernel(const Front
     // the window is private to this wavefront and the LDS executes one wave's
     // accesses in order: no workgroup barrier, only keep the compiler from
     // moving reads above the writes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
 
     const uint32_t info = fir1_tile_compute<EXACT, R>(p, lds, Tp, t0, tid, cap, words);
     if (tid == 0) p.tile_info[(uint64_t)cap * p.tiles_per_cap + t0 / kTile] = info;
@@ -531,9 +509,7 @@ __global__ __launch_bounds__(64 * kFir2Waves) void fir2_bits_kernel(const FrontP
             lds0[li + li / G::P1] = fetch_raw(p, src, a0 + li);
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
 
     // ---- stage 1: lane t -> local outputs R1*t .. R1*t + R1-1 ---------------------------
     {
@@ -549,9 +525,7 @@ __global__ __launch_bounds__(64 * kFir2Waves) void fir2_bits_kernel(const FrontP
             lds1[j + j / G::P2] = make_float2(acc[r].x, acc[r].y);
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
 
     // ---- stage 2: lane t -> final outputs J0 + R2*t .. + R2-1 ------------------------------
     v2f acc[G::R2];

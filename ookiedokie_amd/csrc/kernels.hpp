@@ -13,6 +13,8 @@ namespace ookd {
 
 constexpr int kMaxStages = 8;
 constexpr int kTapChunk = 32;           // taps are padded to a multiple of this
+constexpr int kTunedChunk = 16;         // complex taps per chunk of the register-blocked tuned kernels (front end and
+                                        // survey): 32 SGPRs, what a chunk of real taps holds too
 constexpr int kFirThreads = 256;        // lanes behind one 4096-output block of bit words
 constexpr int kFirR = 16;               // outputs per lane in the 1-stage kernel
 constexpr int kFirTile = kFirThreads * kFirR;   // 4096 outputs per workgroup
@@ -515,23 +517,25 @@ struct SurveyParams {
 // LDS offsets of `p` and returns the dynamic LDS size through *lds_bytes.  tap_floats: floats per tap in the
 // workgroup's LDS copy of the taps (2 for the tuned survey's pairs).
 uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes, uint32_t tap_floats = 1);
-hipError_t launch_survey(const SurveyParams &p, uint32_t num_captures, size_t lds_bytes, hipStream_t stream);
+// ctaps == null: the untuned survey, real taps from p.taps.  Otherwise the tuned survey in the contract's order for
+// any shape (at least one stage), its complex taps from ctaps (below).
+hipError_t launch_survey(const SurveyParams &p, const float *ctaps, uint32_t num_captures, size_t lds_bytes,
+                         hipStream_t stream);
+// multiprocessors of the current device (what a persistent grid is sized by)
+hipError_t survey_device_cus(int *cus);
 
 // ---- tuned envelope survey (survey_tuned.hip) ------------------------------------
 // The histogram of the tuned contract's power (ookd_filter_tuned_taps): exact order, no guard band.  SurveyParams
 // is the untuned survey's, unchanged; the complex taps travel beside it: ctaps = (re, im) pairs, stage s at
 // ctaps + 2 * tap_off, and behind the last stage's taps zero pairs up to a multiple of 16 (the register-blocked
 // form reads whole chunks).
-//   generic : survey_kernel's structure with the four statements per tap, any shape (tile and LDS offsets from
-//             survey_tile(p, &lds, 2))
+//   generic : survey_kernel<FMT, true> (survey.hip): the four statements per tap, any shape (launch_survey with
+//             ctaps; tile and LDS offsets from survey_tile(p, &lds, 2))
 //   fir1    : 1 stage, decimation 1, <= 256 taps: register-blocked, one wave = one tile of 64 R outputs,
-//             persistent workgroups of `waves` waves; p.tile = 64 R, p.stage[0].ntaps_pad a multiple of 16
-constexpr int kSurveyTunedChunk = 16;           // complex taps per chunk of the register-blocked form: 32 SGPRs
+//             persistent workgroups of `waves` waves; p.tile = 64 R, p.stage[0].ntaps_pad a multiple of kTunedChunk
 constexpr int kSurveyFir1R = 8;                 // outputs per lane       } chosen by measurement: DESIGN.md 4.13
 constexpr int kSurveyFir1Waves = 4;             // waves per workgroup    }
 bool survey_tuned_fir1_shape(uint32_t R, uint32_t waves);      // a shape the kernel is instantiated for
-hipError_t launch_survey_tuned_generic(const SurveyParams &p, const float *ctaps, uint32_t num_captures,
-                                       size_t lds_bytes, hipStream_t stream);
 hipError_t launch_survey_tuned_fir1(const SurveyParams &p, const float *ctaps, uint32_t num_captures, uint32_t R,
                                     uint32_t waves, hipStream_t stream);
 

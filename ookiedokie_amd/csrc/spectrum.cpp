@@ -5,20 +5,14 @@
 #include <cstring>
 #include <memory>
 
-#include "common.hpp"
-#include "kernels.hpp"
+#include "scan_ctx.hpp"
 
 using namespace ookd;
 
 static_assert(OOKD_SPECTRUM_BINS == kSpecBins, "OOKD_SPECTRUM_BINS");
 
-struct ookd_spectrum {
-    int dev = 0;
+struct ookd_spectrum : ScanCtx {
     int cus = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    uint32_t fmt = kFmtSc16;
-    uint32_t max_captures = 1;
     float2 *d_twiddle = nullptr;
     float *d_window = nullptr;
     double *d_partial = nullptr;
@@ -26,22 +20,18 @@ struct ookd_spectrum {
     double *d_power = nullptr;      // [max_captures][1024]
     void *d_stage = nullptr;        // ookd_spectrum_host's copy of the capture, kept and grown
     size_t stage_bytes = 0;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    float kernel_ms = 0.0f;
     uint32_t num_captures = 0;      // of the last run
     uint64_t frames = 0;            // floor(n / 1024) of the last run
     std::vector<double> power;      // [num_captures][1024]
 
     ~ookd_spectrum() {
+        if (dev < 0) return;
         (void)hipSetDevice(dev);
         if (d_twiddle) (void)hipFree(d_twiddle);
         if (d_window) (void)hipFree(d_window);
         if (d_partial) (void)hipFree(d_partial);
         if (d_power) (void)hipFree(d_power);
         if (d_stage) (void)hipFree(d_stage);
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -98,37 +88,13 @@ int ookd_suggest_carriers(const ookd_spectrum_result *sp, double min_ratio, uint
 
 ookd_spectrum *ookd_spectrum_create(int32_t hip_device, uint32_t sample_flags, uint32_t max_captures, void *stream) {
     clear_error();
-    const uint32_t both = OOKD_RX_SAMPLES_CS8 | OOKD_RX_SAMPLES_CU8;
-    if ((sample_flags & ~both) || (sample_flags & both) == both) {
-        set_error("ookd_spectrum_create: sample_flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8");
-        return nullptr;
-    }
-    if (max_captures == 0 || max_captures > 65535u) {
-        set_error("ookd_spectrum_create: max_captures must be 1 .. 65535");
-        return nullptr;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || hip_device < 0 || hip_device >= ndev) {
-        set_error("no HIP device %d available: libookiedokie_amd has no CPU fallback", hip_device);
-        return nullptr;
-    }
+    const char *who = "ookd_spectrum_create";
+    if (!scan_ctx_check_create(who, sample_flags, max_captures)) return nullptr;
     std::unique_ptr<ookd_spectrum> s(new ookd_spectrum());
-    s->dev = hip_device;
-    s->max_captures = max_captures;
-    s->fmt = (sample_flags & OOKD_RX_SAMPLES_CS8) ? kFmtCs8 : (sample_flags & OOKD_RX_SAMPLES_CU8) ? kFmtCu8 : kFmtSc16;
-    (void)hipSetDevice(hip_device);
+    if (!scan_ctx_open(*s, who, hip_device, sample_flags, max_captures, stream)) return nullptr;
     if (hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, hip_device) != hipSuccess || s->cus < 1) {
         set_error("ookd_spectrum_create: cannot read the device's CU count");
         return nullptr;
-    }
-    if (stream) {
-        s->stream = static_cast<hipStream_t>(stream);
-    } else {
-        if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-            set_error("ookd_spectrum_create: hipStreamCreate failed: %s", hipGetErrorString(hipGetLastError()));
-            return nullptr;
-        }
-        s->own_stream = true;
     }
     // the tables, in double, rounded once: the angle is reduced to an exact multiple of 1/1024 turn first
     std::vector<float2> tw(kSpecBins);
@@ -149,8 +115,7 @@ ookd_spectrum *ookd_spectrum_create(int32_t hip_device, uint32_t sample_flags, u
         hipMalloc(reinterpret_cast<void **>(&s->d_power), (size_t)max_captures * kSpecBins * sizeof(double)) !=
             hipSuccess ||
         hipMemcpy(s->d_twiddle, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s->d_window, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipEventCreate(&s->t0) != hipSuccess || hipEventCreate(&s->t1) != hipSuccess) {
+        hipMemcpy(s->d_window, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("ookd_spectrum_create: device allocation failed: %s", hipGetErrorString(hipGetLastError()));
         return nullptr;
     }
@@ -162,22 +127,10 @@ void ookd_spectrum_destroy(ookd_spectrum *s) { delete s; }
 int ookd_spectrum_device(ookd_spectrum *s, const void *d_iq, uint32_t num_captures, uint64_t samples_per_capture,
                          uint64_t capture_stride_samples) {
     clear_error();
-    if (!s || num_captures == 0 || num_captures > s->max_captures || (!d_iq && samples_per_capture) ||
-        (num_captures > 1 && capture_stride_samples < samples_per_capture)) {
-        set_error("ookd_spectrum_device: bad argument (captures %u of at most %u, %llu samples, stride %llu)",
-                  num_captures, s ? s->max_captures : 0, (unsigned long long)samples_per_capture,
-                  (unsigned long long)capture_stride_samples);
-        return OOKD_ERR_ARG;
-    }
-    if ((samples_per_capture >> 48) || (capture_stride_samples >> 48)) {
-        set_error("ookd_spectrum_device: captures of 2^48 samples and more are not supported");
-        return OOKD_ERR_ARG;
-    }
+    const int rc = scan_ctx_check_run(s, "ookd_spectrum_device", d_iq, num_captures, samples_per_capture,
+                                      capture_stride_samples, true);
+    if (rc != OOKD_OK) return rc;
     const uint32_t sb = sample_bytes(s->fmt);
-    if ((uintptr_t)d_iq % sb) {
-        set_error("ookd_spectrum_device: the capture is not aligned to its %u-byte samples", sb);
-        return OOKD_ERR_ARG;
-    }
     (void)hipSetDevice(s->dev);
     SpectrumParams p{};
     p.iq = d_iq;
@@ -224,27 +177,11 @@ int ookd_spectrum_device(ookd_spectrum *s, const void *d_iq, uint32_t num_captur
 
 int ookd_spectrum_host(ookd_spectrum *s, const void *iq, uint64_t num_samples) {
     clear_error();
-    if (!s || (!iq && num_samples)) {
-        set_error("ookd_spectrum_host: bad argument");
-        return OOKD_ERR_ARG;
-    }
-    (void)hipSetDevice(s->dev);
-    const size_t bytes = (size_t)num_samples * sample_bytes(s->fmt);
-    if (bytes > s->stage_bytes) {           // the staging buffer stays with the context and only grows
-        if (s->d_stage) (void)hipFree(s->d_stage);
-        s->d_stage = nullptr;
-        s->stage_bytes = 0;
-        if (hipMalloc(&s->d_stage, bytes) != hipSuccess) {
-            set_error("ookd_spectrum_host: cannot allocate %zu bytes of device memory", bytes);
-            return OOKD_ERR_NOMEM;
-        }
-        s->stage_bytes = bytes;
-    }
-    if (bytes && hipMemcpy(s->d_stage, iq, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("ookd_spectrum_host: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-        return OOKD_ERR_HIP;
-    }
-    return ookd_spectrum_device(s, bytes ? s->d_stage : nullptr, 1, num_samples, num_samples);
+    // the staging buffer stays with the context and only grows
+    const int rc = scan_ctx_stage(s, "ookd_spectrum_host", iq, num_samples, s ? &s->d_stage : nullptr,
+                                  s ? &s->stage_bytes : nullptr);
+    if (rc != OOKD_OK) return rc;
+    return ookd_spectrum_device(s, num_samples ? s->d_stage : nullptr, 1, num_samples, num_samples);
 }
 
 int ookd_spectrum_get(const ookd_spectrum *s, uint32_t capture, ookd_spectrum_result *out) {

@@ -4,19 +4,13 @@
 #include <cstring>
 #include <memory>
 
-#include "common.hpp"
-#include "kernels.hpp"
+#include "scan_ctx.hpp"
 
 using namespace ookd;
 
 static_assert(OOKD_LEVEL_BINS == kLevelBins, "OOKD_LEVEL_BINS");
 
-struct ookd_survey {
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    uint32_t fmt = kFmtSc16;
-    uint32_t max_captures = 1;
+struct ookd_survey : ScanCtx {
     uint32_t total_decim = 1;
     SurveyParams params{};          // stages, taps, tile geometry
     size_t lds_bytes = 0;
@@ -28,20 +22,16 @@ struct ookd_survey {
     float *d_ctaps = nullptr;
     uint32_t fir1_R = kSurveyFir1R, fir1_waves = kSurveyFir1Waves;
     unsigned long long *d_hist = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    float kernel_ms = 0.0f;
     uint32_t num_captures = 0;      // of the last run
     uint64_t samples = 0;           // floor(n / D) of the last run
     std::vector<uint64_t> hist;     // [num_captures][kLevelBins]
 
     ~ookd_survey() {
+        if (dev < 0) return;
         (void)hipSetDevice(dev);
         if (d_taps) (void)hipFree(d_taps);
         if (d_ctaps) (void)hipFree(d_ctaps);
         if (d_hist) (void)hipFree(d_hist);
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -194,25 +184,14 @@ int ookd_suggest_threshold(const ookd_level_hist *h, ookd_threshold_suggestion *
 // survey whatever `exact` says.
 static ookd_survey *survey_create(const char *who, int32_t hip_device, const ookd_filter *filter,
                                   uint32_t sample_flags, uint32_t max_captures, void *stream, double nu, bool exact) {
-    if (max_captures == 0 || max_captures > 65535u) {
-        set_error("%s: max_captures must be 1 .. 65535", who);
-        return nullptr;
-    }
+    if (!scan_ctx_check_create(who, sample_flags, max_captures)) return nullptr;
     if (filter && (filter->stages.empty() || filter->stages.size() > (size_t)kMaxStages)) {
         set_error("%s: filters of 1 .. %d stages are supported", who, kMaxStages);
         return nullptr;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || hip_device < 0 || hip_device >= ndev) {
-        set_error("no HIP device %d available: libookiedokie_amd has no CPU fallback", hip_device);
-        return nullptr;
-    }
     std::unique_ptr<ookd_survey> s(new ookd_survey());
-    s->dev = hip_device;
-    s->max_captures = max_captures;
-    s->fmt = (sample_flags & OOKD_RX_SAMPLES_CS8) ? kFmtCs8 : (sample_flags & OOKD_RX_SAMPLES_CU8) ? kFmtCu8 : kFmtSc16;
+    if (!scan_ctx_open(*s, who, hip_device, sample_flags, max_captures, stream)) return nullptr;
     s->tune_nu = nu != 0.0 ? nu : 0.0;
-    (void)hipSetDevice(hip_device);
     std::vector<float> taps;
     SurveyParams &p = s->params;
     p.sample_fmt = s->fmt;
@@ -237,7 +216,7 @@ static ookd_survey *survey_create(const char *who, int32_t hip_device, const ook
     if (nu != 0.0) {
         const bool fir1 = !exact && p.num_stages == 1 && p.stage[0].decim == 1 && p.stage[0].ntaps <= 256u;
         s->form = fir1 ? OOKD_SURVEY_TUNED_FIR1 : OOKD_SURVEY_TUNED_GENERIC;
-        const size_t pad = (taps.size() + kSurveyTunedChunk - 1) / kSurveyTunedChunk * kSurveyTunedChunk;
+        const size_t pad = (taps.size() + kTunedChunk - 1) / kTunedChunk * kTunedChunk;
         ctaps.assign(2 * pad, 0.0f);
         uint64_t before = 1;
         for (uint32_t i = 0; i < p.num_stages; ++i) {
@@ -271,15 +250,6 @@ static ookd_survey *survey_create(const char *who, int32_t hip_device, const ook
         set_error("%s: the filter's history does not fit the kernel's LDS window", who);
         return nullptr;
     }
-    if (stream) {
-        s->stream = static_cast<hipStream_t>(stream);
-    } else {
-        if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-            set_error("%s: hipStreamCreate failed: %s", who, hipGetErrorString(hipGetLastError()));
-            return nullptr;
-        }
-        s->own_stream = true;
-    }
     const size_t tap_bytes = (taps.empty() ? 1 : taps.size()) * sizeof(float);
     if (hipMalloc(reinterpret_cast<void **>(&s->d_taps), tap_bytes) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&s->d_hist),
@@ -288,8 +258,7 @@ static ookd_survey *survey_create(const char *who, int32_t hip_device, const ook
          hipMemcpy(s->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ||
         (!ctaps.empty() &&
          (hipMalloc(reinterpret_cast<void **>(&s->d_ctaps), ctaps.size() * sizeof(float)) != hipSuccess ||
-          hipMemcpy(s->d_ctaps, ctaps.data(), ctaps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) ||
-        hipEventCreate(&s->t0) != hipSuccess || hipEventCreate(&s->t1) != hipSuccess) {
+          hipMemcpy(s->d_ctaps, ctaps.data(), ctaps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))) {
         set_error("%s: device allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
         return nullptr;
     }
@@ -301,11 +270,6 @@ static ookd_survey *survey_create(const char *who, int32_t hip_device, const ook
 ookd_survey *ookd_survey_create(int32_t hip_device, const ookd_filter *filter, uint32_t sample_flags,
                                 uint32_t max_captures, void *stream) {
     clear_error();
-    const uint32_t both = OOKD_RX_SAMPLES_CS8 | OOKD_RX_SAMPLES_CU8;
-    if ((sample_flags & ~both) || (sample_flags & both) == both) {
-        set_error("ookd_survey_create: sample_flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8");
-        return nullptr;
-    }
     return survey_create("ookd_survey_create", hip_device, filter, sample_flags, max_captures, stream, 0.0, false);
 }
 
@@ -345,17 +309,9 @@ void ookd_survey_destroy(ookd_survey *s) { delete s; }
 int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, uint64_t samples_per_capture,
                        uint64_t capture_stride_samples) {
     clear_error();
-    if (!s || num_captures == 0 || num_captures > s->max_captures || (!d_iq && samples_per_capture) ||
-        (num_captures > 1 && capture_stride_samples < samples_per_capture)) {
-        set_error("ookd_survey_device: bad argument (captures %u of at most %u, %llu samples, stride %llu)",
-                  num_captures, s ? s->max_captures : 0, (unsigned long long)samples_per_capture,
-                  (unsigned long long)capture_stride_samples);
-        return OOKD_ERR_ARG;
-    }
-    if (samples_per_capture >> 48) {
-        set_error("ookd_survey_device: captures of 2^48 samples and more are not supported");
-        return OOKD_ERR_ARG;
-    }
+    const int rc = scan_ctx_check_run(s, "ookd_survey_device", d_iq, num_captures, samples_per_capture,
+                                      capture_stride_samples, false);
+    if (rc != OOKD_OK) return rc;
     (void)hipSetDevice(s->dev);
     SurveyParams p = s->params;
     p.iq = d_iq;
@@ -370,10 +326,8 @@ int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, 
     ok = ok && hipEventRecord(s->t0, s->stream) == hipSuccess;
     if (s->form == OOKD_SURVEY_TUNED_FIR1)
         ok = ok && launch_survey_tuned_fir1(p, s->d_ctaps, num_captures, s->fir1_R, s->fir1_waves, s->stream) == hipSuccess;
-    else if (s->form == OOKD_SURVEY_TUNED_GENERIC)
-        ok = ok && launch_survey_tuned_generic(p, s->d_ctaps, num_captures, s->lds_bytes, s->stream) == hipSuccess;
-    else
-        ok = ok && launch_survey(p, num_captures, s->lds_bytes, s->stream) == hipSuccess;
+    else        // (d_ctaps is null unless the form is OOKD_SURVEY_TUNED_GENERIC)
+        ok = ok && launch_survey(p, s->d_ctaps, num_captures, s->lds_bytes, s->stream) == hipSuccess;
     ok = ok && hipEventRecord(s->t1, s->stream) == hipSuccess;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "histogram word");
     ok = ok && hipMemcpyAsync(s->hist.data(), s->d_hist, hist_bytes, hipMemcpyDeviceToHost, s->stream) == hipSuccess;
@@ -390,25 +344,10 @@ int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, 
 
 int ookd_survey_host(ookd_survey *s, const void *iq, uint64_t num_samples) {
     clear_error();
-    if (!s || (!iq && num_samples)) {
-        set_error("ookd_survey_host: bad argument");
-        return OOKD_ERR_ARG;
-    }
-    (void)hipSetDevice(s->dev);
-    void *d_iq = nullptr;
-    const size_t bytes = (size_t)num_samples * sample_bytes(s->fmt);
-    if (bytes) {
-        if (hipMalloc(&d_iq, bytes) != hipSuccess) {
-            set_error("ookd_survey_host: cannot allocate %zu bytes of device memory", bytes);
-            return OOKD_ERR_NOMEM;
-        }
-        if (hipMemcpy(d_iq, iq, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("ookd_survey_host: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-            (void)hipFree(d_iq);
-            return OOKD_ERR_HIP;
-        }
-    }
-    const int rc = ookd_survey_device(s, d_iq, 1, num_samples, num_samples);
+    void *d_iq = nullptr;               // this run's alone: freed again below
+    size_t capacity = 0;
+    int rc = scan_ctx_stage(s, "ookd_survey_host", iq, num_samples, &d_iq, &capacity);
+    if (rc == OOKD_OK) rc = ookd_survey_device(s, d_iq, 1, num_samples, num_samples);
     if (d_iq) (void)hipFree(d_iq);
     return rc;
 }

@@ -18,10 +18,17 @@
 // collide.  A workgroup walks many tiles and flushes once at its end: 256 lanes sum the four waves' counters
 // and issue one 64-bit vector atomic per non-zero bin to the capture's histogram in HBM.
 //
+// survey_kernel<FMT, TUNED>: TUNED = false is the above.  TUNED = true is the tuned survey for any shape
+// (OOKD_SURVEY_TUNED_GENERIC): the same walk with complex taps -- (re, im) pairs in LDS -- and the tuned contract's
+// four statements per tap (tuned_step, front_dev.hpp); a tuned survey always has a filter.  The register-blocked
+// tuned form is in survey_tuned.hip.
+//
 // Compiled with -ffp-contract=off like every kernel of the library.
 #include "kernels.hpp"
 #include "common.hpp"
 #include "survey_dev.hpp"
+
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -33,13 +40,14 @@ constexpr int kSurveyThreads = 256;
 constexpr int kSurveyWaves = kSurveyThreads / 64;
 constexpr uint64_t kMaxTilesPerGroup = 1ull << 20;  // x 1024 outputs: a 32-bit LDS counter cannot wrap
 
-template <int FMT>
-__global__ __launch_bounds__(kSurveyThreads) void survey_kernel(const SurveyParams p) {
+template <int FMT, bool TUNED>
+__global__ __launch_bounds__(kSurveyThreads) void survey_kernel(const SurveyParams p, const float *ctaps) {
+    typedef typename std::conditional<TUNED, float2, float>::type tap_t;    // one tap in LDS
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // one LDS base and offsets from it (a pointer picked from an array would be a generic one: flat loads)
     float2 *lds = reinterpret_cast<float2 *>(smem_raw);
     uint32_t *hist = reinterpret_cast<uint32_t *>(smem_raw + p.lds_hist_off);
-    float *ltaps = reinterpret_cast<float *>(smem_raw + p.lds_taps_off);
+    tap_t *ltaps = reinterpret_cast<tap_t *>(smem_raw + p.lds_taps_off);
 
     const uint32_t tid = threadIdx.x;
     const uint32_t cap = blockIdx.y;
@@ -49,14 +57,17 @@ __global__ __launch_bounds__(kSurveyThreads) void survey_kernel(const SurveyPara
                                (uint64_t)cap * p.cap_stride * sample_bytes((uint32_t)FMT);
 
     for (uint32_t i = tid; i < (uint32_t)(kSurveyWaves * kLevelBins); i += kSurveyThreads) hist[i] = 0u;
-    for (uint32_t i = tid; i < p.num_taps; i += kSurveyThreads) ltaps[i] = p.taps[i];
+    for (uint32_t i = tid; i < p.num_taps; i += kSurveyThreads) {
+        if constexpr (TUNED) ltaps[i] = make_float2(ctaps[2 * i], ctaps[2 * i + 1]);
+        else ltaps[i] = p.taps[i];
+    }
     __syncthreads();
 
     for (uint64_t tile = blockIdx.x; tile < p.num_tiles; tile += gridDim.x) {
         const int64_t j0 = (int64_t)(tile * p.tile);
         const uint64_t left = p.n_out - (uint64_t)j0;
         const uint32_t len = left < p.tile ? (uint32_t)left : p.tile;
-        if (S == 0) {                   // the samples themselves
+        if (!TUNED && S == 0) {         // the samples themselves
             for (uint32_t base = 0; base < len; base += kSurveyThreads) {
                 const uint32_t i = base + tid;
                 const bool valid = i < len;
@@ -81,7 +92,7 @@ __global__ __launch_bounds__(kSurveyThreads) void survey_kernel(const SurveyPara
         for (int s = 0; s < S; ++s) {
             const float2 *in = lds + ((s & 1) ? p.lds_b_off : 0u);
             float2 *out = lds + ((s & 1) ? 0u : p.lds_b_off);
-            const float *taps = ltaps + p.stage[s].tap_off;
+            const tap_t *taps = ltaps + p.stage[s].tap_off;
             const int64_t D = p.stage[s].decim;
             const uint32_t T = p.stage[s].ntaps;
             const bool last = (s == S - 1);
@@ -96,12 +107,17 @@ __global__ __launch_bounds__(kSurveyThreads) void survey_kernel(const SurveyPara
                     const float2 *x0 = in + ((uint32_t)D * i + T - 1u);
 #pragma unroll 4
                     for (uint32_t k = 0; k < T; ++k) {
-                        const float2 x = x0[-(int)k];
-                        const float t = taps[k];
-                        const float pr = t * x.x;
-                        const float pi = t * x.y;
-                        re = re + pr;
-                        im = im + pi;
+                        if constexpr (TUNED) {
+                            const float2 c = taps[k];
+                            tuned_step(re, im, c.x, c.y, x0[-(int)k]);
+                        } else {
+                            const float2 x = x0[-(int)k];
+                            const float t = taps[k];
+                            const float pr = t * x.x;
+                            const float pi = t * x.y;
+                            re = re + pr;
+                            im = im + pi;
+                        }
                     }
                 }
                 if (!last) {
@@ -165,12 +181,28 @@ uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes, uint32_t tap_floats) {
     return 0;
 }
 
-hipError_t launch_survey(const SurveyParams &p, uint32_t num_captures, size_t lds_bytes, hipStream_t stream) {
+hipError_t survey_device_cus(int *cus) {
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    return e != hipSuccess ? e : hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+}
+
+template <bool TUNED>
+static const void *survey_kernel_of(uint32_t fmt) {
+    switch (fmt) {
+    case kFmtSc16: return reinterpret_cast<const void *>(&survey_kernel<(int)kFmtSc16, TUNED>);
+    case kFmtCs8: return reinterpret_cast<const void *>(&survey_kernel<(int)kFmtCs8, TUNED>);
+    case kFmtCu8: return reinterpret_cast<const void *>(&survey_kernel<(int)kFmtCu8, TUNED>);
+    default: return nullptr;
+    }
+}
+
+hipError_t launch_survey(const SurveyParams &p, const float *ctaps, uint32_t num_captures, size_t lds_bytes,
+                         hipStream_t stream) {
     if (p.num_tiles == 0 || num_captures == 0) return hipSuccess;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (ctaps && p.num_stages == 0) return hipErrorInvalidValue;
+    int cus = 0;
+    hipError_t e = survey_device_cus(&cus);
     if (e != hipSuccess) return e;
     // as many workgroups as fit the device at once, each walking its share of the tiles and flushing once
     uint64_t per_cu = (160 * 1024) / lds_bytes;
@@ -181,21 +213,12 @@ hipError_t launch_survey(const SurveyParams &p, uint32_t num_captures, size_t ld
     if (gx < least) gx = least;
     if (gx > p.num_tiles) gx = p.num_tiles;
     if (gx > 0x7fffffffull || num_captures > 65535u) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t)gx, num_captures);
-    switch (p.sample_fmt) {
-    case kFmtSc16:
-        hipLaunchKernelGGL(survey_kernel<(int)kFmtSc16>, grid, dim3(kSurveyThreads), lds_bytes, stream, p);
-        break;
-    case kFmtCs8:
-        hipLaunchKernelGGL(survey_kernel<(int)kFmtCs8>, grid, dim3(kSurveyThreads), lds_bytes, stream, p);
-        break;
-    case kFmtCu8:
-        hipLaunchKernelGGL(survey_kernel<(int)kFmtCu8>, grid, dim3(kSurveyThreads), lds_bytes, stream, p);
-        break;
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const void *fn = ctaps ? survey_kernel_of<true>(p.sample_fmt) : survey_kernel_of<false>(p.sample_fmt);
+    if (!fn) return hipErrorInvalidValue;
+    SurveyParams pp = p;
+    void *args[] = {&pp, &ctaps};
+    e = hipLaunchKernel(fn, dim3((uint32_t)gx, num_captures), dim3(kSurveyThreads), args, lds_bytes, stream);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 }  // namespace ookd

@@ -1,9 +1,10 @@
 // survey_dev.hpp -- device code shared by the envelope survey's kernel files (survey.hip, survey_tuned.hip): the
-// slice of every level a tile needs, one sample of any format as float2, the bin of an output, and the wave's
-// aggregated count.  Compiled with -ffp-contract=off: the power keeps its three roundings.
+// slice of every level a tile needs, one sample of any format as float2 (unpack_iq, front_dev.hpp), the bin of an
+// output, and the wave's aggregated count.  Compiled with -ffp-contract=off: the power keeps its three roundings.
 #pragma once
 
 #include "kernels.hpp"
+#include "front_dev.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -15,7 +16,7 @@ constexpr int kPeelRounds = 4;
 constexpr size_t kSurveyLdsBudget = 40 * 1024;      // level buffers + histograms: four workgroups per CU
 
 // first index and length of the slice of every level that outputs [j0, j0 + len) of the last level need
-// (gen_levels of kernels.hip for origin 0)
+// (gen_levels of front_dev.hpp for origin 0)
 __host__ __device__ inline void survey_levels(const SurveyParams &p, int64_t j0, uint32_t len, int64_t *a,
                                               uint32_t *n) {
     const int S = (int)p.num_stages;
@@ -32,11 +33,8 @@ __host__ __device__ inline void survey_levels(const SurveyParams &p, int64_t j0,
 #ifdef __HIPCC__
 template <int FMT>
 __device__ __forceinline__ float2 survey_sample(const void *src, int64_t i) {
-    const float s = 1.0f / 2048.0f;
-    uint32_t w;
-    if (FMT == (int)kFmtSc16) w = reinterpret_cast<const uint32_t *>(src)[i];
-    else w = widen8<FMT>(reinterpret_cast<const uint16_t *>(src)[i]);
-    return make_float2((float)(int16_t)(w & 0xffffu) * s, (float)(int16_t)(w >> 16) * s);
+    if (FMT == (int)kFmtSc16) return unpack_iq(reinterpret_cast<const uint32_t *>(src)[i]);
+    return unpack_iq(widen8<FMT>(reinterpret_cast<const uint16_t *>(src)[i]));
 }
 
 __device__ __forceinline__ uint32_t survey_bin(float re, float im) {

@@ -7,7 +7,7 @@ One process, one seeded capture made like bench.py's north_star capture (synthet
 capture cut to 8 bits (CS8), filter fs32_fs4.  Three surveys take turns on it, one run in flight at a time:
   (a) the untuned Survey                                  form 1, survey_kernel
   (b) the tuned Survey, nu = 0.2                          form 3, survey_tuned_fir1_kernel
-  (c) the same with exact=True                            form 2, survey_tuned_generic_kernel
+  (c) the same with exact=True                            form 2, survey_kernel<FMT, true>
 Written: ookd_survey_kernel_ms of each as median with min and max, (b) / (a), (b) / (c), and whether (b) and (c) gave
 the same histogram.  --sweep also times form 3 in every shape the kernel is instantiated for (outputs per lane x waves
 per workgroup, through the OOKD_SURVEY_TUNED_SHAPE experiment hook) -- what kSurveyFir1R / kSurveyFir1Waves were
