@@ -4,7 +4,8 @@
  *     spectrum (ookd_spectrum_*, ookd_suggest_carriers)        which carriers are there
  *  -> per carrier a tuned envelope survey (ookd_survey_create_tuned, ookd_suggest_threshold)
  *                                                              which threshold does this carrier want
- *  -> per carrier and device a tuned context (ookd_rx_create_tuned) at that threshold
+ *  -> per device ONE carrier context (ookd_rx_create_carriers) that decodes every carrier at its own threshold in
+ *     one pass over the capture
  *  -> formatter / rx_print text on stdout.
  * The capture is loaded once and stays in HBM; every pass reads it there.
  *
@@ -66,6 +67,8 @@ int main(int argc, char **argv)
     ookd_spectrum *spectrum = NULL;
     ookd_survey *survey = NULL;
     ookd_rx *rx = NULL;
+    ookd_message *msgs[MAX_DEVICES] = { NULL };     /* per device: the messages of all carriers */
+    uint64_t nmsgs[MAX_DEVICES] = { 0 };
     char *text = NULL;
 
     void *sdr = sdr_hip_file_init((const struct ookiedokie_cfg *)&cfg);   /* same layout: see ookd_host_cfg */
@@ -110,6 +113,10 @@ int main(int argc, char **argv)
         goto out;
     }
 
+    ookd_rx_carrier carrier[MAX_CARRIERS];  /* the carriers that have a threshold, in the order they were found */
+    double carrier_hz[MAX_CARRIERS];
+    uint32_t ncar = 0;
+    memset(carrier, 0, sizeof(carrier));
     for (uint32_t c = 0; c < nfound; ++c) {
         if (found[c].at_dc) continue;
         const double hz = found[c].nu * (double) rate;
@@ -133,37 +140,52 @@ int main(int argc, char **argv)
         }
         fprintf(stderr, "carrier %+.6g Hz: threshold %.6g (off %.6g, on %.6g)\n", hz, sug.threshold, sug.off_level,
                 sug.on_level);
+        carrier[ncar].nu = found[c].nu;
+        carrier[ncar].threshold = sug.threshold;
+        carrier_hz[ncar] = hz;
+        ++ncar;
+    }
 
-        /* 3. decode, once per device */
+    /* 3. decode: per device ONE carrier context, which reads the capture once for all carriers.  Its messages come
+     * in carrier order, ookd_message.capture being the carrier index. */
+    for (int d = 0; d < ndev && ncar; ++d) {
+        ookd_rx_config rc;
+        memset(&rc, 0, sizeof(rc));
+        rc.samples_per_buffer = cfg.samples_per_buffer;
+        rc.max_samples = n ? n : 1;
+        rc.flags = sample_flags;
+        rx = ookd_rx_create_carriers(&rc, filter, device[d], carrier, ncar);
+        if (!rx) { fail("ookd_rx_create_carriers"); goto out; }
+        if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }
+        nmsgs[d] = ookd_rx_num_messages(rx);
+        if (nmsgs[d]) {
+            msgs[d] = malloc(nmsgs[d] * sizeof(ookd_message));
+            if (!msgs[d]) goto out;
+            memcpy(msgs[d], ookd_rx_messages(rx), nmsgs[d] * sizeof(ookd_message));
+        }
+        ookd_rx_destroy(rx);
+        rx = NULL;
+    }
+    /* one block per carrier and device, carrier by carrier */
+    for (uint32_t c = 0; c < ncar; ++c) {
         for (int d = 0; d < ndev; ++d) {
-            ookd_rx_config rc;
-            memset(&rc, 0, sizeof(rc));
-            rc.threshold = sug.threshold;
-            rc.samples_per_buffer = cfg.samples_per_buffer;
-            rc.max_samples = n ? n : 1;
-            rc.flags = sample_flags;
-            rx = ookd_rx_create_tuned(&rc, filter, device[d], &tune);
-            if (!rx) { fail("ookd_rx_create_tuned"); goto out; }
-            if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }
-            const uint64_t nmsg = ookd_rx_num_messages(rx);
-            if (nmsg) {
-                const ookd_message *msgs = ookd_rx_messages(rx);
-                int fp = 1;                 /* every block has its device's own CSV heading, as ookd_rx prints it */
-                const size_t len = ookd_print_messages(formatter[d], fmt, &fp, msgs, nmsg, cfg.samples_per_buffer,
-                                                       decimation, NULL, 0);
-                text = malloc(len + 1);
-                if (!text) goto out;
-                fp = 1;
-                ookd_print_messages(formatter[d], fmt, &fp, msgs, nmsg, cfg.samples_per_buffer, decimation,
-                                    text, len + 1);
-                fprintf(stderr, "carrier %+.6g Hz, %s: %llu messages\n", hz, ookd_device_name(device[d]),
-                        (unsigned long long) nmsg);
-                fputs(text, stdout);
-                free(text);
-                text = NULL;
-            }
-            ookd_rx_destroy(rx);
-            rx = NULL;
+            uint64_t first = 0, nmsg = 0;
+            while (first < nmsgs[d] && msgs[d][first].capture < c) ++first;
+            while (first + nmsg < nmsgs[d] && msgs[d][first + nmsg].capture == c) ++nmsg;
+            if (!nmsg) continue;
+            int fp = 1;                 /* every block has its device's own CSV heading, as ookd_rx prints it */
+            const size_t len = ookd_print_messages(formatter[d], fmt, &fp, msgs[d] + first, nmsg, cfg.samples_per_buffer,
+                                                   decimation, NULL, 0);
+            text = malloc(len + 1);
+            if (!text) goto out;
+            fp = 1;
+            ookd_print_messages(formatter[d], fmt, &fp, msgs[d] + first, nmsg, cfg.samples_per_buffer, decimation,
+                                text, len + 1);
+            fprintf(stderr, "carrier %+.6g Hz, %s: %llu messages\n", carrier_hz[c], ookd_device_name(device[d]),
+                    (unsigned long long) nmsg);
+            fputs(text, stdout);
+            free(text);
+            text = NULL;
         }
     }
     status = EXIT_SUCCESS;
@@ -174,6 +196,7 @@ out:
     ookd_survey_destroy(survey);
     ookd_spectrum_destroy(spectrum);
     for (int d = 0; d < MAX_DEVICES; ++d) {
+        free(msgs[d]);
         ookd_formatter_free(formatter[d]);
         ookd_device_free(device[d]);
     }

@@ -344,9 +344,13 @@ enum {
     OOKD_FRONT_TUNED_GENERIC = 12,  /* any shape, the contract's order throughout
                                        (also what OOKD_RX_EXACT_FIR selects):
                                        KEEP_FIR floats are the contract's       */
-    OOKD_FRONT_TUNED_FIR1 = 13      /* 1 stage, decimation 1, <= 256 taps:
+    OOKD_FRONT_TUNED_FIR1 = 13,     /* 1 stage, decimation 1, <= 256 taps:
                                        packed-VALU FMA (four per sample-tap) +
                                        guard band, recompute in contract order  */
+    /* Carrier contexts (ookd_rx_create_carriers): OOKD_FRONT_TUNED_FIR1's shape for
+     * all carriers in one pass over the capture.  Every other shape, and
+     * OOKD_RX_EXACT_FIR, runs OOKD_FRONT_TUNED_GENERIC once per carrier and reports 12. */
+    OOKD_FRONT_TUNED_MULTI = 14
 };
 
 /* The front end a context settled on at create time, and the forward error
@@ -390,6 +394,62 @@ typedef struct ookd_tune {
 ookd_rx *ookd_rx_create_tuned(const ookd_rx_config *cfg, const ookd_filter *filter,
                               const ookd_device *device, const ookd_tune *tune);
 double ookd_rx_tune(const ookd_rx *rx);    /* nu of the context, 0 for an untuned one */
+
+/* Several carriers of ONE capture in one context: the capture is read from HBM,
+ * tested for silence and unpacked once, the complex-tap accumulation and the
+ * threshold run per carrier (OOKD_FRONT_TUNED_MULTI, for the shape
+ * OOKD_FRONT_TUNED_FIR1 takes: 1 stage, decimation 1, <= 256 taps).
+ *
+ * CONTRACT.  Carrier k of a run is, bit for bit, the run of
+ * ookd_rx_create_tuned(cfg with threshold = carriers[k].threshold, filter,
+ * device, {carriers[k].nu}) on the same capture: bit words, edges, OUTPUT_READY
+ * sample indices, payloads and error positions.  With OOKD_RX_KEEP_FIR the
+ * floats are within that carrier's err_valu (ookd_rx_get_carrier_front_info) of
+ * the contract at ookd_filter_tuned_taps, and bitwise equal to it under
+ * OOKD_RX_EXACT_FIR.  nu = 0 is a legal carrier (im == +0: the untuned context's
+ * result); the same nu may appear twice with different thresholds.
+ * cfg->threshold is not used.
+ *
+ * Runs.  A carrier context runs ONE capture per run: ookd_rx_process_device,
+ * ookd_rx_submit_device / ookd_rx_wait with num_captures == 1, and
+ * ookd_rx_process_host.  cfg->max_captures must be 0 or 1; num_captures > 1,
+ * ookd_rx_shard_begin and ookd_rx_shard_refine fail with a message;
+ * pipeline_chunk_samples is ignored (the run is never pipelined).  One device
+ * per context.
+ *
+ * Results.  Inside, the carriers are the "captures" of a batched run: carrier
+ * k's bit words, edges, floats and messages live where capture k's would, with
+ * buffers sized for num_carriers captures at create time (a non-zero
+ * cfg->edge_capacity or message_capacity is the whole run's, all carriers
+ * together, as for a batch).  ookd_message.capture
+ * is the carrier index, and ookd_rx_get_bits, _get_edges, _get_fir,
+ * _get_fir_sc16q11, _dig_text, _record_dig and _record_fir take the carrier
+ * index as `capture`.  stats.total_waves and stats.quiet_waves count
+ * (window, carrier) pairs.
+ *
+ * Forms.  front_form / ookd_front_info.form report OOKD_FRONT_TUNED_MULTI when
+ * the fused kernel ran, OOKD_FRONT_TUNED_GENERIC when the shape is not the fused
+ * one (decimating or multi-stage filters, more than 256 taps) or with
+ * OOKD_RX_EXACT_FIR: then the generic kernel runs once per carrier.  8-bit
+ * contexts (OOKD_RX_SAMPLES_CS8 / _CU8) widen the capture ONCE into a staging
+ * copy and run either form on it.
+ *
+ * Fails, with a message: num_carriers == 0 or > OOKD_RX_MAX_CARRIERS,
+ * carriers == NULL, a NaN nu, |nu| > 0.5, no filter, non-zero reserved words,
+ * cfg->max_captures > 1. */
+#define OOKD_RX_MAX_CARRIERS 16
+typedef struct ookd_rx_carrier {
+    double nu;                      /* cycles per input sample, |nu| <= 0.5; 0 is allowed */
+    float threshold;                /* this carrier's rx threshold (cfg->threshold is not used) */
+    uint32_t reserved[5];           /* zero                                     */
+} ookd_rx_carrier;
+ookd_rx *ookd_rx_create_carriers(const ookd_rx_config *cfg, const ookd_filter *filter,
+                                 const ookd_device *device,
+                                 const ookd_rx_carrier *carriers, uint32_t num_carriers);
+uint32_t ookd_rx_num_carriers(const ookd_rx *rx);   /* 0 for every other context */
+int ookd_rx_get_carrier(const ookd_rx *rx, uint32_t k, ookd_rx_carrier *out);
+/* ookd_rx_get_front_info with carrier k's p_star, band and err_valu */
+int ookd_rx_get_carrier_front_info(const ookd_rx *rx, uint32_t k, ookd_front_info *out);
 void ookd_rx_destroy(ookd_rx *rx);
 /* Bytes per input sample of this context: 4 (SC16Q11) or 2 (CS8 / CU8).  Everywhere below a sample
  * count, stride or halo length counts samples of that size, and a pointer to samples is a pointer

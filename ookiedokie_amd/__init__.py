@@ -67,6 +67,8 @@ FRONT_FIR1_MFMA_8 = 10
 FRONT_FIR2_MFMA_8 = 11
 FRONT_TUNED_GENERIC = 12                # a tuned context (Receiver(tune=...)): any shape, the contract's order
 FRONT_TUNED_FIR1 = 13                   # ... 1 stage, decimation 1, <= 256 taps: packed FMAs + guard band
+FRONT_TUNED_MULTI = 14                  # a carrier context (Receiver(carriers=[...])): that shape, all carriers in one pass
+RX_MAX_CARRIERS = 16
 SURVEY_GENERIC = 1                      # survey forms (Survey.form): OOKD_SURVEY_*; what an untuned Survey runs
 SURVEY_TUNED_GENERIC = 2                # a tuned Survey (Survey(tune=...)): any shape, the contract's order
 SURVEY_TUNED_FIR1 = 3                   # ... 1 stage, decimation 1, <= 256 taps: register-blocked, same histogram
@@ -161,6 +163,10 @@ class Tune(C.Structure):
     _fields_ = [("nu", C.c_double), ("reserved", C.c_uint64 * 3)]
 
 
+class RxCarrier(C.Structure):
+    _fields_ = [("nu", C.c_double), ("threshold", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [
         ("seed", C.c_uint64), ("sample_rate", C.c_uint32), ("amplitude", C.c_uint32),
@@ -231,6 +237,11 @@ _PROTOTYPES = {
     "ookd_rx_create": (C.c_void_p, [C.POINTER(RxConfig), C.c_void_p, C.c_void_p]),
     "ookd_rx_create_tuned": (C.c_void_p, [C.POINTER(RxConfig), C.c_void_p, C.c_void_p, C.POINTER(Tune)]),
     "ookd_rx_tune": (C.c_double, [C.c_void_p]),
+    "ookd_rx_create_carriers": (C.c_void_p, [C.POINTER(RxConfig), C.c_void_p, C.c_void_p, C.POINTER(RxCarrier),
+                                             C.c_uint32]),
+    "ookd_rx_num_carriers": (C.c_uint32, [C.c_void_p]),
+    "ookd_rx_get_carrier": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RxCarrier)]),
+    "ookd_rx_get_carrier_front_info": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(FrontInfo)]),
     "ookd_rx_destroy": (None, [C.c_void_p]),
     "ookd_rx_sample_bytes": (C.c_uint32, [C.c_void_p]),
     "ookd_rx_process_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
@@ -647,10 +658,18 @@ class Receiver:
                  front_gate: Optional["FrontGate"] = None, fir_valu: bool = False,
                  scan_tables: bool = False, sample_format: str = "sc16q11",
                  tune: Optional[float] = None, tune_hz: Optional[float] = None,
-                 sample_rate: Optional[float] = None):
+                 sample_rate: Optional[float] = None,
+                 carriers: Optional[Sequence] = None):
         """tune: carrier offset in cycles per input sample (|tune| <= 0.5), or tune_hz with sample_rate -- one
         of the two forms.  The context then filters with the taps `Filter.tuned_taps` returns (ookd_rx_create_tuned);
-        0 is an untuned context."""
+        0 is an untuned context.
+
+        carriers: several carriers of ONE capture decoded in one pass (ookd_rx_create_carriers): entries are `nu`
+        (cycles per input sample, with this receiver's `threshold`) or `(nu, threshold)`.  Not together with tune /
+        tune_hz.  Such a context runs one capture per run; wherever a method takes a capture index it takes the
+        carrier index, and a result's `captures` field holds each message's carrier."""
+        if carriers is not None and (tune is not None or tune_hz is not None):
+            raise ValueError("carriers and tune / tune_hz are mutually exclusive: a carrier list names every nu")
         if tune is not None and (tune_hz is not None or sample_rate is not None):
             raise ValueError("give either tune (cycles per sample) or tune_hz with sample_rate, not both")
         if (tune_hz is None) != (sample_rate is None):
@@ -685,7 +704,17 @@ class Receiver:
         self._filter, self._device = filt, device
         self.payload_bytes = device.payload_bytes if device else 0
         self.total_decimation = filt.total_decimation if filt else 1
-        if tune is None:
+        if carriers is not None:
+            entries = []
+            for c in carriers:
+                nu, thr = c if isinstance(c, (tuple, list)) else (c, threshold)
+                entries.append((float(nu), float(thr)))
+            arr = (RxCarrier * max(len(entries), 1))()
+            for k, (nu, thr) in enumerate(entries):
+                arr[k].nu, arr[k].threshold = nu, thr
+            self._h = lib().ookd_rx_create_carriers(C.byref(cfg), filt._h if filt else None,
+                                                    device._h if device else None, arr, len(entries))
+        elif tune is None:
             self._h = lib().ookd_rx_create(C.byref(cfg), filt._h if filt else None,
                                            device._h if device else None)
         else:
@@ -700,6 +729,23 @@ class Receiver:
     def tune(self) -> float:
         """Carrier offset this context is tuned to, cycles per input sample (0: untuned)."""
         return float(lib().ookd_rx_tune(self._h))
+
+    @property
+    def num_carriers(self) -> int:
+        """Carriers of a carrier context (Receiver(carriers=[...])), 0 for every other context."""
+        return int(lib().ookd_rx_num_carriers(self._h))
+
+    def carrier(self, k: int) -> Tuple[float, float]:
+        """(nu, threshold) of carrier k."""
+        c = RxCarrier()
+        _check(lib().ookd_rx_get_carrier(self._h, k, C.byref(c)))
+        return float(c.nu), float(c.threshold)
+
+    def carrier_front_info(self, k: int) -> dict:
+        """`front_info` with carrier k's p_star, guard band and err_valu."""
+        f = FrontInfo()
+        _check(lib().ookd_rx_get_carrier_front_info(self._h, k, C.byref(f)))
+        return {name: getattr(f, name) for name, _ in FrontInfo._fields_}
 
     # -- runs ---------------------------------------------------------------
     def rx_device(self, d_iq_ptr: int, samples_per_capture: int, num_captures: int = 1,

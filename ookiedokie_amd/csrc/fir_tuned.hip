@@ -14,6 +14,8 @@
 //   fir1_tuned_kernel        : 1 stage, decimation 1, <= 256 taps (OOKD_FRONT_TUNED_FIR1): fused packed FMAs
 //                              (tuned_chunk<false, R>, front_dev.hpp), guard band and epilogue of fir1_tile_finish,
 //                              recompute in the contract's order
+//   fir1_tuned_multi_kernel  : the same shape for K carriers in one pass over the capture (OOKD_FRONT_TUNED_MULTI):
+//                              loads, quiet statistics and unpack once per tile, accumulation and epilogue per carrier
 //   fir_tuned_generic_kernel : the contract for every shape (OOKD_FRONT_TUNED_GENERIC)
 //
 // Compiled with -ffp-contract=off (see kernels.hip).
@@ -149,6 +151,170 @@ __global__ __launch_bounds__(64) void fir1_tuned_kernel(const FrontParams p) {
 }
 
 // ---------------------------------------------------------------------------
+// K carriers in one pass: fir1_tuned_kernel's tile with everything that does not depend on nu done once
+// ---------------------------------------------------------------------------
+// The three nu-independent steps of an interior window, as fir1_tuned_kernel spells them inline.  (That kernel keeps
+// its own text: with only its load and unpack rounds routed through these functions both of its listings came out
+// different -- same length, other instruction order and registers -- and its instruction stream is what
+// profiles/tuned_rate.json measured.  The statistics here also end in SGPRs, which its listing does not have.)
+template <int R, int ROUNDS>
+__device__ __forceinline__ void tuned_window_load(const uint4 *src4, uint32_t tid, uint32_t nvec, uint4 (&q)[ROUNDS]) {
+    constexpr uint32_t kTile = 64u * R;
+#pragma unroll
+    for (int i = 0; i < ROUNDS; ++i) {
+        const uint32_t v = tid + 64u * i;
+        // (a lane without a vector in this round repeats its first one: the quiet statistics take minima too)
+        q[i] = (64u * (i + 1) <= kTile / 4 || v < nvec) ? ld_nt4(src4 + v) : q[0];
+    }
+}
+
+// a = the larger component range, b = the larger |min + max| of the window (raw LSB), the same in every lane
+template <int ROUNDS>
+__device__ __forceinline__ void tuned_window_stats(const uint4 (&q)[ROUNDS], float &a, float &b) {
+    v2s mx = (v2s){-32768, -32768}, mn = (v2s){32767, 32767};
+#pragma unroll
+    for (int i = 0; i < ROUNDS; ++i) {
+        mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2s(q[i].x), as_v2s(q[i].y)));
+        mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2s(q[i].z), as_v2s(q[i].w)));
+        mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2s(q[i].x), as_v2s(q[i].y)));
+        mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2s(q[i].z), as_v2s(q[i].w)));
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        mx = __builtin_elementwise_max(mx, as_v2s(__shfl_xor(__builtin_bit_cast(uint32_t, mx), d)));
+        mn = __builtin_elementwise_min(mn, as_v2s(__shfl_xor(__builtin_bit_cast(uint32_t, mn), d)));
+    }
+    const int ri = (int)mx.x - (int)mn.x, rq = (int)mx.y - (int)mn.y;
+    const int si = abs((int)mx.x + (int)mn.x), sq = abs((int)mx.y + (int)mn.y);
+    // (every lane holds the same two numbers: one copy in SGPRs keeps the per-carrier tests off the vector unit's
+    //  divergence handling)
+    a = (float)__builtin_amdgcn_readfirstlane(max(ri, rq));
+    b = (float)__builtin_amdgcn_readfirstlane(max(si, sq));
+}
+
+template <int R, int ROUNDS>
+__device__ __forceinline__ void tuned_window_unpack(float2 *lds, uint32_t tid, uint32_t nvec, const uint4 (&q)[ROUNDS]) {
+    constexpr uint32_t kTile = 64u * R;
+#pragma unroll
+    for (int i = 0; i < ROUNDS; ++i) {
+        const uint32_t v = tid + 64u * i;
+        if (64u * (i + 1) <= kTile / 4 || v < nvec) store_unpacked<(int)kFmtSc16, R>(lds, v, q[i]);
+    }
+}
+
+// carrier k's table entry (wave-uniform, 32 bytes) -> SGPRs, as load_tap_chunk32 fetches the taps
+__device__ __forceinline__ TunedCarrierDev load_carrier(const TunedCarrierDev *tab, uint32_t k) {
+    static_assert(sizeof(TunedCarrierDev) == 32, "one s_load_dwordx8");
+    v8f e;
+    asm volatile("s_load_dwordx8 %0, %1, 0x0\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(e)
+                 : "s"(tab + k)
+                 : "memory");
+    TunedCarrierDev c;
+    c.tap_off = __builtin_bit_cast(uint32_t, e[0]);
+    c.p_star = e[1];
+    c.p_lo = e[2];
+    c.p_hi = e[3];
+    c.quiet_a = e[4];
+    c.quiet_b = e[5];
+    c.pad[0] = c.pad[1] = 0;
+    return c;
+}
+
+// One wavefront = one tile of 64 R outputs of EVERY carrier: the capture is read, tested and unpacked once, then the
+// chunk loop and the epilogue of fir1_tuned_kernel run once per carrier that is not quiet in this tile, on the same
+// LDS window and in the same accumulators.  Carrier k's bit words, tile infos and floats live where capture k's
+// would (the edge / state machine chain runs a batch of K); the grid is (tiles, 1).
+template <int R>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R == kFir1RShort ? 8 : 5)))
+void fir1_tuned_multi_kernel(const FrontParams p, const TunedCarrierDev *tab,
+                                                              const uint32_t K) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+
+    constexpr uint32_t kTile = 64u * R;                 // outputs per wavefront
+    constexpr int kRounds = (kTile + 256 + 255) / 256;  // 16 B loads per lane (taps <= 256)
+    static_assert(kTile / 4 >= 64, "the first load round is a full one");
+    const uint32_t tid = threadIdx.x & 63u;
+    const uint64_t tile = (uint64_t)blockIdx.x + p.tile_base;
+    const uint64_t t0 = tile * kTile;
+    const uint32_t Tp = p.stage[0].ntaps_pad;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(p.iq);
+    float2 *lds = reinterpret_cast<float2 *>(smem_raw);
+
+    // ---- load the wave's window: slot j <-> input index t0 - Tp + j ------------
+    const uint32_t nvec = (kTile + Tp) >> 2;
+    const bool aligned16 = ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool interior = aligned16 && t0 >= Tp && t0 + kTile <= p.n_valid;
+    uint32_t quiet = 0;                                 // bit k: carrier k cannot reach its threshold in this tile
+    if (interior) {
+        uint4 q[kRounds];
+        tuned_window_load<R>(reinterpret_cast<const uint4 *>(src + (t0 - Tp)), tid, nvec, q);
+        // ---- quiet test: fir1_tuned_kernel's bound, the window's statistics once, the weights per carrier ----
+        if (!p.fir_out && p.quiet_lsb > 0) {
+            float a, b;
+            tuned_window_stats(q, a, b);
+#pragma nounroll
+            for (uint32_t k = 0; k < K; ++k) {
+                const TunedCarrierDev c = load_carrier(tab, k);
+                if (a * c.quiet_a + b * c.quiet_b < 1.0f) {
+                    quiet |= 1u << k;
+                    // (sparse output: nothing is stored -- see fir1_bits_kernel)
+                    if (!p.sparse) {
+                        if (tid < kTile / 64) p.bits[(uint64_t)k * p.words_per_cap + (t0 >> 6) + tid] = 0;
+                        if (tid == 0) p.tile_info[(uint64_t)k * p.tiles_per_cap + tile] = 0;
+                    }
+                }
+            }
+            // (window, carrier) pairs that skipped the filter
+            if (quiet && p.quiet_count && tid == 0) atomicAdd(p.quiet_count + (blockIdx.x % kQuietCounters), (uint32_t)__popc(quiet));
+            if (quiet == (1u << K) - 1u) return;        // K <= 16
+        }
+        tuned_window_unpack<R>(lds, tid, nvec, q);
+    } else {
+        // first / last tiles of a capture, unaligned host pointers
+        for (uint32_t v = tid; v < nvec; v += 64) {
+            const int64_t n = (int64_t)t0 - (int64_t)Tp + 4 * (int64_t)v;
+            float2 *dst = lds + slot<R>(4 * v);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dst[i] = fetch_sample(p, src, nullptr, n + i);
+        }
+    }
+    // the window is private to this wavefront and the LDS executes one wave's accesses in order; from here on it
+    // is only read
+    wave_lds_fence();
+
+    const uint32_t nchunks = Tp / kTunedChunk;
+#pragma nounroll
+    for (uint32_t k = 0; k < K; ++k) {
+        if ((quiet >> k) & 1u) continue;
+        const TunedCarrierDev c = load_carrier(tab, k);
+        const float *ctaps = p.ctaps + c.tap_off;
+        // ---- accumulate: fir1_tuned_kernel's chunk loop on this carrier's taps ----
+        v2f acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = (v2f){0.0f, 0.0f};
+        for (uint32_t ch = 0; ch < nchunks; ++ch) {
+            v2f tpair[16];
+            load_tap_chunk32(ctaps + 2u * ch * kTunedChunk, tpair);
+            const uint32_t m = nchunks - 1 - ch;
+            const v2f *base = reinterpret_cast<const v2f *>(lds + (uint32_t)(R + 1) * tid + (16u + 16u / R) * m);
+            tuned_chunk<false, R>(acc, tpair, base, std::make_integer_sequence<int, R + kTunedChunk - 1>{});
+        }
+        // ---- its own band, bit words, float plane and tile info ----
+        FrontParams pk = p;
+        pk.p_star = c.p_star;
+        pk.p_lo = c.p_lo;
+        pk.p_hi = c.p_hi;
+        uint64_t *words = p.bits + (uint64_t)k * p.words_per_cap;
+        const uint32_t info = fir1_tile_finish<false, R>(pk, acc, t0, tid, k, words, [&](uint32_t r) {
+            return fir1_tuned_exact_output<R>(lds, Tp + R * tid + r, ctaps, p.stage[0].ntaps);
+        });
+        if (tid == 0) p.tile_info[(uint64_t)k * p.tiles_per_cap + tile] = info;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // any shape, the contract's order throughout: fir_generic_kernel (kernels.hip) with complex taps
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fir_tuned_generic_kernel(const FrontParams p, uint32_t lds_b_off) {
@@ -240,6 +406,31 @@ hipError_t launch_front_tuned_fir1(const FrontParams &p, uint32_t num_captures, 
     hipError_t e = ensure_dynamic_lds(fn, lds);
     if (e != hipSuccess) return e;
     e = hipExtLaunchKernel(fn, dim3((uint32_t)grid, num_captures), dim3(64), args, lds, stream, t0, t1, 0);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_front_tuned_multi(const FrontParams &p, const TunedCarrierDev *carriers, uint32_t num_carriers,
+                                    hipStream_t stream, hipEvent_t t0, hipEvent_t t1, uint64_t tile_begin,
+                                    uint64_t tile_count) {
+    if (!front_uses_tuned_fir1(p) || p.sample_fmt != kFmtSc16 || p.halo || !carriers || num_carriers == 0 ||
+        num_carriers > kMaxCarriers) {
+        return hipErrorInvalidValue;
+    }
+    const int R = tuned_R(p);
+    // whole 4096-output blocks, so every bit word of every carrier is written
+    const uint64_t all = (p.n_out + kFirTile - 1) / kFirTile * (kFirTile / (64 * R));
+    const uint64_t b = tile_begin < all ? tile_begin : all;
+    const uint64_t grid = tile_count < all - b ? tile_count : all - b;
+    if (grid == 0) return hipSuccess;
+    FrontParams pp = p;
+    pp.tile_base = (uint32_t)b;
+    void *args[] = {&pp, &carriers, &num_carriers};
+    const void *fn = R == kFir1RShort ? reinterpret_cast<const void *>(&fir1_tuned_multi_kernel<kFir1RShort>)
+                                      : reinterpret_cast<const void *>(&fir1_tuned_multi_kernel<kFir1RLong>);
+    const size_t lds = tuned_lds_bytes(p);
+    hipError_t e = ensure_dynamic_lds(fn, lds);
+    if (e != hipSuccess) return e;
+    e = hipExtLaunchKernel(fn, dim3((uint32_t)grid, 1), dim3(64), args, lds, stream, t0, t1, 0);
     return e != hipSuccess ? e : hipGetLastError();
 }
 

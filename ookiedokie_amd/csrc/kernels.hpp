@@ -189,6 +189,21 @@ uint32_t tuned_fir1_tile_bits(const FrontParams &p);
 hipError_t launch_front_tuned_fir1(const FrontParams &p, uint32_t num_captures, hipStream_t stream, hipEvent_t t0,
                                    hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count);
 hipError_t launch_front_tuned_generic(const FrontParams &p, uint32_t num_captures, hipStream_t stream);
+// Several carriers in one pass over ONE capture (fir1_tuned_multi_kernel; the shape front_uses_tuned_fir1 takes, no
+// halo).  What depends on the carrier travels in a table beside FrontParams (whose p_star / p_lo / p_hi / quiet_a /
+// quiet_b are not read): carrier k's taps at p.ctaps + tap_off, its results where capture k's would be
+// (p.bits + k words_per_cap, p.tile_info + k tiles_per_cap, p.fir_out + 2 k n_out).  p.quiet_lsb > 0: the small tile
+// and the quiet test; a carrier without a test carries infinite weights.
+constexpr uint32_t kMaxCarriers = 16;   // OOKD_RX_MAX_CARRIERS
+struct TunedCarrierDev {
+    uint32_t tap_off;           // floats from FrontParams::ctaps to this carrier's (re, im) pairs of stage 0
+    float p_star, p_lo, p_hi;   // its threshold and guard band
+    float quiet_a, quiet_b;     // its quiet weights (setup_tuned_quiet)
+    uint32_t pad[2];
+};
+hipError_t launch_front_tuned_multi(const FrontParams &p, const TunedCarrierDev *carriers, uint32_t num_carriers,
+                                    hipStream_t stream, hipEvent_t t0, hipEvent_t t1, uint64_t tile_begin,
+                                    uint64_t tile_count);
 // Generic multi-stage kernel regardless of shape (cross-check / streaming FIR).
 hipError_t launch_front_generic(const FrontParams &p, uint32_t num_captures,
                                 hipStream_t stream);

@@ -374,6 +374,23 @@ struct ookd_rx : RxHandles {
     double tune_nu = 0.0;
     DevBuf<float> d_ctaps;
     float quiet_a = 0, quiet_b = 0;
+    // carrier context (ookd_rx_create_carriers): K carriers of ONE capture, their results where the K captures of a
+    // batched run would be (run_caps == K behind the front end).  d_ctaps holds every carrier's taps one after the
+    // other, carrier k's image (setup_tuned's layout) at tap_off floats; d_carriers is the fused kernel's table.
+    struct Carrier {
+        double nu = 0.0;
+        float threshold = 0, p_star = 0, p_lo = 0, p_hi = 0, quiet_a = INFINITY, quiet_b = INFINITY;
+        double err_valu = 0.0;
+        uint32_t tap_off = 0;
+    };
+    std::vector<Carrier> carriers;
+    DevBuf<TunedCarrierDev> d_carriers;
+    // what a run reports for front_form()'s number: a carrier context's fused form has its own
+    uint32_t reported_form(uint32_t form) const {
+        if (carriers.empty()) return form;
+        return form == OOKD_FRONT_TUNED_FIR1 ? (uint32_t)OOKD_FRONT_TUNED_MULTI : (uint32_t)OOKD_FRONT_TUNED_GENERIC;
+    }
+    hipError_t launch_carriers(const FrontParams &fp, hipEvent_t t0, hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count);
     uint32_t tile_bits = 0;         // bits per wave tile of the front-end kernel (front_tile_bits), 0 = generic kernel
     bool exact = false;
     bool count_quiet = false;
@@ -555,7 +572,7 @@ struct ookd_rx : RxHandles {
         p.sparse = sparse ? 1u : 0u;
         p.stamp_bits = tile_stamp << kTileStampShift;
         p.sample_fmt = sample_fmt;
-        p.tune = tune_nu != 0.0 ? (exact ? 2u : 1u) : 0u;
+        p.tune = (tune_nu != 0.0 || !carriers.empty()) ? (exact ? 2u : 1u) : 0u;
         p.ctaps = d_ctaps.p;
         p.quiet_a = quiet_a;
         p.quiet_b = quiet_b;
@@ -676,11 +693,13 @@ int ookd_rx::widen_for_form(FrontParams &fp, uint32_t form) {
         form == OOKD_FRONT_FIR2_MFMA_8) {
         return OOKD_OK;
     }
+    // (a carrier context reads one capture whatever its carrier count: one staging copy)
+    const bool one = !carriers.empty();
     if (!d_widen.p) {
-        const int rc = d_widen.alloc(2 * (size_t)max_samples * max_captures + 8);
+        const int rc = d_widen.alloc(2 * (size_t)max_samples * (one ? 1u : max_captures) + 8);
         if (rc != OOKD_OK) return rc;
     }
-    HIPCHK(launch_widen(fp.iq, fp.sample_fmt, d_widen.p, run_n_valid, run_caps, fp.cap_stride, run_n_valid, stream));
+    HIPCHK(launch_widen(fp.iq, fp.sample_fmt, d_widen.p, run_n_valid, one ? 1u : run_caps, fp.cap_stride, run_n_valid, stream));
     fp.iq = d_widen.p;
     fp.cap_stride = run_n_valid;
     if (fp.halo && fp.halo_len) {
@@ -880,6 +899,29 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     return OOKD_OK;
 }
 
+// The front end of a carrier context: the fused kernel for all carriers (OOKD_FRONT_TUNED_MULTI), or the generic
+// tuned kernel once per carrier, each launch with that carrier's taps, threshold and result planes.
+hipError_t ookd_rx::launch_carriers(const FrontParams &fp, hipEvent_t t0, hipEvent_t t1, uint64_t tile_begin,
+                                    uint64_t tile_count) {
+    const uint32_t K = (uint32_t)carriers.size();
+    if (fp.n_out != 0 && run_form == OOKD_FRONT_TUNED_MULTI) {
+        return launch_front_tuned_multi(fp, d_carriers.p, K, stream, t0, t1, tile_begin, tile_count);
+    }
+    if (tile_begin != 0 || tile_count != ~0ull) return hipErrorInvalidValue;    // the generic kernel runs whole captures
+    if (t0 && hipEventRecord(t0, stream) != hipSuccess) return hipGetLastError();
+    for (uint32_t k = 0; k < K && fp.n_out != 0; ++k) {
+        FrontParams pk = fp;
+        pk.ctaps = d_ctaps.p + carriers[k].tap_off;
+        pk.p_star = carriers[k].p_star;
+        pk.bits = fp.bits + (size_t)k * run_words;
+        if (fp.fir_out) pk.fir_out = fp.fir_out + 2 * (size_t)k * run_n_out;
+        const hipError_t e = launch_front_tuned_generic(pk, 1, stream);
+        if (e != hipSuccess) return e;
+    }
+    if (t1 && hipEventRecord(t1, stream) != hipSuccess) return hipGetLastError();
+    return hipSuccess;
+}
+
 int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d_halo_ptr,
                              uint32_t halo_len) {
     if (hdr_dirty) HIPCHK(hipMemsetAsync(d_hdr.p, 0, sizeof(ResultHeader), stream));
@@ -887,9 +929,9 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
     FrontParams fp = front_params(d_iq, stride);
     fp.halo = d_halo_ptr;
     fp.halo_len = halo_len;
-    run_form = front_form(fp, exact);
+    run_form = reported_form(front_form(fp, exact));
     {
-        int rc = widen_for_form(fp, run_form);
+        int rc = widen_for_form(fp, front_form(fp, exact));
         if (rc == OOKD_OK) rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
     }
@@ -900,15 +942,20 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
     // and once dispatched they run beside the next launch.  ev[0] / ev[1] = start of the first,
     // end of the last launch.
     const uint64_t tiles = tile_bits ? (uint64_t)fp.tiles_per_cap : 0;
-    const uint64_t per = tile_bits ? std::max<uint64_t>(1, front_launch_outputs / tile_bits / std::max(1u, run_caps)) : 0;
+    // (a carrier context's grid covers the one capture it reads, whatever its carrier count)
+    const uint32_t read_caps = carriers.empty() ? run_caps : 1u;
+    const uint64_t per = tile_bits ? std::max<uint64_t>(1, front_launch_outputs / tile_bits / std::max(1u, read_caps)) : 0;
+    auto launch_range = [&](hipEvent_t e0, hipEvent_t e1, uint64_t t, uint64_t n) -> hipError_t {
+        if (!carriers.empty()) return launch_carriers(fp, e0, e1, t, n);
+        return launch_front(fp, run_caps, exact, stream, e0, e1, t, n);
+    };
     auto launch_all = [&]() -> hipError_t {
         front_launches = 1;
-        if (!tile_bits || tiles <= per + per / 2) return launch_front(fp, run_caps, exact, stream, ev[0], ev[1]);
+        if (!tile_bits || tiles <= per + per / 2) return launch_range(ev[0], ev[1], 0, ~0ull);
         front_launches = (uint32_t)((tiles + per - 1) / per);
         for (uint64_t t = 0; t < tiles; t += per) {
             const bool first = t == 0, last = t + per >= tiles;
-            const hipError_t e = launch_front(fp, run_caps, exact, stream, first ? ev[0] : nullptr,
-                                              last ? ev[1] : nullptr, t, per);
+            const hipError_t e = launch_range(first ? ev[0] : nullptr, last ? ev[1] : nullptr, t, per);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -1576,8 +1623,9 @@ double tuned_guard_error(const std::vector<std::vector<float>> &re, const std::v
 //     sqrt(2) / (2 * 2048) * ((A + e) a + (G + e) b) < 0.999 thr,      e = 1.01 (2T + 1) u S,
 // the 0.1 % covering the power's own three roundings and this test's float evaluation.  Only interior windows
 // are tested (every sample a capture sample), and only the 1-stage kernel has the test.
-void setup_tuned_quiet(ookd_rx &rx, const std::vector<float> &re, const std::vector<float> &im, const ookd_rx_config &cfg) {
-    if (!(cfg.threshold > 0.0f) || !std::isfinite(cfg.threshold) || (cfg.flags & OOKD_RX_NO_QUIET_SKIP)) return;
+bool tuned_quiet_weights(const std::vector<float> &re, const std::vector<float> &im, float threshold, uint32_t flags,
+                         float &quiet_a, float &quiet_b) {
+    if (!(threshold > 0.0f) || !std::isfinite(threshold) || (flags & OOKD_RX_NO_QUIET_SKIP)) return false;
     double A = 0.0, S = 0.0, gr = 0.0, gi = 0.0;
     for (size_t k = 0; k < re.size(); ++k) {
         A += std::hypot((double)re[k], (double)im[k]);
@@ -1585,26 +1633,30 @@ void setup_tuned_quiet(ookd_rx &rx, const std::vector<float> &re, const std::vec
         gr += (double)re[k];
         gi += (double)im[k];
     }
-    if (!(A > 0.0)) return;
+    if (!(A > 0.0)) return false;
     const double G = std::hypot(gr, gi) + 1e-12 * S;        // (the double sums' own rounding)
     const double e = 1.01 * (2.0 * (double)re.size() + 1.0) * std::ldexp(1.0, -24) * S;
-    const double scale = 1.41421356237309515 / (2.0 * 2048.0) / (0.999 * (double)cfg.threshold);
+    const double scale = 1.41421356237309515 / (2.0 * 2048.0) / (0.999 * (double)threshold);
     const double qa = (A + e) * scale, qb = (G + e) * scale;
-    if (!(qa < 1e30) || !(qb < 1e30)) return;
-    rx.quiet_a = nextafterf((float)qa, INFINITY);
-    rx.quiet_b = nextafterf((float)qb, INFINITY);
-    rx.quiet_lsb = 1;       // "the shortcut applies": the tuned kernel tests with quiet_a / quiet_b
+    if (!(qa < 1e30) || !(qb < 1e30)) return false;
+    quiet_a = nextafterf((float)qa, INFINITY);
+    quiet_b = nextafterf((float)qb, INFINITY);
+    return true;
 }
 
-bool setup_tuned(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg) {
+// Host side of one carrier at c.nu with c.threshold / c.p_star: its taps in the device layout (stage s at
+// 2 * tap_off, zero padded to ntaps_pad pairs) and, unless the context computes in the contract's order throughout,
+// its forward bound, guard band and quiet weights.  -> the quiet test applies to this carrier
+bool tuned_carrier_host(const ookd_rx &rx, const ookd_filter &filter, uint32_t flags, std::vector<float> &dev,
+                        ookd_rx::Carrier &c) {
     std::vector<std::vector<float>> re, im;
-    std::vector<float> dev;
+    dev.clear();
     uint64_t before = 1;
     for (uint32_t s = 0; s < rx.num_stages; ++s) {
         const std::vector<float> &h = filter.stages[s].taps;
         re.emplace_back(h.size());
         im.emplace_back(h.size());
-        tuned_stage_taps(h, rx.tune_nu, before, re[s].data(), im[s].data());
+        tuned_stage_taps(h, c.nu, before, re[s].data(), im[s].data());
         before *= filter.stages[s].decimation;
         // zero padding keeps sums bit-identical, as in setup_filter
         dev.resize(2 * (size_t)(rx.stage[s].tap_off + rx.stage[s].ntaps_pad), 0.0f);
@@ -1613,17 +1665,78 @@ bool setup_tuned(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &c
             dev[2 * (rx.stage[s].tap_off + k) + 1] = im[s][k];
         }
     }
+    if (rx.exact) return false;
+    c.err_valu = tuned_guard_error(re, im, 16.0);
+    band_from_error(c.err_valu, c.p_star, c.p_lo, c.p_hi);
+    // (the shape front_uses_tuned_fir1 takes: the only tuned kernels with a quiet test)
+    return rx.num_stages == 1 && rx.stage[0].decim == 1 && rx.stage[0].ntaps_pad <= 256u &&
+           tuned_quiet_weights(re[0], im[0], c.threshold, flags, c.quiet_a, c.quiet_b);
+}
+
+bool upload_ctaps(ookd_rx &rx, const std::vector<float> &dev) {
     if (rx.d_ctaps.alloc(dev.size()) != OOKD_OK) return false;
     if (hipMemcpy(rx.d_ctaps.p, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("tuned tap upload failed");
         return false;
     }
-    if (!rx.exact) {
-        rx.err_valu = tuned_guard_error(re, im, 16.0);
-        band_from_error(rx.err_valu, rx.p_star, rx.p_lo, rx.p_hi);
-        // (the shape front_uses_tuned_fir1 takes: the only tuned kernel with a quiet test)
-        if (rx.num_stages == 1 && rx.stage[0].decim == 1 && rx.stage[0].ntaps_pad <= 256u) setup_tuned_quiet(rx, re[0], im[0], cfg);
+    return true;
+}
+
+bool setup_tuned(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg) {
+    ookd_rx::Carrier c;
+    c.nu = rx.tune_nu;
+    c.threshold = cfg.threshold;
+    c.p_star = c.p_lo = c.p_hi = rx.p_star;
+    std::vector<float> dev;
+    const bool quiet = tuned_carrier_host(rx, filter, cfg.flags, dev, c);
+    if (!upload_ctaps(rx, dev)) return false;
+    rx.err_valu = c.err_valu;
+    rx.p_lo = c.p_lo;
+    rx.p_hi = c.p_hi;
+    if (quiet) {
+        rx.quiet_a = c.quiet_a;
+        rx.quiet_b = c.quiet_b;
+        rx.quiet_lsb = 1;       // "the shortcut applies": the tuned kernel tests with quiet_a / quiet_b
     }
+    return true;
+}
+
+// A carrier context's front end: setup_tuned per carrier, the taps behind one another, the fused kernel's table.
+bool setup_carriers(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg, const ookd_rx_carrier *in,
+                    uint32_t num_carriers) {
+    std::vector<float> all, dev;
+    std::vector<TunedCarrierDev> tab(num_carriers);
+    for (uint32_t k = 0; k < num_carriers; ++k) {
+        ookd_rx::Carrier c;
+        c.nu = in[k].nu == 0.0 ? 0.0 : in[k].nu;
+        c.threshold = in[k].threshold;
+        c.p_star = c.p_lo = c.p_hi = power_threshold(c.threshold);
+        // (a carrier without a quiet test keeps its infinite weights: never quiet)
+        if (tuned_carrier_host(rx, filter, cfg.flags, dev, c)) rx.quiet_lsb = 1;
+        else c.quiet_a = c.quiet_b = INFINITY;
+        c.tap_off = (uint32_t)all.size();
+        all.insert(all.end(), dev.begin(), dev.end());
+        TunedCarrierDev &t = tab[k];
+        t = TunedCarrierDev{};
+        t.tap_off = c.tap_off;
+        t.p_star = c.p_star;
+        t.p_lo = c.p_lo;
+        t.p_hi = c.p_hi;
+        t.quiet_a = c.quiet_a;
+        t.quiet_b = c.quiet_b;
+        rx.carriers.push_back(c);
+    }
+    if (!upload_ctaps(rx, all)) return false;
+    if (rx.d_carriers.alloc(tab.size()) != OOKD_OK) return false;
+    if (hipMemcpy(rx.d_carriers.p, tab.data(), tab.size() * sizeof(TunedCarrierDev), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("carrier table upload failed");
+        return false;
+    }
+    // what ookd_rx_get_front_info reports: carrier 0's (every carrier's: ookd_rx_get_carrier_front_info)
+    rx.p_star = rx.carriers[0].p_star;
+    rx.p_lo = rx.carriers[0].p_lo;
+    rx.p_hi = rx.carriers[0].p_hi;
+    rx.err_valu = rx.carriers[0].err_valu;
     return true;
 }
 
@@ -1893,7 +2006,7 @@ bool setup_pipeline(ookd_rx &rx, const ookd_rx_config &cfg) {
     uint64_t want = cfg.pipeline_chunk_samples;
     if (!want && dev_getenv("OOKD_PIPELINE")) want = kPipeDefaultChunk;
     rx.pipe_chunk_in = want ? want : kPipeDefaultChunk;
-    rx.pipe_ok = want != 0 && rx.have_fsm && rx.scan_ok && rx.tile_bits != 0 && !(cfg.flags & OOKD_RX_NO_PIPELINE) &&
+    rx.pipe_ok = want != 0 && rx.carriers.empty() && rx.have_fsm && rx.scan_ok && rx.tile_bits != 0 && !(cfg.flags & OOKD_RX_NO_PIPELINE) &&
                  cfg.pipeline_chunk_samples != ~0ull && !dev_getenv("OOKD_NO_PIPELINE") &&
                  rx.max_n_out >= 2 * (rx.pipe_chunk_in / rx.total_decim);
     if (!rx.pipe_ok) return true;
@@ -1940,10 +2053,9 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
 
 double ookd_rx_tune(const ookd_rx *rx) { return rx ? rx->tune_nu : 0.0; }
 
-ookd_rx *ookd_rx_create_tuned(const ookd_rx_config *cfg, const ookd_filter *filter,
-                              const ookd_device *device, const ookd_tune *tune) {
-    clear_error();
-    const double nu = tune ? tune->nu : 0.0;
+// the body of every create call: a context tuned to nu, or (num_carriers != 0) a carrier context
+static ookd_rx *create_context(const ookd_rx_config *cfg, const ookd_filter *filter, const ookd_device *device,
+                               double nu, const ookd_rx_carrier *carriers, uint32_t num_carriers) {
     if (!(std::fabs(nu) <= 0.5)) {
         set_error("ookd_rx_create_tuned: nu must be within [-0.5, 0.5] cycles per sample");
         return nullptr;
@@ -1993,14 +2105,17 @@ ookd_rx *ookd_rx_create_tuned(const ookd_rx_config *cfg, const ookd_filter *filt
         return nullptr;
     }
     rx->sample_fmt = (cfg->flags & OOKD_RX_SAMPLES_CS8) ? kFmtCs8 : (cfg->flags & OOKD_RX_SAMPLES_CU8) ? kFmtCu8 : kFmtSc16;
-    rx->max_captures = cfg->max_captures ? cfg->max_captures : 1;
+    // (a carrier context's results are those of a batch of num_carriers captures)
+    rx->max_captures = num_carriers ? num_carriers : cfg->max_captures ? cfg->max_captures : 1;
     rx->max_samples = cfg->max_samples;
 
     if (filter && !setup_filter(*rx, *filter)) return nullptr;
     rx->p_star = power_threshold(cfg->threshold);
     rx->p_lo = rx->p_hi = rx->p_star;
     rx->tune_nu = nu == 0.0 ? 0.0 : nu;
-    if (rx->tune_nu != 0.0) {
+    if (num_carriers) {
+        if (!setup_carriers(*rx, *filter, *cfg, carriers, num_carriers)) return nullptr;
+    } else if (rx->tune_nu != 0.0) {
         if (!setup_tuned(*rx, *filter, *cfg)) return nullptr;
     } else {
         if (filter && !rx->exact && !setup_front_form(*rx, *filter, cfg->flags)) return nullptr;
@@ -2015,6 +2130,58 @@ ookd_rx *ookd_rx_create_tuned(const ookd_rx_config *cfg, const ookd_filter *filt
     // (tests: start the tile stamp near its wrap-around)
     if (const char *e = dev_getenv("OOKD_TILE_STAMP_START")) rx->tile_stamp = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), kTileStampMax);
     return rx.release();
+}
+
+ookd_rx *ookd_rx_create_tuned(const ookd_rx_config *cfg, const ookd_filter *filter,
+                              const ookd_device *device, const ookd_tune *tune) {
+    clear_error();
+    return create_context(cfg, filter, device, tune ? tune->nu : 0.0, nullptr, 0);
+}
+
+ookd_rx *ookd_rx_create_carriers(const ookd_rx_config *cfg, const ookd_filter *filter, const ookd_device *device,
+                                 const ookd_rx_carrier *carriers, uint32_t num_carriers) {
+    clear_error();
+    if (!carriers || num_carriers == 0 || num_carriers > OOKD_RX_MAX_CARRIERS) {
+        set_error("ookd_rx_create_carriers: 1 to %d carriers, got %u%s", OOKD_RX_MAX_CARRIERS, num_carriers,
+                  carriers ? "" : " (carriers == NULL)");
+        return nullptr;
+    }
+    static_assert(OOKD_RX_MAX_CARRIERS == kMaxCarriers, "the fused kernel's carrier mask");
+    for (uint32_t k = 0; k < num_carriers; ++k) {
+        if (!(std::fabs(carriers[k].nu) <= 0.5)) {
+            set_error("ookd_rx_create_carriers: carrier %u: nu must be within [-0.5, 0.5] cycles per sample", k);
+            return nullptr;
+        }
+        for (uint32_t r : carriers[k].reserved) {
+            if (r) {
+                set_error("ookd_rx_create_carriers: carrier %u: reserved words must be zero", k);
+                return nullptr;
+            }
+        }
+    }
+    if (!filter) {
+        set_error("ookd_rx_create_carriers needs a filter: without one the slicer sees |x|, which does not depend on nu");
+        return nullptr;
+    }
+    if (cfg && cfg->max_captures > 1) {
+        set_error("ookd_rx_create_carriers: a carrier context runs one capture per run (max_captures = %u)", cfg->max_captures);
+        return nullptr;
+    }
+    return create_context(cfg, filter, device, 0.0, carriers, num_carriers);
+}
+
+uint32_t ookd_rx_num_carriers(const ookd_rx *rx) { return rx ? (uint32_t)rx->carriers.size() : 0u; }
+
+int ookd_rx_get_carrier(const ookd_rx *rx, uint32_t k, ookd_rx_carrier *out) {
+    clear_error();
+    if (!rx || !out || k >= rx->carriers.size()) {
+        set_error("ookd_rx_get_carrier: bad argument");
+        return OOKD_ERR_ARG;
+    }
+    *out = ookd_rx_carrier{};
+    out->nu = rx->carriers[k].nu;
+    out->threshold = rx->carriers[k].threshold;
+    return OOKD_OK;
 }
 
 void ookd_rx_destroy(ookd_rx *rx) { delete rx; }
@@ -2036,6 +2203,10 @@ int ookd_rx_submit_device(ookd_rx *rx, const void *d_iq, uint32_t num_captures,
         set_error("ookd_rx_submit_device: the previous run has not been waited for");
         return OOKD_ERR_ARG;
     }
+    if (!rx->carriers.empty() && num_captures != 1) {
+        set_error("a carrier context runs one capture per run (num_captures = %u)", num_captures);
+        return OOKD_ERR_ARG;
+    }
     if (num_captures == 0 || num_captures > rx->max_captures || samples_per_capture > rx->max_samples) {
         set_error("run of %u captures x %llu samples exceeds the context capacity (%u x %llu)",
                   num_captures, (unsigned long long)samples_per_capture, rx->max_captures,
@@ -2047,7 +2218,8 @@ int ookd_rx_submit_device(ookd_rx *rx, const void *d_iq, uint32_t num_captures,
         return OOKD_ERR_ARG;
     }
     HIPCHK(hipSetDevice(rx->dev));
-    rx->run_caps = num_captures;
+    // (behind the front end a carrier context's carriers are the captures of a batch)
+    rx->run_caps = rx->carriers.empty() ? num_captures : (uint32_t)rx->carriers.size();
     rx->run_n_valid = samples_per_capture;
     rx->geometry(samples_per_capture, true, rx->run_n_in, rx->run_n_out, rx->run_words,
                  rx->run_blocks, rx->run_segs_per_cap);
@@ -2247,6 +2419,10 @@ int ookd_rx_shard_begin(ookd_rx *rx, const void *d_iq, uint64_t num_samples, con
         set_error("ookd_rx_shard_begin: bad argument");
         return OOKD_ERR_ARG;
     }
+    if (!rx->carriers.empty()) {
+        set_error("ookd_rx_shard_begin: a carrier context runs whole captures, not shards");
+        return OOKD_ERR_ARG;
+    }
     const uint64_t spb = rx->cfg.samples_per_buffer;
     const uint64_t align = spb / gcd64(spb, rx->total_decim) * rx->total_decim;
     if (!last_shard && (num_samples % align) != 0) {
@@ -2300,6 +2476,10 @@ int ookd_rx_shard_refine(ookd_rx *rx, const ookd_fsm_state *state_in, ookd_fsm_s
         set_error("ookd_rx_shard_refine: null argument");
         return OOKD_ERR_ARG;
     }
+    if (!rx->carriers.empty()) {
+        set_error("ookd_rx_shard_refine: a carrier context runs whole captures, not shards");
+        return OOKD_ERR_ARG;
+    }
     HIPCHK(hipSetDevice(rx->dev));
     if (!rx->have_fsm || rx->run_n_out == 0) {
         if (state_out) *state_out = *state_in;
@@ -2342,7 +2522,7 @@ int ookd_rx_get_stats(const ookd_rx *rx, ookd_rx_stats *out) {
 int ookd_rx_get_front_info(const ookd_rx *rx, ookd_front_info *out) {
     if (!rx || !out) return OOKD_ERR_ARG;
     ookd_front_info f{};
-    f.form = front_form(rx->front_params(nullptr, 0), rx->exact);
+    f.form = rx->reported_form(front_form(rx->front_params(nullptr, 0), rx->exact));
     f.mfma_ksteps = rx->mfma_ksteps;
     f.p_star = rx->p_star;
     f.p_lo = rx->p_lo;
@@ -2353,6 +2533,22 @@ int ookd_rx_get_front_info(const ookd_rx *rx, ookd_front_info *out) {
     f.err_valu = rx->err_valu;
     f.mfma_delta = rx->mfma_delta;
     *out = f;
+    return OOKD_OK;
+}
+
+int ookd_rx_get_carrier_front_info(const ookd_rx *rx, uint32_t k, ookd_front_info *out) {
+    clear_error();
+    if (!rx || !out || k >= rx->carriers.size()) {
+        set_error("ookd_rx_get_carrier_front_info: bad argument");
+        return OOKD_ERR_ARG;
+    }
+    const int rc = ookd_rx_get_front_info(rx, out);
+    if (rc != OOKD_OK) return rc;
+    const ookd_rx::Carrier &c = rx->carriers[k];
+    out->p_star = c.p_star;
+    out->p_lo = c.p_lo;
+    out->p_hi = c.p_hi;
+    out->err_valu = c.err_valu;
     return OOKD_OK;
 }
 
