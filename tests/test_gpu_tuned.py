@@ -2,13 +2,13 @@
 numpy restatement of the contract (tests/tuned_contract.py; test_tuned_host.py pins it to the CPU oracle at nu = 0)
 fed with the library's own taps (Filter.tuned_taps), so bits -- and the floats of the contract-order form -- are
 compared exactly."""
-import json
 import zlib
 
 import numpy as np
 import pytest
 
 from tests.helpers import edges_of, golden_path
+from tests.tuned_bounds_inputs import rand_taps as _rand_taps, tight as _tight, write_filter as _write
 from tests.tuned_contract import RATE, SPB, THR, contract_rx, golden_capture, lib_stages, moved, to_8bit
 
 pytestmark = pytest.mark.gpu
@@ -26,18 +26,6 @@ def ok():
     import ookiedokie_amd as okm
     okm.lib()
     return okm
-
-
-def _write(tmp_path, name, stages):
-    p = tmp_path / (name + ".json")
-    p.write_text(json.dumps({"filter": {"stages": [{"decimation": int(d), "taps": [float(t) for t in taps]}
-                                                   for d, taps in stages]}}))
-    return str(p)
-
-
-def _rand_taps(n, seed, total=1.3):
-    h = np.random.default_rng(seed).normal(0, 1, n)
-    return (h / np.abs(h).sum() * total).astype(np.float32)
 
 
 def _fs32(ok):
@@ -175,36 +163,6 @@ def test_recovery_of_an_off_centre_carrier(ok, oracle, cap, nmsg, hz):
 
 
 # ---------------------------------------------------------------------------- 4. guard band ----
-
-def _tight(re, im, A, n_win, rng, cancel):
-    """windows whose products all have one sign in the real component (partial sums up to sum(|re| + |im|) A), or
-    whose second half cancels the first to a few per cent; one sample of each window moves by a few LSB so the
-    outputs spread over a few ulp around one magnitude.  -> capture, output indices of the windows"""
-    T = re.size
-    sr = np.where(re >= 0, 1, -1)
-    si = np.where(im >= 0, -1, 1)
-    w = np.abs(re.astype(np.float64)) + np.abs(im.astype(np.float64))
-    if cancel:
-        flip = np.cumsum(w) / w.sum() > 0.52
-        sr, si = np.where(flip, -sr, sr), np.where(flip, -si, si)
-    n = (n_win + 1) * (T + 1)
-    xr = rng.integers(-A // 4, A // 4 + 1, size=n)
-    xi = rng.integers(-A // 4, A // 4 + 1, size=n)
-    # the tap at which one LSB moves the output by about two float32 ulp of its magnitude
-    mag0 = np.hypot(np.sum(re * sr - im * si), np.sum(re * si + im * sr)) * A / 2048.0
-    kp = int(np.argmin(np.abs(w - 2048.0 * 2.0 ** -22 * mag0)))
-    outs = []
-    for i in range(n_win):
-        e = (i + 1) * (T + 1) - 1
-        k = np.arange(T)
-        xr[e - k] = sr * A
-        xi[e - k] = si * A
-        xr[e - kp] = sr[kp] * (A - 8) + rng.integers(-8, 9)
-        outs.append(e)
-    iq = np.empty(2 * n, np.int16)
-    iq[0::2], iq[1::2] = xr, xi
-    return iq, np.array(outs)
-
 
 @pytest.mark.parametrize("cancel", [False, True], ids=["aligned", "cancel"])
 @pytest.mark.parametrize("ntaps", [32, 255])
