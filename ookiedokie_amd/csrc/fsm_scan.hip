@@ -98,7 +98,7 @@ struct LTab {
 
 __host__ __device__ __forceinline__ uint32_t clamp32(uint64_t v) { return v == ~0ull ? kNone : (uint32_t)v; }
 
-// The tables are laid out once on the host (fsm_scan_fill_ltab): the kernels
+// The tables are laid out once on the host (build_scan_tables): the kernels
 // fetch the image with 16-byte loads.
 static_assert(sizeof(LTab) % 16 == 0, "LTab is copied in 16-byte pieces");
 __device__ __forceinline__ void copy_ltab(LTab &T, const void *g) {
@@ -516,7 +516,7 @@ struct ScanParams {
     // span tables (build_leaf_tables): packed result of a span as a function of its
     // length, per (row, level); null = simulate
     const uint32_t *lt_off, *lt_n0, *lt_pk;
-    const void *ltab;           // device copy of the LTab (fsm_scan_fill_ltab)
+    const void *ltab;           // device copy of the LTab (ScanTables::ltab)
     const uint16_t *reach;      // abstract codes a span can be entered in (from the span tables), or null = all
     uint32_t nreach, nreach_base;       // all of them / the normal, skip and poison codes among them (they come first)
     uint32_t nreach_lv[2];              // reach + nreach: the base codes met at level 0, then those met at level 1
@@ -576,6 +576,14 @@ constexpr uint32_t kPkRelative = 0x20000000u;   // [7:0] end state, [23:8] appen
 constexpr uint32_t kPkShared = 0x10000000u;     // transient: class "all bits" takes this result too
 constexpr uint32_t kPkStuck = 0x08000000u;      // no trigger fired on the edge, the counter runs on
 constexpr uint32_t kPkEventShift = 24;          // relative results: bits 24..25 = the span's events in short (pack_normal)
+// entry of the reach list (ScanTables::reach): a code and the levels it is met at
+constexpr uint32_t kReachCode = 0x3fffu;
+constexpr uint32_t kReachLevel0 = 0x4000u;      // << L: met at level L
+constexpr uint32_t kReachLevels = 0xc000u;      // met at either level
+// word of the rows in the form the sync walk steps through (append_sync_codes); 0 = not a plain result
+constexpr uint32_t kWalkPlain = 0x80000000u;    // [7:0] end state (S: skip / poison), [23:8] its bit count, ...
+constexpr uint32_t kWalkRelative = 0x40000000u; // ... or the bits appended to the entry's; [25:24] as kPkEventShift
+static_assert(kWalkPlain == 0x80000000u, "scan_syncwalk_kernel and scan_emit_kernel test this bit as the sign");
 
 __host__ __device__ __forceinline__ uint32_t pack_absolute(uint32_t code, uint32_t NB1) {
     return code | ((code / NB1) << 16) | kPkAbsolute;
@@ -626,6 +634,30 @@ __device__ __forceinline__ uint32_t lt_lookup(const uint32_t *off, const uint32_
         else hi = mid;
     }
     return pk[lo];
+}
+
+// the same search on the host (merged rows, self-check)
+uint32_t lt_lookup_host(const std::vector<uint32_t> &off, const std::vector<uint32_t> &n0, const std::vector<uint32_t> &pk,
+                        uint32_t row, uint32_t L, uint32_t n) {
+    uint32_t lo = off[2 * row + L], hi = off[2 * row + L + 1];
+    if (lo >= hi) return 0u;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (n0[mid] <= n) lo = mid;
+        else hi = mid;
+    }
+    return pk[lo];
+}
+
+// host: the code a span with packed result p ends in when entered with nb bits; kNone = no plain
+// end (stuck, bit-count sensitive, position dependent)
+uint32_t pk_end_code(uint32_t p, uint32_t nb, uint32_t NB1) {
+    if (p & kPkAbsolute) return p & 0xffffu;
+    if (p & kPkRelative) {
+        const uint32_t nbo = nb + ((p >> 8) & 0xffffu);
+        return (p & 0xffu) * NB1 + (nbo >= NB1 ? NB1 - 1 : nbo);
+    }
+    return kNone;
 }
 
 // ---- stuck codes (kStuckDepth) ---------------------------------------------------------
@@ -2569,7 +2601,7 @@ __global__ __launch_bounds__(256) void scan_syncwalk_kernel(ScanParams sp) {
                         q = plain ? q : 0u;
                         if ((int32_t)q < 0) {
                             // state' | bit count (absolute) or bits appended (relative) << 8
-                            nb = min(((q & 0x40000000u) ? nb : 0u) + ((q >> 8) & 0xffffu), NB1 - 1u);
+                            nb = min(((q & kWalkRelative) ? nb : 0u) + ((q >> 8) & 0xffffu), NB1 - 1u);
                             cur = q & 0xffu;
                         } else {
                             // skip codes: scan_sync_kernel's skip rows; stuck codes, rows that need a simulation: the full step
@@ -3472,19 +3504,6 @@ void row_candidates(const LTab &T, PSim f, uint32_t L, bool first_is_edge, std::
     }
 }
 
-}  // namespace
-
-size_t fsm_scan_ltab_bytes() { return sizeof(LTab); }
-
-uint32_t fsm_scan_fill_ltab(void *dst, const FsmTablesDev &g, uint32_t spb, uint32_t decim,
-                            const std::vector<uint16_t> &stuck_src, const std::vector<uint8_t> &stuck_rows) {
-    memset(dst, 0, sizeof(LTab));
-    LTab &T = *static_cast<LTab *>(dst);
-    fill_ltab_host(T, g, spb, decim);
-    add_stuck(T, stuck_src, stuck_rows);
-    return T.D;
-}
-
 // Abstract codes a span can be entered in, and with which level: closure of {reset at
 // level 0, skip x2, poison} under every result the span tables hold (any length).  Entries
 // that need a simulation add nothing: they are spans with an error before their last
@@ -3513,19 +3532,14 @@ static void reachable_codes(LTab &T, const std::vector<uint32_t> &off, const std
     auto follow = [&](uint32_t row, uint32_t L, uint32_t nb, uint32_t next) -> bool {
         bool any_stuck = false;
         for (uint32_t i = off[2 * row + L]; i < off[2 * row + L + 1]; ++i) {
-            const uint32_t v = pk[i];
-            uint32_t c = D0;
-            if (v & kPkAbsolute) {
-                c = v & 0xffffu;
-            } else if (v & kPkRelative) {
-                const uint32_t nbo = nb + ((v >> 8) & 0xffffu);
-                c = (v & 0xffu) * NB1 + (nbo >= NB1 ? NB1 - 1 : nbo);
+            const uint32_t v = pk[i], c = pk_end_code(v, nb, NB1);
+            if (c != kNone) {
+                add(c, next);
             } else if (v & kPkSensitive) {
                 unknown = true;
             } else if (v & kPkStuck) {
                 any_stuck = true;
             }
-            if (c < D0) add(c, next);
         }
         return any_stuck;
     };
@@ -3576,9 +3590,9 @@ static void reachable_codes(LTab &T, const std::vector<uint32_t> &off, const std
     }
     // entry = code | levels it is met at << 14 (bit 14: level 0, bit 15: level 1)
     for (uint32_t c = 0; c < D0; ++c) {
-        if (in[2 * c] || in[2 * c + 1]) reach.push_back((uint16_t)(c | (in[2 * c] ? 0x4000u : 0u) | (in[2 * c + 1] ? 0x8000u : 0u)));
+        if (in[2 * c] || in[2 * c + 1]) reach.push_back((uint16_t)(c | (in[2 * c] ? kReachLevel0 : 0u) | (in[2 * c + 1] ? kReachLevel0 << 1 : 0u)));
     }
-    for (uint32_t c = D0; c < T.D; ++c) reach.push_back((uint16_t)(c | 0xc000u));
+    for (uint32_t c = D0; c < T.D; ++c) reach.push_back((uint16_t)(c | kReachLevels));
 }
 
 bool build_leaf_tables(const FsmTablesDev &g, uint32_t spb, uint32_t decim, std::vector<uint32_t> &off,
@@ -3647,10 +3661,6 @@ bool build_leaf_tables(const FsmTablesDev &g, uint32_t spb, uint32_t decim, std:
     return true;
 }
 
-// ---------------------------------------------------------------------------
-// launcher
-// ---------------------------------------------------------------------------
-
 uint32_t fsm_scan_leaf_block(uint32_t D, uint32_t S, uint32_t SNB) {
     // 64 leaves per block: about one simulation task per lane, and the tables
     // (~35 KiB for the shipped devices) let several workgroups share a CU
@@ -3659,18 +3669,25 @@ uint32_t fsm_scan_leaf_block(uint32_t D, uint32_t S, uint32_t SNB) {
     return lb;
 }
 
+// the codes below `bound` that the reach list says are met at level L (empty list = unknown: all of them)
+std::vector<uint16_t> reach_codes_at(const std::vector<uint16_t> &reach, uint32_t L, uint32_t bound) {
+    std::vector<uint16_t> codes;
+    if (reach.empty()) {
+        for (uint32_t c = 0; c < bound; ++c) codes.push_back((uint16_t)c);
+    }
+    for (uint16_t v : reach) {
+        if ((v & kReachCode) < bound && (v & (kReachLevel0 << L))) codes.push_back((uint16_t)(v & kReachCode));
+    }
+    return codes;
+}
+
+// The span tables merged over the rows: per level the sorted union of all (state, class) rows' breakpoints,
+// and for every interval between two of them the 2S packed rows a span of that length has -- ONE search per
+// leaf, independent of the state the leaf is entered in.  Layout (32-bit words):
+//   [0] nbp level 0, [1] nbp level 1, [2] 2S, [3] 0 | bp level 0 | bp level 1 | rows level 0 [nbp0][2S] |
+//   rows level 1 [nbp1][2S]
 std::vector<uint32_t> build_merged_rows(uint32_t S, const std::vector<uint32_t> &off, const std::vector<uint32_t> &n0,
                                         const std::vector<uint32_t> &pk) {
-    auto lookup = [&](uint32_t row, uint32_t L, uint32_t n) -> uint32_t {      // lt_lookup
-        uint32_t lo = off[2 * row + L], hi = off[2 * row + L + 1];
-        if (lo >= hi) return 0u;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (n0[mid] <= n) lo = mid;
-            else hi = mid;
-        }
-        return pk[lo];
-    };
     std::vector<uint32_t> bp[2];
     for (uint32_t L = 0; L < 2; ++L) {
         bp[L].push_back(0);
@@ -3686,8 +3703,8 @@ std::vector<uint32_t> build_merged_rows(uint32_t S, const std::vector<uint32_t> 
         for (uint32_t n : bp[L]) {
             for (uint32_t k = 0; k < S; ++k) {
                 // (what the leaf kernels make of a leaf's two lookups: a shared class-0 result also stands for class 1)
-                const uint32_t p0 = lookup(2 * k, L, n);
-                const uint32_t p1 = (p0 & kPkShared) ? p0 : lookup(2 * k + 1, L, n);
+                const uint32_t p0 = lt_lookup_host(off, n0, pk, 2 * k, L, n);
+                const uint32_t p1 = (p0 & kPkShared) ? p0 : lt_lookup_host(off, n0, pk, 2 * k + 1, L, n);
                 out.push_back(p0 & ~kPkShared);
                 out.push_back(p1 & ~kPkShared);
             }
@@ -3710,15 +3727,7 @@ void append_sync_codes(std::vector<uint32_t> &merged, uint32_t S, uint32_t NB1, 
     if (merged.size() < 4) return;
     const uint32_t nbp[2] = {merged[0], merged[1]}, twoS = 2 * S, SNB = S * NB1;
     const uint32_t rows0 = 4 + nbp[0] + nbp[1];
-    std::vector<uint16_t> codes[2];
-    for (uint32_t L = 0; L < 2; ++L) {
-        if (reach.empty()) {
-            for (uint32_t c = 0; c < SNB; ++c) codes[L].push_back((uint16_t)c);
-        } else {
-            for (uint16_t v : reach)
-                if ((v & 0x3fffu) < SNB && (v & (0x4000u << L))) codes[L].push_back((uint16_t)(v & 0x3fffu));
-        }
-    }
+    const std::vector<uint16_t> codes[2] = {reach_codes_at(reach, 0, SNB), reach_codes_at(reach, 1, SNB)};
     std::vector<uint32_t> out;
     for (uint32_t L = 0; L < 2; ++L) {
         for (uint32_t z = 0; z < nbp[L]; ++z) {
@@ -3728,18 +3737,13 @@ void append_sync_codes(std::vector<uint32_t> &merged, uint32_t S, uint32_t NB1, 
             for (uint16_t c : codes[L]) {
                 const uint32_t cur = c / NB1, nb = c - cur * NB1;
                 const uint32_t p = row[2 * cur + (nb >= max_bits ? 1u : 0u)];
-                uint32_t end;
-                if (p & kPkAbsolute) {
-                    end = p & 0xffffu;
-                    if (end >= SNB + 2) ok = false;         // poison: not an exit the walk carries
-                } else if (p & kPkRelative) {
-                    const uint32_t nbo = nb + ((p >> 8) & 0xffffu);
-                    end = (p & 0xffu) * NB1 + (nbo >= NB1 ? NB1 - 1 : nbo);
-                } else {
+                const uint32_t end = pk_end_code(p, nb, NB1);
+                if (end == kNone) {
                     if (p & kPkStuck) stuckable = 1;
                     ok = false;                             // stuck, bit-count sensitive, position dependent
                     continue;
                 }
+                if (end >= SNB + 2) ok = false;             // poison: not an exit the walk carries
                 uint32_t j = 0;
                 while (j < n && img[j] != end) ++j;
                 if (j == n) {
@@ -3754,19 +3758,19 @@ void append_sync_codes(std::vector<uint32_t> &merged, uint32_t S, uint32_t NB1, 
     }
     // ... and the rows once more in the form the walk steps through (a state is kept as state / bit count, skip and
     // poison as state S with bit count 0 / 1 / 2): state' | (bit count or bits appended) << 8 | the span's events in
-    // short << 24 (pack_normal: what scan_emit_kernel writes without simulating) | relative << 30 | 0x80000000;
+    // short << 24 (pack_normal: what scan_emit_kernel writes without simulating) | kWalkRelative | kWalkPlain;
     // 0 = not a plain result (stuck, bit-count sensitive, position dependent): the full step
     std::vector<uint32_t> rows2;
     for (size_t i = rows0; i < merged.size(); ++i) {
         const uint32_t p = merged[i];
         uint32_t q = 0;
         if (p & kPkAbsolute) {
-            const uint32_t code = p & 0xffffu;
+            const uint32_t code = pk_end_code(p, 0u, NB1);      // (whatever the entry's bit count)
             const uint32_t cur = code < SNB ? code / NB1 : S, nb = code < SNB ? code - cur * NB1 : code - SNB;
-            if (code < SNB + 3) q = cur | (nb << 8) | 0x80000000u;
-        } else if (p & kPkRelative) {
+            if (code < SNB + 3) q = cur | (nb << 8) | kWalkPlain;
+        } else if (p & kPkRelative) {                           // (the bits appended, not an end code: the walk adds them)
             const uint32_t add = (p >> 8) & 0xffffu;
-            q = (p & 0xffu) | ((add > NB1 ? NB1 : add) << 8) | (((p >> kPkEventShift) & 3u) << 24) | 0x40000000u | 0x80000000u;
+            q = (p & 0xffu) | ((add > NB1 ? NB1 : add) << 8) | (((p >> kPkEventShift) & 3u) << 24) | kWalkRelative | kWalkPlain;
         }
         rows2.push_back(q);
     }
@@ -3774,6 +3778,99 @@ void append_sync_codes(std::vector<uint32_t> &merged, uint32_t S, uint32_t NB1, 
     merged.insert(merged.end(), out.begin(), out.end());
     merged.insert(merged.end(), rows2.begin(), rows2.end());
 }
+
+}  // namespace
+
+ScanTables build_scan_tables(const FsmTablesDev &g, uint32_t spb, uint32_t decim, bool with_spans) {
+    ScanTables t{};
+    t.spans_built = with_spans && build_leaf_tables(g, spb, decim, t.off, t.n0, t.pk, t.reach, t.stuck_src, t.stuck_rows);
+    if (!t.spans_built) t = ScanTables{};               // refused: what was built so far goes, the kernels simulate
+    t.S = g.num_states;
+    t.max_bits = g.max_bits;
+    t.NB1 = g.max_bits + 2;
+    t.SNB = t.S * t.NB1;
+    if (!t.reach.empty()) {
+        // for the composition of chunk tables, the codes met at level 0 and those met at level 1 as two
+        // plain lists (a chunk starts at one level: only that list is walked); the stuck codes stay out
+        for (uint32_t L = 0; L < 2; ++L) {
+            const std::vector<uint16_t> lv = reach_codes_at(t.reach, L, t.SNB + 3);
+            t.reach_lv[L] = (uint32_t)lv.size();
+            t.reach_by_level.insert(t.reach_by_level.end(), lv.begin(), lv.end());
+        }
+        for (uint16_t v : t.reach) t.reach_base += (v & kReachCode) < t.SNB + 3 ? 1u : 0u;
+    }
+    if (!t.n0.empty()) {
+        t.merged = build_merged_rows(t.S, t.off, t.n0, t.pk);
+        t.merged_rows_words = (uint32_t)t.merged.size();
+        append_sync_codes(t.merged, t.S, t.NB1, t.max_bits, t.reach);
+    }
+    t.ltab.assign((sizeof(LTab) + 15) / 16, make_uint4(0u, 0u, 0u, 0u));     // as the kernels fetch it (copy_ltab)
+    LTab &T = *reinterpret_cast<LTab *>(t.ltab.data());
+    fill_ltab_host(T, g, spb, decim);
+    add_stuck(T, t.stuck_src, t.stuck_rows);
+    t.D = T.D;
+    t.leaf_block = fsm_scan_leaf_block(t.D, t.S, t.SNB);
+    return t;
+}
+
+// The merged rows (one search per leaf for scan_entry_kernel) must say what the per-row searches say, at every
+// breakpoint, next to it and far beyond; the sync walk's second copy of the rows (append_sync_codes) must step every
+// normal code exactly as the rows do, and every interval's image must hold what its reachable codes end in.
+bool scan_tables_selfcheck(const ScanTables &t) {
+    if (!t.spans_built) return false;
+    if (t.n0.empty()) return true;
+    const std::vector<uint32_t> &m = t.merged;
+    const uint32_t S = t.S, NB1 = t.NB1, SNB = t.SNB, twoS = 2 * S;
+    const uint32_t nbp[2] = {m[0], m[1]}, rows0 = 4 + nbp[0] + nbp[1], sync_off = m[3];
+    const uint32_t rows2 = sync_off + 2 * (nbp[0] + nbp[1]);
+    if (sync_off != t.merged_rows_words || m.size() != rows2 + (size_t)(nbp[0] + nbp[1]) * twoS) return false;
+    std::vector<uint32_t> probes = {0u, 1u, 0xfffffff0u, 0x7fffffffu};
+    for (uint32_t v : t.n0) {
+        probes.push_back(v);
+        probes.push_back(v + 1);
+        if (v) probes.push_back(v - 1);
+    }
+    for (uint32_t L = 0; L < 2; ++L) {
+        const uint32_t *bp = m.data() + 4 + (L ? nbp[0] : 0u);
+        for (uint32_t n : probes) {
+            const uint32_t z = (uint32_t)(std::upper_bound(bp, bp + nbp[L], n) - bp) - 1u;     // bp[0] = 0
+            const uint32_t *rows = m.data() + rows0 + (size_t)((L ? nbp[0] : 0u) + z) * twoS;
+            for (uint32_t k = 0; k < S; ++k) {
+                const uint32_t p0 = lt_lookup_host(t.off, t.n0, t.pk, 2 * k, L, n);
+                const uint32_t p1 = (p0 & kPkShared) ? p0 : lt_lookup_host(t.off, t.n0, t.pk, 2 * k + 1, L, n);
+                if (rows[2 * k] != (p0 & ~kPkShared) || rows[2 * k + 1] != (p1 & ~kPkShared)) return false;
+            }
+        }
+    }
+    for (uint32_t L = 0; L < 2; ++L) {
+        std::vector<char> reachable(SNB, 0);
+        for (uint16_t c : reach_codes_at(t.reach, L, SNB)) reachable[c] = 1;
+        for (uint32_t z = 0; z < nbp[L]; ++z) {
+            const size_t iv = (L ? nbp[0] : 0u) + z, at = iv * twoS;
+            const uint32_t w0 = m[sync_off + 2 * iv], w1 = m[sync_off + 2 * iv + 1];
+            const uint32_t nimg = (w1 >> 16) & 0xfu, img[3] = {w0 & 0xffffu, w0 >> 16, w1 & 0xffffu};
+            for (uint32_t c = 0; c < SNB; ++c) {
+                const uint32_t cur = c / NB1, nb = c - cur * NB1, r = 2 * cur + (nb >= t.max_bits ? 1u : 0u);
+                const uint32_t want = pk_end_code(m[rows0 + at + r], nb, NB1), q = m[rows2 + at + r];
+                if (want == kNone || want >= SNB + 3) {
+                    if (q != 0) return false;
+                    continue;
+                }
+                if (!(q & kWalkPlain)) return false;
+                // as scan_syncwalk_kernel steps: state' (S: skip / poison), bit count or bits appended
+                const uint32_t nb2 = std::min(((q & kWalkRelative) ? nb : 0u) + ((q >> 8) & 0xffffu), NB1 - 1u), cur2 = q & 0xffu;
+                if ((cur2 < S ? cur2 * NB1 + nb2 : SNB + nb2) != want) return false;
+                // a reachable code's result is in the image (when the interval has one)
+                if (nimg && reachable[c] && want != img[0] && want != img[1] && want != img[2]) return false;
+            }
+        }
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// launcher
+// ---------------------------------------------------------------------------
 
 uint32_t fsm_scan_fin_block() { return (uint32_t)kFinBlock; }
 

@@ -377,14 +377,14 @@ struct FsmScanArgs {
     FsmParams f;                // tables, edges, geometry, msgs / totals
     uint32_t D, S;              // abstract states (with stuck codes), machine states
     uint32_t SNB;               // S * (max_bits + 2): the normal codes
-    uint32_t leaf_block;        // from fsm_scan_leaf_block()
+    uint32_t leaf_block;        // ScanTables::leaf_block
     uint32_t grid_blocks;       // persistent workgroups for the leaf / emit kernels
     uint16_t *block_tab;        // [total_blocks_cap][D rounded up to 8]
-    const uint32_t *lt_off, *lt_n0, *lt_pk;     // span tables from build_leaf_tables, or null
+    const uint32_t *lt_off, *lt_n0, *lt_pk;     // ScanTables::off / n0 / pk, or null
     uint32_t lt_words;          // their size in words (offsets + 2 x intervals)
-    const uint32_t *lt_merged;  // build_merged_rows of them, or null
+    const uint32_t *lt_merged;  // ScanTables::merged, or null
     uint32_t lt_merged_words;
-    const void *ltab;           // device copy of the kernels' table layout (fsm_scan_fill_ltab)
+    const void *ltab;           // device copy of ScanTables::ltab
     PublishParams publish;      // d_hdr != null: the scan's last kernel also publishes the results
     const uint16_t *reach;      // codes a span can be entered in (ascending), or null = all
     uint32_t nreach, nreach_base;       // all / those below the stuck codes (S * (max_bits + 2) + 3)
@@ -424,7 +424,7 @@ struct FsmScanArgs {
     uint16_t *cap_first;        // [captures]
     uint32_t *sync_rec;         // [total_blocks_cap][8] the walk's block records (fsm_scan.hip, kSyncRec*)
     uint64_t pre_plane;         // pre_codes holds 4 planes this many elements apart (0: one plane, no such walk)
-    uint32_t lt_sync_words;     // lt_merged's size with append_sync_codes' tables (lt_merged_words: the rows alone)
+    uint32_t lt_sync_words;     // lt_merged's size with the sync walk's tables (lt_merged_words: the rows alone)
     uint32_t *sync_fail;        // device word, zero at launch: the walk from the synchronising spans gave up
     uint32_t sync_try;          // 1: try that walk first, the composing kernels queued behind it (they return at once unless
                                 // it gave up); 2: the walk alone -- giving up refuses the run with kScanFbSync and the host
@@ -432,33 +432,30 @@ struct FsmScanArgs {
 };
 
 constexpr uint32_t kScanFbSync = 16;      // refusal bit: the walk from synchronising spans gave up in a launch without composing kernels
-uint32_t fsm_scan_leaf_block(uint32_t D, uint32_t S, uint32_t SNB);
-// The trigger / state tables in the layout the scan kernels keep in LDS: size, and
-// a host-side fill (16-byte aligned destination) to be uploaded once per context.
-size_t fsm_scan_ltab_bytes();
-// returns the size of the abstract domain (states x bit counts + 3 + stuck codes)
-uint32_t fsm_scan_fill_ltab(void *dst, const FsmTablesDev &tables, uint32_t spb, uint32_t decim,
-                            const std::vector<uint16_t> &stuck_src, const std::vector<uint8_t> &stuck_rows);
-// Packed result of a span as a step function of its length, per (row, level)
-// (host side; false = not tabulated, the kernels simulate).
-// reach: the abstract codes a span can be entered in (closure of the tables' results);
-// empty when that cannot be told.  stuck_src / stuck_rows: the normal codes / table rows with
-// a "no trigger fired on the edge" result (they extend the domain: fsm_scan_fill_ltab).
-bool build_leaf_tables(const FsmTablesDev &tables, uint32_t spb, uint32_t decim, std::vector<uint32_t> &off,
-                       std::vector<uint32_t> &n0, std::vector<uint32_t> &pk, std::vector<uint16_t> &reach,
-                       std::vector<uint16_t> &stuck_src, std::vector<uint8_t> &stuck_rows);
-// The span tables merged over the rows: per level the sorted union of all (state, class) rows' breakpoints,
-// and for every interval between two of them the 2S packed rows a span of that length has -- ONE search per
-// leaf, independent of the state the leaf is entered in.  Layout (32-bit words):
-//   [0] nbp level 0, [1] nbp level 1, [2] 2S, [3] 0 | bp level 0 | bp level 1 | rows level 0 [nbp0][2S] |
-//   rows level 1 [nbp1][2S]
-std::vector<uint32_t> build_merged_rows(uint32_t S, const std::vector<uint32_t> &off, const std::vector<uint32_t> &n0,
-                                        const std::vector<uint32_t> &pk);
-// Marks the intervals of the merged rows in which a span is SYNCHRONISING (every row a span of that level can be
-// entered in holds the same absolute normal code): one word per interval behind the rows (the code, or 0xffff),
-// header word [3] = where they start.  reach: code | level mask << 14 as build_leaf_tables returns it.
-void append_sync_codes(std::vector<uint32_t> &merged, uint32_t S, uint32_t NB1, uint32_t max_bits,
-                       const std::vector<uint16_t> &reach);
+// Everything the scan derives from a device's tables, host side (built once per context).
+struct ScanTables {
+    bool spans_built;           // the span tables' verdict (false: refused or not asked for -- the kernels simulate)
+    uint32_t S, max_bits, NB1, SNB, D, leaf_block;      // D: the abstract domain (S * NB1 + 3 + stuck codes)
+    // Span tables (empty unless spans_built): packed result of a span as a step function of its length --
+    // table (row, L) = entries [off[2 * row + L], off[2 * row + L + 1]), entry i covers lengths n0[i] .. n0[i + 1] - 1.
+    std::vector<uint32_t> off, n0, pk;
+    std::vector<uint16_t> reach;                // codes a span can be entered in: code | level mask << 14, ascending; empty = unknown
+    std::vector<uint16_t> reach_by_level;       // the codes below the stuck ones met at level 0, then those met at level 1
+    uint32_t reach_base, reach_lv[2];           // reach entries below the stuck codes; sizes of the two lists
+    // normal codes / table rows with a "no trigger fired on the edge" result (they extend the domain)
+    std::vector<uint16_t> stuck_src;
+    std::vector<uint8_t> stuck_rows;
+    // The span tables merged over the rows (one search per leaf, whatever state it is entered in), and behind the
+    // first merged_rows_words words the tables of the walk from synchronising spans (fsm_scan.hip: append_sync_codes)
+    std::vector<uint32_t> merged;
+    uint32_t merged_rows_words;
+    std::vector<uint4> ltab;                    // the trigger / state tables in the layout the kernels keep in LDS
+};
+// with_spans = false: no span tables (the kernels simulate every span), the domain without stuck codes
+ScanTables build_scan_tables(const FsmTablesDev &tables, uint32_t spb, uint32_t decim, bool with_spans);
+// Host-side consistency check of the merged rows and the sync walk's tables against the span tables
+// (a diagnostic: creating a context does not run it).  false also when the span tables were not built.
+bool scan_tables_selfcheck(const ScanTables &t);
 uint32_t fsm_scan_fin_block();
 // t_end (optional): event that takes the end time stamp of the scan's last kernel
 hipError_t launch_fsm_scan(const FsmScanArgs &a, hipStream_t stream, hipEvent_t t_end = nullptr);

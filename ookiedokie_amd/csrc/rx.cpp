@@ -101,6 +101,53 @@ struct DevBuf {
         }
         return OOKD_OK;
     }
+    // allocates and fills from host memory (an empty vector leaves the buffer empty)
+    int upload(const std::vector<T> &v) {
+        const int rc = alloc(v.size());
+        if (rc != OOKD_OK || v.empty()) return rc;
+        if (hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("upload of %zu bytes failed", v.size() * sizeof(T));
+            return OOKD_ERR_HIP;
+        }
+        return OOKD_OK;
+    }
+};
+
+// The scan's tables (fsm_scan.hip: build_scan_tables) and their device copies, uploaded once per context
+struct ScanTablesDev {
+    ScanTables h{};                 // host side: the domain D, S, max_bits, leaf_block and the reach counts are read here
+    DevBuf<uint32_t> d_lt_off, d_lt_n0, d_lt_pk;    // span tables (empty = the scan simulates)
+    DevBuf<uint32_t> d_lt_merged;   // their merged rows + the sync walk's tables
+    DevBuf<uint16_t> d_reach;       // abstract codes a span can be entered in, then the per-level lists (empty = all)
+    DevBuf<uint4> d_ltab;           // the scan kernels' LDS table image
+
+    int upload(ScanTables &&t) {
+        h = std::move(t);
+        std::vector<uint16_t> reach = h.reach;
+        reach.insert(reach.end(), h.reach_by_level.begin(), h.reach_by_level.end());
+        int rc = d_reach.upload(reach);
+        if (!h.n0.empty()) rc |= d_lt_off.upload(h.off) | d_lt_n0.upload(h.n0) | d_lt_pk.upload(h.pk);
+        return rc | d_lt_merged.upload(h.merged) | d_ltab.upload(h.ltab);
+    }
+    void fill(FsmScanArgs &a) const {
+        a.D = h.D;
+        a.S = h.S;
+        a.SNB = h.SNB;
+        a.leaf_block = h.leaf_block;
+        a.lt_off = d_lt_off.p;
+        a.lt_n0 = d_lt_n0.p;
+        a.lt_pk = d_lt_pk.p;
+        a.lt_words = (uint32_t)(d_lt_off.n + d_lt_n0.n + d_lt_pk.n);
+        a.lt_merged = d_lt_merged.p;
+        a.lt_merged_words = h.merged_rows_words;
+        a.lt_sync_words = (uint32_t)d_lt_merged.n;
+        a.ltab = d_ltab.p;
+        a.reach = d_reach.p;
+        a.nreach = (uint32_t)h.reach.size();
+        a.nreach_base = h.reach_base;
+        a.nreach_lv[0] = h.reach_lv[0];
+        a.nreach_lv[1] = h.reach_lv[1];
+    }
 };
 
 // smallest float p with sqrtf(p) >= thr  (SURVEY.md hard part 3)
@@ -425,7 +472,6 @@ struct ookd_rx : RxHandles {
     DevBuf<uint32_t> d_skipc;               // every leaf applied to the two skip codes (leaf kernel -> entry walk)
     DevBuf<uint32_t> d_sync_rec;            // the block records of the walk from synchronising spans
     uint64_t pre_plane = 0;                 // elements per plane of d_pre (4 planes when that walk can run)
-    uint32_t lt_merged_rows = 0;            // size of d_lt_merged without append_sync_codes' tables
     bool scan_sync = false;                 // try the walk from synchronising spans first
     // How the next scan is queued.  The walk alone while it works (the composing kernels behind it would only return
     // at once: five launches, ~25 us of the chain).  A run where it gives up is refused and queued again with the
@@ -474,16 +520,9 @@ struct ookd_rx : RxHandles {
     bool scan_pending = false;      // a scan is queued; its verdict is read with the results
     bool pending_first_valid = false;
     FsmStateDev pending_first{};
-    uint32_t scan_reach_base = 0;   // reach entries below the stuck codes
-    uint32_t scan_reach_n = 0;      // reach entries; behind them the per-level lists (scan_reach_lv[level] codes each)
-    uint32_t scan_reach_lv[2] = {0, 0};
-    uint32_t scan_D = 0, scan_S = 0, scan_leaf_block = 0, scan_blocks_cap = 0;
-    uint32_t scan_max_bits = 0;
+    ScanTablesDev scan_tab;         // its tables and what they say about the domain
+    uint32_t scan_blocks_cap = 0;
     DevBuf<uint16_t> d_block_tab;
-    DevBuf<uint32_t> d_lt_off, d_lt_n0, d_lt_pk;    // span tables (empty = the scan simulates)
-    DevBuf<uint32_t> d_lt_merged;                    // build_merged_rows of them
-    DevBuf<uint4> d_ltab;           // the scan kernels' LDS table image
-    DevBuf<uint16_t> d_reach;       // abstract codes a span can be entered in (empty = all)
     DevBuf<uint32_t> d_cap_group_off, d_cap_super_off;
     DevBuf<uint16_t> d_group_tab, d_super_tab, d_super_in, d_cap_end;
     DevBuf<uint32_t> d_cap_block_off;
@@ -1143,7 +1182,7 @@ int ookd_rx::run_state_machine(const FsmStateDev *first, bool fresh) {
         return OOKD_OK;
     }
     bool try_scan = scan_ok;
-    if (first && (first->cur >= scan_S || first->nbits > scan_max_bits + 1)) try_scan = false;
+    if (first && (first->cur >= scan_tab.h.S || first->nbits > scan_tab.h.max_bits + 1)) try_scan = false;
     if (try_scan) {
         // queued without a host sync; fetch_results() looks at the scan's verdict
         // and, if it refused the capture, runs the round path instead
@@ -1165,25 +1204,9 @@ int ookd_rx::run_state_machine(const FsmStateDev *first, bool fresh) {
 FsmScanArgs ookd_rx::scan_args() const {
     FsmScanArgs a{};
     a.f = fsm_params();
-    a.D = scan_D;
-    a.S = scan_S;
-    a.SNB = scan_S * (scan_max_bits + 2);
-    a.leaf_block = scan_leaf_block;
+    scan_tab.fill(a);
     a.grid_blocks = 1024;
     a.block_tab = d_block_tab.p;
-    a.lt_off = d_lt_off.p;
-    a.lt_n0 = d_lt_n0.p;
-    a.lt_pk = d_lt_pk.p;
-    a.lt_words = (uint32_t)(d_lt_off.n + d_lt_n0.n + d_lt_pk.n);
-    a.lt_merged = d_lt_merged.p;
-    a.lt_merged_words = lt_merged_rows;
-    a.lt_sync_words = (uint32_t)d_lt_merged.n;
-    a.ltab = d_ltab.p;
-    a.reach = d_reach.p;
-    a.nreach = scan_reach_n;
-    a.nreach_base = scan_reach_base;
-    a.nreach_lv[0] = scan_reach_lv[0];
-    a.nreach_lv[1] = scan_reach_lv[1];
     a.publish = publish_params();
     a.cap_group_off = d_cap_group_off.p;
     a.group_tab = d_group_tab.p;
@@ -1271,7 +1294,7 @@ int ookd_rx::dump_scan_debug() {
         HIPCHK(hipMemcpy(&ne32[0], d_blk_offset.p, 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(&ne32[1], d_blk_offset.p + run_blocks, 4, hipMemcpyDeviceToHost));
         const uint32_t ne = ne32[1] - ne32[0];
-        fprintf(stderr, "[scan] blocks %u..%u ne %u D %u LB %u\n", off[0], off[1], ne, scan_D, scan_leaf_block);
+        fprintf(stderr, "[scan] blocks %u..%u ne %u D %u LB %u\n", off[0], off[1], ne, scan_tab.h.D, scan_tab.h.leaf_block);
         std::vector<LeafEvDev> evs(ne + 1);
         HIPCHK(hipMemcpy(evs.data(), d_events.p, (ne + 1) * sizeof(LeafEvDev), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i <= ne && i < 14; ++i)
@@ -1840,109 +1863,20 @@ bool setup_run_buffers(ookd_rx &rx, const ookd_rx_config &cfg) {
     return rc == OOKD_OK;
 }
 
-// The scan form of the state machine (fsm_scan.hip): its tables and buffers
-bool setup_scan(ookd_rx &rx, const ookd_device &device, const ookd_rx_config &cfg) {
+// The scan's run buffers, sized by the domain and the leaf block its tables gave
+int setup_scan_workspace(ookd_rx &rx) {
     const size_t caps = rx.max_captures;
-    // abstract states = states x bit counts + skip x2 + poison
-    rx.scan_S = (uint32_t)device.state_duration_us.size();
-    rx.scan_max_bits = device.num_bits;
-    rx.scan_D = rx.scan_S * (device.num_bits + 2) + 3;
-    rx.scan_ok = !(cfg.flags & OOKD_RX_FSM_ROUNDS) && rx.scan_D <= 384 && device.num_bits <= 254 && !rx.big_device;
-    if (!rx.scan_ok) return true;
+    const uint32_t D = rx.scan_tab.h.D, leaf_block = rx.scan_tab.h.leaf_block;
     int rc = OOKD_OK;
-    std::vector<uint16_t> stuck_src;        // normal codes an inert edge can leave stuck (domain extension)
-    std::vector<uint8_t> stuck_rows;
-    if (!(cfg.flags & OOKD_RX_SCAN_SIMS)) {
-        // span tables: packed result of a span as a step function of its length
-        std::vector<uint32_t> off, n0, pk;
-        std::vector<uint16_t> reach;
-        const auto t0 = std::chrono::steady_clock::now();
-        const bool ok = build_leaf_tables(*rx.h_tables, cfg.samples_per_buffer, rx.total_decim, off, n0, pk,
-                                          reach, stuck_src, stuck_rows);
-        if (!ok) {
-            stuck_src.clear();
-            stuck_rows.clear();
-        }
-        if (getenv("OOKD_DEBUG")) {
-            size_t zeros = 0;
-            for (uint32_t v : pk) zeros += v == 0;
-            fprintf(stderr, "[ookd] span tables: %s, %zu intervals (%zu need simulation), %zu codes can get stuck, "
-                            "%zu codes reachable, %.1f ms\n",
-                    ok ? "built" : "REFUSED", n0.size(), zeros, stuck_src.size(), reach.size(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            if (getenv("OOKD_DEBUG")[0] == '2') {
-                for (size_t t = 0; t + 1 < off.size(); ++t) {
-                    fprintf(stderr, "[ookd]  row %zu L %zu:", t / 2, t % 2);
-                    for (uint32_t i = off[t]; i < off[t + 1]; ++i) fprintf(stderr, " %u:%08x", n0[i], pk[i]);
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-        if (ok && !reach.empty()) {
-            const uint32_t d0 = rx.scan_S * (device.num_bits + 2) + 3;
-            rx.scan_reach_base = 0;                // entries are code | level mask << 14, ascending in the code
-            for (uint16_t v : reach) rx.scan_reach_base += (v & 0x3fffu) < d0 ? 1u : 0u;
-            // ... then, for the composition of chunk tables, the codes met at level 0 and those met at
-            // level 1 as two plain lists (a chunk starts at one level: only that list is walked)
-            rx.scan_reach_n = (uint32_t)reach.size();
-            {
-                std::vector<uint16_t> l0, l1;
-                for (uint32_t i = 0; i < rx.scan_reach_base; ++i) {
-                    if (reach[i] & 0x4000u) l0.push_back((uint16_t)(reach[i] & 0x3fffu));
-                    if (reach[i] & 0x8000u) l1.push_back((uint16_t)(reach[i] & 0x3fffu));
-                }
-                rx.scan_reach_lv[0] = (uint32_t)l0.size();
-                rx.scan_reach_lv[1] = (uint32_t)l1.size();
-                reach.insert(reach.end(), l0.begin(), l0.end());
-                reach.insert(reach.end(), l1.begin(), l1.end());
-            }
-            rc |= rx.d_reach.alloc(reach.size());
-            if (rc == OOKD_OK && hipMemcpy(rx.d_reach.p, reach.data(), reach.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-                rc = OOKD_ERR_HIP;
-            }
-        }
-        if (ok && !n0.empty()) {
-            rc |= rx.d_lt_off.alloc(off.size());
-            rc |= rx.d_lt_n0.alloc(n0.size());
-            rc |= rx.d_lt_pk.alloc(pk.size());
-            if (rc == OOKD_OK &&
-                (hipMemcpy(rx.d_lt_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                 hipMemcpy(rx.d_lt_n0.p, n0.data(), n0.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                 hipMemcpy(rx.d_lt_pk.p, pk.data(), pk.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
-                rc = OOKD_ERR_HIP;
-            }
-            std::vector<uint32_t> merged = build_merged_rows(rx.scan_S, off, n0, pk);
-            rx.lt_merged_rows = (uint32_t)merged.size();
-            {
-                // (reach: the level lists were appended behind the scan_reach_n masked codes above)
-                const std::vector<uint16_t> masked(reach.begin(), reach.begin() + (reach.empty() ? 0 : rx.scan_reach_n));
-                append_sync_codes(merged, rx.scan_S, device.num_bits + 2, device.num_bits, masked);
-                rx.scan_sync = !(cfg.flags & OOKD_RX_SCAN_TABLES) && !dev_getenv("OOKD_SCAN_NO_SYNC");
-                if (const char *e = dev_getenv("OOKD_SYNC_MIN_EDGES")) rx.sync_min_edges = strtoull(e, nullptr, 0);
-            }
-            rc |= rx.d_lt_merged.alloc(merged.size());
-            if (rc == OOKD_OK && hipMemcpy(rx.d_lt_merged.p, merged.data(), merged.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-                rc = OOKD_ERR_HIP;
-            }
-        }
-    }
-    std::vector<uint4> image((fsm_scan_ltab_bytes() + 15) / 16);
-    rx.scan_D = fsm_scan_fill_ltab(image.data(), *rx.h_tables, cfg.samples_per_buffer, rx.total_decim,
-                                   stuck_src, stuck_rows);
-    rc |= rx.d_ltab.alloc(image.size());
-    if (rc == OOKD_OK && hipMemcpy(rx.d_ltab.p, image.data(), image.size() * 16, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = OOKD_ERR_HIP;
-    }
-    rx.scan_leaf_block = fsm_scan_leaf_block(rx.scan_D, rx.scan_S, rx.scan_S * (rx.scan_max_bits + 2));
-    rx.scan_blocks_cap = (uint32_t)(rx.edge_capacity / rx.scan_leaf_block + caps + 8);
-    rc |= rx.d_block_tab.alloc((size_t)rx.scan_blocks_cap * ((rx.scan_D + 7u) & ~7u) + 64);
+    rx.scan_blocks_cap = (uint32_t)(rx.edge_capacity / leaf_block + caps + 8);
+    rc |= rx.d_block_tab.alloc((size_t)rx.scan_blocks_cap * ((D + 7u) & ~7u) + 64);
     {
         const size_t ngroups = rx.scan_blocks_cap / 16 + caps + 8;
         rc |= rx.d_cap_group_off.alloc(caps + 1);
-        rc |= rx.d_group_tab.alloc(ngroups * ((rx.scan_D + 7u) & ~7u) + 64);
+        rc |= rx.d_group_tab.alloc(ngroups * ((D + 7u) & ~7u) + 64);
         const size_t nsuper = rx.scan_blocks_cap / 64 + caps + 8;
         rc |= rx.d_cap_super_off.alloc(caps + 1);
-        rc |= rx.d_super_tab.alloc(nsuper * ((rx.scan_D + 7u) & ~7u) + 64);
+        rc |= rx.d_super_tab.alloc(nsuper * ((D + 7u) & ~7u) + 64);
         rc |= rx.d_super_in.alloc(nsuper);
         rc |= rx.d_cap_end.alloc(2 * (caps + 8));         // + cap_first
     }
@@ -1953,10 +1887,10 @@ bool setup_scan(ookd_rx &rx, const ookd_device &device, const ookd_rx_config &cf
     rc |= rx.d_scan_errs.alloc(1u << 16);
     rc |= rx.d_cap_fallback.alloc(caps);
     // (the walk from synchronising spans keeps a plane of entry codes per candidate)
-    rx.pre_plane = rx.scan_sync ? (size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64 : 0;
-    rc |= rx.d_pre.alloc(((size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64) * (rx.scan_sync ? 4 : 1));
-    rc |= rx.d_rowz.alloc((size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64);
-    rc |= rx.d_skipc.alloc((size_t)rx.scan_blocks_cap * rx.scan_leaf_block + 64);
+    rx.pre_plane = rx.scan_sync ? (size_t)rx.scan_blocks_cap * leaf_block + 64 : 0;
+    rc |= rx.d_pre.alloc(((size_t)rx.scan_blocks_cap * leaf_block + 64) * (rx.scan_sync ? 4 : 1));
+    rc |= rx.d_rowz.alloc((size_t)rx.scan_blocks_cap * leaf_block + 64);
+    rc |= rx.d_skipc.alloc((size_t)rx.scan_blocks_cap * leaf_block + 64);
     rc |= rx.d_sync_rec.alloc(((size_t)rx.scan_blocks_cap + 8) * 10);     // records, digests, selections
     rc |= rx.d_blk_in.alloc((size_t)rx.scan_blocks_cap + 16);
     rc |= rx.d_final_state.alloc(caps);
@@ -1968,6 +1902,39 @@ bool setup_scan(ookd_rx &rx, const ookd_device &device, const ookd_rx_config &cf
     if (rc == OOKD_OK && hipMemset(rx.d_fin_tickets.p, 0, (kMaxChunks + 1) * sizeof(unsigned long long)) != hipSuccess) rc = OOKD_ERR_HIP;
     // stamped aggregates: the stamp half of every word must start out as "no run"
     if (rc == OOKD_OK && hipMemset(rx.d_fsum.p, 0, rx.d_fsum.n * sizeof(uint64_t)) != hipSuccess) rc = OOKD_ERR_HIP;
+    return rc;
+}
+
+// The scan form of the state machine (fsm_scan.hip): its tables and buffers
+bool setup_scan(ookd_rx &rx, const ookd_device &device, const ookd_rx_config &cfg) {
+    // abstract states = states x bit counts + skip x2 + poison
+    const uint32_t d0 = (uint32_t)device.state_duration_us.size() * (device.num_bits + 2) + 3;
+    rx.scan_ok = !(cfg.flags & OOKD_RX_FSM_ROUNDS) && d0 <= 384 && device.num_bits <= 254 && !rx.big_device;
+    if (!rx.scan_ok) return true;
+    const bool with_spans = !(cfg.flags & OOKD_RX_SCAN_SIMS);
+    const auto t0 = std::chrono::steady_clock::now();
+    ScanTables t = build_scan_tables(*rx.h_tables, cfg.samples_per_buffer, rx.total_decim, with_spans);
+    if (with_spans && getenv("OOKD_DEBUG")) {
+        size_t zeros = 0;
+        for (uint32_t v : t.pk) zeros += v == 0;
+        fprintf(stderr, "[ookd] span tables: %s, %zu intervals (%zu need simulation), %zu codes can get stuck, "
+                        "%zu codes reachable, %.1f ms\n",
+                t.spans_built ? "built" : "REFUSED", t.n0.size(), zeros, t.stuck_src.size(), t.reach.size(),
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        if (getenv("OOKD_DEBUG")[0] == '2') {
+            for (size_t r = 0; r + 1 < t.off.size(); ++r) {
+                fprintf(stderr, "[ookd]  row %zu L %zu:", r / 2, r % 2);
+                for (uint32_t i = t.off[r]; i < t.off[r + 1]; ++i) fprintf(stderr, " %u:%08x", t.n0[i], t.pk[i]);
+                fprintf(stderr, "\n");
+            }
+        }
+    }
+    int rc = rx.scan_tab.upload(std::move(t));
+    if (rx.scan_tab.d_lt_merged.n) {
+        rx.scan_sync = !(cfg.flags & OOKD_RX_SCAN_TABLES) && !dev_getenv("OOKD_SCAN_NO_SYNC");
+        if (const char *e = dev_getenv("OOKD_SYNC_MIN_EDGES")) rx.sync_min_edges = strtoull(e, nullptr, 0);
+    }
+    rc |= setup_scan_workspace(rx);
     return rc == OOKD_OK;
 }
 
@@ -2301,113 +2268,42 @@ int ookd_scan_domain_info(const ookd_device *device, uint32_t samples_per_buffer
         set_error("ookd_scan_domain_info: bad argument");
         return OOKD_ERR_ARG;
     }
-    std::unique_ptr<FsmTablesDev> t(new FsmTablesDev());
-    memset(t.get(), 0, sizeof(FsmTablesDev));
-    fill_fsm_tables(*device, *t);
-    std::vector<uint32_t> off, n0, pk;
-    std::vector<uint16_t> reach, stuck_src;
-    std::vector<uint8_t> stuck_rows;
-    const bool ok = build_leaf_tables(*t, samples_per_buffer, total_decimation, off, n0, pk, reach, stuck_src,
-                                      stuck_rows);
+    std::unique_ptr<FsmTablesDev> g(new FsmTablesDev());
+    memset(g.get(), 0, sizeof(FsmTablesDev));
+    fill_fsm_tables(*device, *g);
+    const ScanTables t = build_scan_tables(*g, samples_per_buffer, total_decimation, true);
     size_t zeros = 0;
-    for (uint32_t v : pk) zeros += v == 0;
-    const uint32_t S = (uint32_t)device->state_duration_us.size();
-    // the merged rows (one search per leaf for scan_entry_kernel) must say what the per-row searches say, at
-    // every breakpoint, next to it and far beyond: a mismatch reports the tables as not built
-    bool merged_ok = true;
-    if (ok && !n0.empty()) {
-        const std::vector<uint32_t> m = build_merged_rows(S, off, n0, pk);
-        auto lookup = [&](uint32_t row, uint32_t L, uint32_t n) -> uint32_t {
-            uint32_t lo = off[2 * row + L], hi = off[2 * row + L + 1];
-            if (lo >= hi) return 0u;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (n0[mid] <= n) lo = mid;
-                else hi = mid;
-            }
-            return pk[lo];
-        };
-        std::vector<uint32_t> probes = {0u, 1u, 0xfffffff0u, 0x7fffffffu};
-        for (uint32_t v : n0) {
-            probes.push_back(v);
-            probes.push_back(v + 1);
-            if (v) probes.push_back(v - 1);
-        }
-        for (uint32_t L = 0; L < 2 && merged_ok; ++L) {
-            const uint32_t nbp = m[L];
-            const uint32_t *bp = m.data() + 4 + (L ? m[0] : 0u);
-            for (uint32_t n : probes) {
-                uint32_t lo = 0, hi = nbp;
-                while (hi - lo > 1) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (bp[mid] <= n) lo = mid;
-                    else hi = mid;
-                }
-                const uint32_t *rows = m.data() + 4 + m[0] + m[1] + ((L ? m[0] : 0u) + lo) * 2u * S;
-                for (uint32_t k = 0; k < S; ++k) {
-                    const uint32_t p0 = lookup(2 * k, L, n);
-                    const uint32_t p1 = (p0 & 0x10000000u) ? p0 : lookup(2 * k + 1, L, n);      // kPkShared
-                    if (rows[2 * k] != (p0 & ~0x10000000u) || rows[2 * k + 1] != (p1 & ~0x10000000u)) merged_ok = false;
-                }
-            }
-        }
-    }
-    // ... and the sync walk's second copy of the rows (append_sync_codes) must step every normal code exactly as the
-    // rows do, and every interval's image must hold what its reachable codes end in
-    if (ok && merged_ok && !n0.empty()) {
-        std::vector<uint32_t> m = build_merged_rows(S, off, n0, pk);
-        const uint32_t NB1 = device->num_bits + 2, max_bits = device->num_bits, SNB = S * NB1;
-        append_sync_codes(m, S, NB1, max_bits, reach);
-        const uint32_t nbp[2] = {m[0], m[1]}, rows0 = 4 + m[0] + m[1], sync_off = m[3];
-        const uint32_t rows2 = sync_off + 2 * (nbp[0] + nbp[1]);
-        if (m.size() != rows2 + (size_t)(nbp[0] + nbp[1]) * 2 * S) merged_ok = false;
-        for (uint32_t L = 0; L < 2 && merged_ok; ++L) {
-            for (uint32_t z = 0; z < nbp[L] && merged_ok; ++z) {
-                const size_t at = (size_t)((L ? nbp[0] : 0u) + z) * 2 * S;
-                const uint32_t w0 = m[sync_off + 2 * ((L ? nbp[0] : 0u) + z)], w1 = m[sync_off + 2 * ((L ? nbp[0] : 0u) + z) + 1];
-                const uint32_t nimg = (w1 >> 16) & 0xfu, img[3] = {w0 & 0xffffu, w0 >> 16, w1 & 0xffffu};
-                for (uint32_t c = 0; c < SNB && merged_ok; ++c) {
-                    const uint32_t cur = c / NB1, nb = c - cur * NB1, r = 2 * cur + (nb >= max_bits ? 1u : 0u);
-                    const uint32_t pp = m[rows0 + at + r], q = m[rows2 + at + r];
-                    uint32_t want = 0xffffffffu;
-                    if (pp & 0x80000000u) {
-                        want = pp & 0xffffu;
-                    } else if (pp & 0x20000000u) {
-                        const uint32_t nbo = nb + ((pp >> 8) & 0xffffu);
-                        want = (pp & 0xffu) * NB1 + (nbo >= NB1 ? NB1 - 1 : nbo);
-                    }
-                    if (want == 0xffffffffu || want >= SNB + 3) {
-                        if (q != 0) merged_ok = false;
-                        continue;
-                    }
-                    if (!(q & 0x80000000u)) {
-                        merged_ok = false;
-                        continue;
-                    }
-                    const uint32_t nb2 = std::min(((q & 0x40000000u) ? nb : 0u) + ((q >> 8) & 0xffffu), NB1 - 1u), cur2 = q & 0xffu;
-                    const uint32_t got = cur2 < S ? cur2 * NB1 + nb2 : SNB + nb2;
-                    if (got != want) merged_ok = false;
-                    // a reachable code's result is in the image (when the interval has one)
-                    bool reachable = reach.empty();
-                    for (uint16_t v : reach) reachable = reachable || ((v & 0x3fffu) == c && (v & (0x4000u << L)));
-                    if (nimg && reachable && want != img[0] && want != img[1] && want != img[2]) merged_ok = false;
-                }
-            }
-        }
-    }
-    out[0] = (ok && merged_ok) ? 1u : 0u;
-    out[1] = (uint32_t)n0.size();
+    for (uint32_t v : t.pk) zeros += v == 0;
+    out[0] = scan_tables_selfcheck(t) ? 1u : 0u;
+    out[1] = (uint32_t)t.n0.size();
     out[2] = (uint32_t)zeros;
-    out[3] = (uint32_t)reach.size();
-    out[4] = ok ? (uint32_t)stuck_src.size() : 0u;
-    out[5] = ok ? (uint32_t)stuck_rows.size() : 0u;
-    std::vector<uint4> image((fsm_scan_ltab_bytes() + 15) / 16);
-    if (!ok) {
-        stuck_src.clear();
-        stuck_rows.clear();
-    }
-    out[6] = fsm_scan_fill_ltab(image.data(), *t, samples_per_buffer, total_decimation, stuck_src, stuck_rows);
-    out[7] = S;
+    out[3] = (uint32_t)t.reach.size();
+    out[4] = (uint32_t)t.stuck_src.size();
+    out[5] = (uint32_t)t.stuck_rows.size();
+    out[6] = t.D;
+    out[7] = t.S;
+    return OOKD_OK;
+}
+
+// Test aid, not in the public header: 64-bit FNV-1a digests of  off | n0 | pk,  reach | reach_by_level,  merged
+// (sync tables appended)  and the LTab image, to hold the host builders against recorded values without a GPU.
+int ookd_scan_tables_digest(const ookd_device *device, uint32_t samples_per_buffer, uint32_t total_decimation,
+                            uint64_t out[4]) {
+    if (!device || !out || !samples_per_buffer || !total_decimation) return OOKD_ERR_ARG;
+    std::unique_ptr<FsmTablesDev> g(new FsmTablesDev());
+    memset(g.get(), 0, sizeof(FsmTablesDev));
+    fill_fsm_tables(*device, *g);
+    const ScanTables t = build_scan_tables(*g, samples_per_buffer, total_decimation, true);
+    auto fnv = [](uint64_t h, const auto &v) {
+        const unsigned char *b = reinterpret_cast<const unsigned char *>(v.data());
+        for (size_t i = 0; i < v.size() * sizeof(v[0]); ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+        return h;
+    };
+    const uint64_t h0 = 0xcbf29ce484222325ull;
+    out[0] = fnv(fnv(fnv(h0, t.off), t.n0), t.pk);
+    out[1] = fnv(fnv(h0, t.reach), t.reach_by_level);
+    out[2] = fnv(h0, t.merged);
+    out[3] = fnv(h0, t.ltab);
     return OOKD_OK;
 }
 

@@ -245,6 +245,36 @@ def test_scan_domain_of_the_shipped_devices(name, stuck, rate):
     assert base // 3 < reach <= domain          # far fewer than all codes are ever entered
 
 
+# 64-bit FNV-1a digests of the scan's host-built tables (span tables, reach lists, merged rows with the
+# sync walk's tables, LTab image), recorded from the six free functions that built them before
+# build_scan_tables took over, called in the order context creation called them.
+_SCAN_TABLE_DIGESTS = {
+    ("p3l-nexa2012", 3000000, 8192, 1): (0x792956e779fcfc5e, 0xe9fb05d564b98bab, 0x65dd0cce3b7a8ccc, 0x19f94e7c9c70a134),
+    ("p3l-nexa2012", 3000000, 8192, 4): (0x792956e779fcfc5e, 0xe9fb05d564b98bab, 0x65dd0cce3b7a8ccc, 0x86dd1dcfd79dce77),
+    ("p3l-nexa2012", 750000, 8192, 1): (0xf512009fff553b75, 0xe9fb05d564b98bab, 0xd3f95ce7dd7130cc, 0xfef853d8575c2d0e),
+    ("p3l-nexa2012", 750000, 8192, 4): (0xf512009fff553b75, 0xe9fb05d564b98bab, 0xd3f95ce7dd7130cc, 0x3e5348d2549185cd),
+    ("unknown-remote1", 3000000, 8192, 1): (0x420c08a18202c450, 0x79526b8fcb2f1277, 0x4c746e2f67ba33f7, 0x84869cbc169dfc07),
+    ("unknown-remote1", 3000000, 8192, 4): (0x420c08a18202c450, 0x79526b8fcb2f1277, 0x4c746e2f67ba33f7, 0xd3ff150797f10e74),
+    ("unknown-remote1", 750000, 8192, 1): (0x0da3b0a23e3e74b3, 0x79526b8fcb2f1277, 0x36c645ec4855c579, 0x923c6697f9378961),
+    ("unknown-remote1", 750000, 8192, 4): (0x0da3b0a23e3e74b3, 0x79526b8fcb2f1277, 0x36c645ec4855c579, 0x0c5411dd194dd512),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_SCAN_TABLE_DIGESTS), ids=lambda c: "%s-%d-%d-%d" % c)
+def test_scan_tables_are_byte_identical_to_the_recorded_ones(case, built_lib):
+    """The tables the scan kernels read are a pure function of (device, rate, buffer size, decimation):
+    every byte of them equals what was recorded (ookd_scan_tables_digest is a test aid of the library,
+    not in the public header)."""
+    name, rate, spb, decim = case
+    d = ok.Device.load(golden_path("devices", name), rate)
+    fn = built_lib.ookd_scan_tables_digest
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    assert fn(d._h, spb, decim, out) == 0
+    assert tuple(out) == _SCAN_TABLE_DIGESTS[case]
+
+
 def test_synth_is_deterministic_and_windowed():
     dev = ok.Device.load(golden_path("devices", "unknown-remote1"), 3000000)
     a = ok.Synth(dev, 500_000, seed=3).fill_host()
