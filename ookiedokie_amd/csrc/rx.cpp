@@ -15,6 +15,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "front_plan.hpp"
 #include "ingest.hpp"
 #include "kernels.hpp"
 
@@ -150,96 +151,27 @@ struct ScanTablesDev {
     }
 };
 
-// smallest float p with sqrtf(p) >= thr  (SURVEY.md hard part 3)
-float power_threshold(float thr) {
-    if (std::isnan(thr)) return NAN;
-    if (thr <= 0.0f) return 0.0f;
-    if (std::isinf(thr)) return INFINITY;
-    float p = (float)((double)thr * (double)thr);
-    while (p > 0.0f && sqrtf(nextafterf(p, 0.0f)) >= thr) p = nextafterf(p, 0.0f);
-    while (!std::isinf(p) && sqrtf(p) < thr) p = nextafterf(p, INFINITY);
-    return p;
-}
+// The front end's plan (front_plan.hpp: plan_front) and its device copies, uploaded once per context
+struct FrontDev {
+    FrontPlan plan;
+    DevBuf<float> d_taps;
+    DevBuf<uint16_t> d_mfma_a;      // A-fragment image of the matrix-core form (empty = packed-VALU form)
+    DevBuf<float> d_ctaps;          // every carrier's complex taps
+    DevBuf<TunedCarrierDev> d_carriers;     // the fused carrier kernel's table
+    FrontParams base{};             // plan.fp with the device pointers: what does not change from run to run
 
-// Guard band for the fused-multiply-add FIR (1 stage): any sample whose
-// FMA-computed power lies in [p_lo, p_hi) is recomputed in reference order.
-// e bounds |y_fma - y_ref| per component: both chains are within
-// gamma_T * sum|h||x| of the exact sum (one rounding per step for fma, two
-// for mul+add), inputs are bounded by 32768/2048 = 16.
-//
-// Several stages: the fused and the reference chain of stage s+1 start from
-// inputs that already differ by e_s, which the stage amplifies by at most
-// sum|h_{s+1}|, and add their own rounding difference on values bounded by
-// 16 * prod sum|h|:  e = 2.2 u * 16 * prod_s S_s * sum_s (T_s + 1).
-void band_from_error(double e, float p_star, float &p_lo, float &p_hi);
-double guard_error(const std::vector<std::vector<float>> &stages, double x_max);
-void guard_band(const std::vector<std::vector<float>> &stages, float p_star, float &p_lo, float &p_hi) {
-    if (std::isnan(p_star) || std::isinf(p_star) || p_star <= 0.0f) {
-        p_lo = p_hi = p_star;
-        return;
+    int upload(FrontPlan &&p) {
+        plan = std::move(p);
+        const int rc = d_taps.upload(plan.taps) | d_mfma_a.upload(plan.mfma.image) | d_ctaps.upload(plan.ctaps) |
+                       d_carriers.upload(plan.carrier_tab);
+        base = plan.fp;
+        base.taps = d_taps.p;
+        base.mfma_a = d_mfma_a.p;
+        base.ctaps = d_ctaps.p;
+        if (const char *dbg = dev_getenv("OOKD_MFMA_DEBUG")) base.mfma_debug = (uint32_t)atoi(dbg);
+        return rc;
     }
-    const double u = std::ldexp(1.0, -24);
-    double S = 1.0, T = 0.0, Tsum = 0.0;
-    for (const auto &taps : stages) {
-        double ss = 0.0;
-        for (float t : taps) ss += std::fabs((double)t);
-        S *= std::max(ss, 1.0);         // a stage with gain < 1 still adds its own roundings
-        T += (double)taps.size() + 1.0;
-        Tsum += (double)taps.size();
-    }
-    const double e = 2.2 * T * u * S * 16.0 * (stages.size() > 1 ? 1.01 : 1.0) + Tsum * std::ldexp(1.0, -140);
-    band_from_error(e, p_star, p_lo, p_hi);
-}
-
-// the same bound for samples up to x_max (in units of 2048 LSB) instead of 16
-double guard_error(const std::vector<std::vector<float>> &stages, double x_max) {
-    const double u = std::ldexp(1.0, -24);
-    double S = 1.0, T = 0.0, Tsum = 0.0;
-    for (const auto &taps : stages) {
-        double ss = 0.0;
-        for (float t : taps) ss += std::fabs((double)t);
-        S *= std::max(ss, 1.0);
-        T += (double)taps.size() + 1.0;
-        Tsum += (double)taps.size();
-    }
-    return 2.2 * T * u * S * x_max * (stages.size() > 1 ? 1.01 : 1.0) + Tsum * std::ldexp(1.0, -140);
-}
-
-// [p_lo, p_hi) around p_star for a filter output known to within e per component
-void band_from_error(double e, float p_star, float &p_lo, float &p_hi) {
-    if (std::isnan(p_star) || std::isinf(p_star) || p_star <= 0.0f) {
-        p_lo = p_hi = p_star;
-        return;
-    }
-    const double u = std::ldexp(1.0, -24);
-    const double P = (double)p_star;
-    // |p_ref - p_fma| <= m(p) = 3.003*e*sqrt(p) + 3e^2 + 6u*p
-    // upper edge: smallest s = sqrt(p) with (1-6u)s^2 - 3.003e s - (3e^2 + P) >= 0
-    {
-        const double a = 1.0 - 6.0 * u, b = 3.003 * e, c = 3.0 * e * e + P;
-        double s = (b + std::sqrt(b * b + 4.0 * a * c)) / (2.0 * a);
-        double ph = s * s * (1.0 + 1e-6);
-        ph = std::max(ph, 4.0 * e * e);     // p - m(p) is increasing beyond ~2.3e^2
-        float f = (float)ph;
-        if ((double)f < ph) f = nextafterf(f, INFINITY);
-        f = nextafterf(f, INFINITY);
-        p_hi = std::max(f, p_star);
-    }
-    // lower edge: largest s with (1+6u)s^2 + 3.003e s + 3e^2 - P < 0
-    {
-        const double a = 1.0 + 6.0 * u, b = 3.003 * e, c = 3.0 * e * e - P;
-        if (c >= 0.0) {
-            p_lo = 0.0f;
-        } else {
-            double s = (-b + std::sqrt(b * b - 4.0 * a * c)) / (2.0 * a);
-            double pl = s > 0.0 ? s * s * (1.0 - 1e-6) : 0.0;
-            float f = (float)pl;
-            if ((double)f > pl) f = nextafterf(f, 0.0f);
-            f = nextafterf(f, 0.0f);
-            p_lo = std::max(f, 0.0f);
-        }
-    }
-}
+};
 
 // Which state does every trajectory settle in while the input stays low?
 // Walks the tables from reset with no edges: only always / timeout /
@@ -398,48 +330,15 @@ struct RxHandles {
 struct ookd_rx : RxHandles {
     ookd_rx_config cfg{};
 
-    // filter
-    uint32_t num_stages = 0;
-    FirStageDev stage[kMaxStages]{};
-    uint32_t total_decim = 1;
-    uint64_t halo_needed = 0;
-    std::vector<float> taps0;       // stage-0 true taps (guard band)
-    DevBuf<float> d_taps;
-    float p_star = 0, p_lo = 0, p_hi = 0;
-    // matrix-core form of the 1-stage front end (fir_mfma.hip): A-fragment image, scale, bands; empty = packed-VALU form
-    DevBuf<uint16_t> d_mfma_a;
-    float mfma_c = 0, p_lo_n = 0, p_hi_n = 0, p_lo_w = 0, p_hi_w = 0;
-    uint32_t mfma_g = 0;
-    uint32_t mfma_xcd = 2;          // FrontParams::mfma_xcd (OOKD_MFMA_XCD)
-    // forward bounds the bands were built from (ookd_rx_get_front_info), per component, output units
-    double err_n = 0, err_w = 0, err_valu = 0, mfma_delta = 0;
-    uint32_t mfma_ksteps = 0;
-    uint32_t run_form = 0;          // OOKD_FRONT_* the last run launched (front_form)
-    int quiet_lsb = 0;              // 0 = the quiet shortcut never applies
-    // tuned context (ookd_rx_create_tuned with nu != 0; fir_tuned.hip): complex taps as (re, im) pairs, stage s at
-    // 2 * tap_off, zero padded like d_taps; the tuned quiet test's two weights (FrontParams::quiet_a / quiet_b)
-    double tune_nu = 0.0;
-    DevBuf<float> d_ctaps;
-    float quiet_a = 0, quiet_b = 0;
-    // carrier context (ookd_rx_create_carriers): K carriers of ONE capture, their results where the K captures of a
-    // batched run would be (run_caps == K behind the front end).  d_ctaps holds every carrier's taps one after the
-    // other, carrier k's image (setup_tuned's layout) at tap_off floats; d_carriers is the fused kernel's table.
-    struct Carrier {
-        double nu = 0.0;
-        float threshold = 0, p_star = 0, p_lo = 0, p_hi = 0, quiet_a = INFINITY, quiet_b = INFINITY;
-        double err_valu = 0.0;
-        uint32_t tap_off = 0;
-    };
-    std::vector<Carrier> carriers;
-    DevBuf<TunedCarrierDev> d_carriers;
-    // what a run reports for front_form()'s number: a carrier context's fused form has its own
-    uint32_t reported_form(uint32_t form) const {
-        if (carriers.empty()) return form;
-        return form == OOKD_FRONT_TUNED_FIR1 ? (uint32_t)OOKD_FRONT_TUNED_MULTI : (uint32_t)OOKD_FRONT_TUNED_GENERIC;
-    }
+    // the front end: filter, bands and bounds, the form that runs (constant for the life of the context)
+    FrontDev front;
+    uint32_t total_decim() const { return front.plan.total_decim; }
+    uint64_t halo_needed() const { return front.plan.halo_needed; }
+    uint32_t tile_bits() const { return front.plan.tile_bits; }     // bits per wave tile of the front-end kernel, 0 = generic kernel
+    // carriers of a carrier context (ookd_rx_create_carriers), 0 for every other: K carriers of ONE capture, their
+    // results where the K captures of a batched run would be (run_caps == K behind the front end)
+    uint32_t num_carriers() const { return front.plan.carrier_context() ? (uint32_t)front.plan.carriers.size() : 0u; }
     hipError_t launch_carriers(const FrontParams &fp, hipEvent_t t0, hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count);
-    uint32_t tile_bits = 0;         // bits per wave tile of the front-end kernel (front_tile_bits), 0 = generic kernel
-    bool exact = false;
     bool count_quiet = false;
     DevBuf<uint32_t> d_quiet;       // kQuietCounters spread counters (diagnostics), running totals
     std::vector<uint32_t> quiet_prev;       // what they held after the run before
@@ -536,7 +435,6 @@ struct ookd_rx : RxHandles {
     uint32_t scan_fin_cap = 0;
     uint32_t scan_stamp = 0;        // stamps the finish kernel's block aggregates, never 0
     DevBuf<int16_t> d_stage_in;     // process_host staging (lazy)
-    uint32_t sample_fmt = kFmtSc16; // what captures and halos hold (OOKD_RX_SAMPLES_*)
     // 8-bit contexts, forms without a fused 8-bit kernel: the capture and the halo widened to SC16Q11
     // (allocated by the first run that takes such a form: widen_for_form)
     DevBuf<int16_t> d_widen, d_halo_w;
@@ -567,7 +465,7 @@ struct ookd_rx : RxHandles {
                   uint64_t &words, uint32_t &blocks, uint32_t &segs) const {
         const uint64_t spb = cfg.samples_per_buffer;
         n_in = pad_to_buffer ? ((n_valid + spb - 1) / spb) * spb : n_valid;
-        n_out = n_in / total_decim;
+        n_out = n_in / total_decim();
         const uint64_t tiles = (n_out + kFirTile - 1) / kFirTile;
         words = tiles * (kFirTile / 64);
         blocks = (uint32_t)(words / kBlockWords);
@@ -576,45 +474,21 @@ struct ookd_rx : RxHandles {
     }
 
     FrontParams front_params(const void *d_iq, uint64_t stride) const {
-        FrontParams p{};
+        FrontParams p = front.base;
         p.iq = static_cast<const int16_t *>(d_iq);
         p.cap_stride = stride;
         p.n_valid = run_n_valid;
         p.n_in = run_n_in;
         p.n_out = run_n_out;
-        p.num_stages = num_stages;
-        for (uint32_t s = 0; s < num_stages; ++s) p.stage[s] = stage[s];
-        p.taps = d_taps.p;
         p.bits = d_bits.p;
         p.words_per_cap = run_words;
-        p.fir_out = (cfg.flags & OOKD_RX_KEEP_FIR) ? d_fir.p : nullptr;
-        p.p_star = p_star;
-        p.p_lo = p_lo;
-        p.p_hi = p_hi;
-        p.mfma_a = d_mfma_a.p;
-        p.mfma_c = mfma_c;
-        p.p_lo_n = p_lo_n;
-        p.p_hi_n = p_hi_n;
-        p.p_lo_w = p_lo_w;
-        p.p_hi_w = p_hi_w;
-        p.mfma_g = mfma_g;
-        p.mfma_xcd = mfma_xcd;
-        {
-            static const uint32_t dbg = dev_getenv("OOKD_MFMA_DEBUG") ? (uint32_t)atoi(dev_getenv("OOKD_MFMA_DEBUG")) : 0u;
-            p.mfma_debug = dbg;
-        }
+        p.fir_out = d_fir.p;            // (allocated with OOKD_RX_KEEP_FIR only)
         p.recompute_count = &d_hdr.p->recompute;
-        p.quiet_lsb = quiet_lsb;
         p.quiet_count = count_quiet ? d_quiet.p : nullptr;
         p.tile_info = d_tile_info.p;
-        p.tiles_per_cap = tile_bits ? (uint32_t)(run_words * 64 / tile_bits) : 0;
+        p.tiles_per_cap = tile_bits() ? (uint32_t)(run_words * 64 / tile_bits()) : 0;
         p.sparse = sparse ? 1u : 0u;
         p.stamp_bits = tile_stamp << kTileStampShift;
-        p.sample_fmt = sample_fmt;
-        p.tune = (tune_nu != 0.0 || !carriers.empty()) ? (exact ? 2u : 1u) : 0u;
-        p.ctaps = d_ctaps.p;
-        p.quiet_a = quiet_a;
-        p.quiet_b = quiet_b;
         return p;
     }
 
@@ -631,9 +505,9 @@ struct ookd_rx : RxHandles {
         e.edges = d_edges.p;
         e.edge_capacity = edge_capacity;
         e.overflow = &d_hdr.p->edge_overflow;
-        if (tile_bits && d_tile_info.p) {
+        if (tile_bits() && d_tile_info.p) {
             e.tile_info = d_tile_info.p;
-            e.tiles_per_block = (uint32_t)(kBlockWords * 64) / tile_bits;
+            e.tiles_per_block = (uint32_t)(kBlockWords * 64) / tile_bits();
             e.stamp_bits = tile_stamp << kTileStampShift;
         }
         return e;
@@ -652,7 +526,7 @@ struct ookd_rx : RxHandles {
         f.num_captures = run_caps;
         f.n_out = run_n_out;
         f.spb = cfg.samples_per_buffer;
-        f.total_decim = total_decim;
+        f.total_decim = total_decim();
         f.seg_len = seg_len;
         f.segs_per_cap = run_segs_per_cap;
         f.seg_bounds = d_seg_bounds.p;
@@ -671,10 +545,10 @@ struct ookd_rx : RxHandles {
         f.totals = d_hdr.p->totals;
         f.debug = d_debug.p;
         f.edge_overflow = &d_hdr.p->edge_overflow;
-        if (tile_bits && d_tile_info.p) {
+        if (tile_bits() && d_tile_info.p) {
             f.tile_info = d_tile_info.p;
-            f.tiles_per_cap = (uint32_t)(run_words * 64 / tile_bits);
-            f.tile_shift = (uint32_t)__builtin_ctz(tile_bits);
+            f.tiles_per_cap = (uint32_t)(run_words * 64 / tile_bits());
+            f.tile_shift = (uint32_t)__builtin_ctz(tile_bits());
             f.stamp_bits = tile_stamp << kTileStampShift;
         }
         return f;
@@ -704,7 +578,7 @@ struct ookd_rx : RxHandles {
     bool plan_chunks();
     int run_pipelined(const void *d_iq);
     int prepare_front(FrontParams &fp);
-    int widen_for_form(FrontParams &fp, uint32_t form);
+    int widen_for_form(FrontParams &fp);
     int run_state_machine(const FsmStateDev *first, bool fresh);
     FsmScanArgs scan_args() const;
     int fsm_scan(const FsmStateDev *first);
@@ -727,13 +601,14 @@ struct ookd_rx : RxHandles {
 // An 8-bit context about to run a form that only exists for SC16Q11 (anything but the OOKD_FRONT_*_8 numbers):
 // the run's captures and halo go through the widening kernel into staging buffers, and the front end is
 // pointed at those.  Test and fallback paths: the fused forms never come here and never pay for the buffer.
-int ookd_rx::widen_for_form(FrontParams &fp, uint32_t form) {
+int ookd_rx::widen_for_form(FrontParams &fp) {
+    const uint32_t form = front.plan.form;
     if (fp.sample_fmt == kFmtSc16 || form == OOKD_FRONT_NO_FILTER_8 || form == OOKD_FRONT_FIR1_MFMA_8 ||
         form == OOKD_FRONT_FIR2_MFMA_8) {
         return OOKD_OK;
     }
     // (a carrier context reads one capture whatever its carrier count: one staging copy)
-    const bool one = !carriers.empty();
+    const bool one = num_carriers() != 0;
     if (!d_widen.p) {
         const int rc = d_widen.alloc(2 * (size_t)max_samples * (one ? 1u : max_captures) + 8);
         if (rc != OOKD_OK) return rc;
@@ -743,7 +618,7 @@ int ookd_rx::widen_for_form(FrontParams &fp, uint32_t form) {
     fp.cap_stride = run_n_valid;
     if (fp.halo && fp.halo_len) {
         if (!d_halo_w.p) {
-            const int rc = d_halo_w.alloc(2 * (halo_needed + 4));
+            const int rc = d_halo_w.alloc(2 * (halo_needed() + 4));
             if (rc != OOKD_OK) return rc;
         }
         HIPCHK(launch_widen(fp.halo, fp.sample_fmt, d_halo_w.p, fp.halo_len, 1, 0, 0, stream));
@@ -754,19 +629,19 @@ int ookd_rx::widen_for_form(FrontParams &fp, uint32_t form) {
 }
 
 int ookd_rx::prepare_front(FrontParams &fp) {
-    if (!tile_bits) return OOKD_OK;
+    if (!tile_bits()) return OOKD_OK;
     if (sparse) {
         const uint64_t tiles = (uint64_t)run_caps * fp.tiles_per_cap;
         const bool same = tiles == dirty_tiles && fp.tiles_per_cap == dirty_tiles_per_cap && run_words == dirty_words_per_cap;
         if (tile_stamp >= kTileStampMax) {
-            const uint64_t wpt = tile_bits / 64u;
+            const uint64_t wpt = tile_bits() / 64u;
             const uint64_t all = std::min<uint64_t>(std::min<uint64_t>(d_tile_info.n, d_bits.n / wpt), 0xfffffff8ull) & ~(uint64_t)7;
             // (the tile -> words mapping is linear: the whole buffer as one capture)
-            HIPCHK(launch_clear_tiles(d_tile_info.p, d_bits.p, all, (uint32_t)all, all * wpt, tile_bits, 0u, stream));
+            HIPCHK(launch_clear_tiles(d_tile_info.p, d_bits.p, all, (uint32_t)all, all * wpt, tile_bits(), 0u, stream));
             tile_stamp = 0;
         } else if (!same && dirty_tiles) {
             HIPCHK(launch_clear_tiles(d_tile_info.p, d_bits.p, dirty_tiles, dirty_tiles_per_cap, dirty_words_per_cap,
-                                      tile_bits, 0u, stream));
+                                      tile_bits(), 0u, stream));
         }
         dirty_tiles = tiles;
         dirty_tiles_per_cap = fp.tiles_per_cap;
@@ -784,7 +659,7 @@ int ookd_rx::prepare_front(FrontParams &fp) {
 // left in the current run's extents.
 int ookd_rx::densify_bits() const {
     if (bits_dense || !sparse || !dirty_tiles) return OOKD_OK;
-    HIPCHK(launch_clear_tiles(d_tile_info.p, d_bits.p, dirty_tiles, dirty_tiles_per_cap, dirty_words_per_cap, tile_bits,
+    HIPCHK(launch_clear_tiles(d_tile_info.p, d_bits.p, dirty_tiles, dirty_tiles_per_cap, dirty_words_per_cap, tile_bits(),
                               tile_stamp << kTileStampShift, stream));
     HIPCHK(hipStreamSynchronize(stream));
     bits_dense = true;
@@ -812,9 +687,9 @@ bool ookd_rx::plan_chunks() {
     if (!pipe_ok || no_pipeline_once || run_caps != 1 || run_n_out == 0) return false;
     const uint64_t spb = cfg.samples_per_buffer;
     // boundary (decimated index) o: o % 4096 == 0 and o * D % spb == 0
-    const uint64_t per_buf = spb / gcd64(spb, total_decim);
+    const uint64_t per_buf = spb / gcd64(spb, total_decim());
     const uint64_t align = (uint64_t)kFirTile / gcd64(kFirTile, per_buf) * per_buf;
-    const uint64_t target = std::max<uint64_t>(align, pipe_chunk_in / total_decim / align * align);
+    const uint64_t target = std::max<uint64_t>(align, pipe_chunk_in / total_decim() / align * align);
     if (run_n_out < 2 * target) return false;
     std::vector<uint64_t> sizes;
     uint64_t left = run_n_out;
@@ -823,7 +698,7 @@ bool ookd_rx::plan_chunks() {
         left -= target;
     }
     // the tail shrinks: the chain of the last chunk is all that is not hidden behind a front end
-    const uint64_t tail_min = std::max<uint64_t>(align, kPipeTailChunk / total_decim / align * align);
+    const uint64_t tail_min = std::max<uint64_t>(align, kPipeTailChunk / total_decim() / align * align);
     while (left > 2 * tail_min && sizes.size() + 2 < (size_t)kMaxChunks) {
         uint64_t half = left / 2 / align * align;
         if (half < tail_min) break;
@@ -860,9 +735,8 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     if (hdr_dirty) HIPCHK(hipMemsetAsync(d_hdr.p, 0, sizeof(ResultHeader), stream));
     hdr_dirty = true;
     FrontParams fp = front_params(d_iq, run_n_valid);
-    run_form = front_form(fp, exact);
     {
-        int rc = widen_for_form(fp, run_form);
+        int rc = widen_for_form(fp);
         if (rc == OOKD_OK) rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
     }
@@ -870,7 +744,7 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     HIPCHK(hipStreamWaitEvent(s_front, ev_start, 0));
     HIPCHK(hipStreamWaitEvent(s_chain, ev_start, 0));
 
-    const uint32_t tiles_per_block = (uint32_t)kFirTile / tile_bits;
+    const uint32_t tiles_per_block = (uint32_t)kFirTile / tile_bits();
     scan_used = false;
     scan_pending = true;
     stats.fsm_path = 0;
@@ -881,7 +755,7 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     // the host still queueing the (ten times as many) chain kernels behind
     for (size_t c = 0; c < nc; ++c) {
         const Chunk &ch = chunks[c];
-        HIPCHK(launch_front(fp, 1, exact, s_front, ev_c0[c], ev_c1[c], (uint64_t)ch.blk0 * tiles_per_block,
+        HIPCHK(launch_front(fp, 1, front.plan.exact, s_front, ev_c0[c], ev_c1[c], (uint64_t)ch.blk0 * tiles_per_block,
                             (uint64_t)ch.nblk * tiles_per_block));
     }
     // one scan form for every chunk: a refusal anywhere redoes the capture whole
@@ -942,16 +816,16 @@ int ookd_rx::run_pipelined(const void *d_iq) {
 // tuned kernel once per carrier, each launch with that carrier's taps, threshold and result planes.
 hipError_t ookd_rx::launch_carriers(const FrontParams &fp, hipEvent_t t0, hipEvent_t t1, uint64_t tile_begin,
                                     uint64_t tile_count) {
-    const uint32_t K = (uint32_t)carriers.size();
-    if (fp.n_out != 0 && run_form == OOKD_FRONT_TUNED_MULTI) {
-        return launch_front_tuned_multi(fp, d_carriers.p, K, stream, t0, t1, tile_begin, tile_count);
+    const uint32_t K = num_carriers();
+    if (fp.n_out != 0 && front.plan.form == OOKD_FRONT_TUNED_MULTI) {
+        return launch_front_tuned_multi(fp, front.d_carriers.p, K, stream, t0, t1, tile_begin, tile_count);
     }
     if (tile_begin != 0 || tile_count != ~0ull) return hipErrorInvalidValue;    // the generic kernel runs whole captures
     if (t0 && hipEventRecord(t0, stream) != hipSuccess) return hipGetLastError();
     for (uint32_t k = 0; k < K && fp.n_out != 0; ++k) {
         FrontParams pk = fp;
-        pk.ctaps = d_ctaps.p + carriers[k].tap_off;
-        pk.p_star = carriers[k].p_star;
+        pk.ctaps = fp.ctaps + front.plan.carriers[k].tap_off;
+        pk.p_star = front.plan.carriers[k].p_star;
         pk.bits = fp.bits + (size_t)k * run_words;
         if (fp.fir_out) pk.fir_out = fp.fir_out + 2 * (size_t)k * run_n_out;
         const hipError_t e = launch_front_tuned_generic(pk, 1, stream);
@@ -968,9 +842,8 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
     FrontParams fp = front_params(d_iq, stride);
     fp.halo = d_halo_ptr;
     fp.halo_len = halo_len;
-    run_form = reported_form(front_form(fp, exact));
     {
-        int rc = widen_for_form(fp, front_form(fp, exact));
+        int rc = widen_for_form(fp);
         if (rc == OOKD_OK) rc = prepare_front(fp);
         if (rc != OOKD_OK) return rc;
     }
@@ -980,17 +853,17 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
     // they get their turn when a front-end launch has drained (profiles/r02_pipeline_trace.txt),
     // and once dispatched they run beside the next launch.  ev[0] / ev[1] = start of the first,
     // end of the last launch.
-    const uint64_t tiles = tile_bits ? (uint64_t)fp.tiles_per_cap : 0;
+    const uint64_t tiles = tile_bits() ? (uint64_t)fp.tiles_per_cap : 0;
     // (a carrier context's grid covers the one capture it reads, whatever its carrier count)
-    const uint32_t read_caps = carriers.empty() ? run_caps : 1u;
-    const uint64_t per = tile_bits ? std::max<uint64_t>(1, front_launch_outputs / tile_bits / std::max(1u, read_caps)) : 0;
+    const uint32_t read_caps = num_carriers() ? 1u : run_caps;
+    const uint64_t per = tile_bits() ? std::max<uint64_t>(1, front_launch_outputs / tile_bits() / std::max(1u, read_caps)) : 0;
     auto launch_range = [&](hipEvent_t e0, hipEvent_t e1, uint64_t t, uint64_t n) -> hipError_t {
-        if (!carriers.empty()) return launch_carriers(fp, e0, e1, t, n);
-        return launch_front(fp, run_caps, exact, stream, e0, e1, t, n);
+        if (num_carriers()) return launch_carriers(fp, e0, e1, t, n);
+        return launch_front(fp, run_caps, front.plan.exact, stream, e0, e1, t, n);
     };
     auto launch_all = [&]() -> hipError_t {
         front_launches = 1;
-        if (!tile_bits || tiles <= per + per / 2) return launch_range(ev[0], ev[1], 0, ~0ull);
+        if (!tile_bits() || tiles <= per + per / 2) return launch_range(ev[0], ev[1], 0, ~0ull);
         front_launches = (uint32_t)((tiles + per - 1) / per);
         for (uint64_t t = 0; t < tiles; t += per) {
             const bool first = t == 0, last = t + per >= tiles;
@@ -1422,7 +1295,7 @@ int ookd_rx::collect_results() {
     stats.num_messages = 0;
     stats.num_errors = 0;
     stats.guard_recomputes = h_hdr->recompute;
-    stats.front_form = run_form;
+    stats.front_form = front.plan.form;
     stats.total_waves = front_wave_tiles(front_params(nullptr, 0)) * run_caps;
     if (stats.total_waves) {
         if (count_quiet) {
@@ -1499,270 +1372,6 @@ int ookd_rx::collect_results() {
 // ---------------------------------------------------------------------------
 namespace {
 
-// stages and their (padded) taps on the device
-bool setup_filter(ookd_rx &rx, const ookd_filter &filter) {
-    if (filter.stages.size() > (size_t)kMaxStages) {
-        set_error("filter has %zu stages, this build supports %d", filter.stages.size(), kMaxStages);
-        return false;
-    }
-    std::vector<float> taps_dev;
-    rx.num_stages = (uint32_t)filter.stages.size();
-    rx.total_decim = filter.total_decimation;
-    uint64_t mult = 1;
-    for (uint32_t s = 0; s < rx.num_stages; ++s) {
-        const auto &st = filter.stages[s];
-        FirStageDev d{};
-        d.decim = st.decimation;
-        d.ntaps = (uint32_t)st.taps.size();
-        d.ntaps_pad = ((d.ntaps + kTapChunk - 1) / kTapChunk) * kTapChunk;
-        d.tap_off = (uint32_t)taps_dev.size();
-        taps_dev.insert(taps_dev.end(), st.taps.begin(), st.taps.end());
-        // zero padding keeps sums bit-identical: acc + (+-0) == acc
-        taps_dev.resize(d.tap_off + d.ntaps_pad, 0.0f);
-        rx.stage[s] = d;
-        rx.halo_needed += (uint64_t)(d.ntaps - 1) * mult;
-        mult *= d.decim;
-    }
-    rx.taps0 = filter.stages[0].taps;
-    if (rx.d_taps.alloc(taps_dev.size()) != OOKD_OK) return false;
-    if (hipMemcpy(rx.d_taps.p, taps_dev.data(), taps_dev.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("tap upload failed");
-        return false;
-    }
-    return true;
-}
-
-// The matrix-core form of the front end (fir_mfma.hip) for taps prepared in mt, whose output is known to
-// within e_n (inputs up to 1, in units of 2048 LSB) or e_w (up to 16) per component.  Filters the band
-// scaling does not suit stay on the packed-VALU kernels: that is not a failure.
-bool setup_mfma(ookd_rx &rx, const MfmaTaps &mt, double e_n, double e_w) {
-    rx.err_n = e_n;
-    rx.err_w = e_w;
-    rx.mfma_ksteps = mt.ksteps;
-    rx.mfma_delta = mt.delta;
-    float lo_n, hi_n, lo_w, hi_w;
-    band_from_error(e_n, rx.p_star, lo_n, hi_n);
-    band_from_error(e_w, rx.p_star, lo_w, hi_w);
-    // the kernel compares in accumulator units; thresholds so far from the filter's range that the
-    // power-of-two scaling leaves the normal floats stay on the packed-VALU loop
-    if (!(mfma_scale_band(mt, lo_n, rx.p_lo_n) && mfma_scale_band(mt, hi_n, rx.p_hi_n) &&
-          mfma_scale_band(mt, lo_w, rx.p_lo_w) && mfma_scale_band(mt, hi_w, rx.p_hi_w))) {
-        return true;
-    }
-    // fl(y^2) = c^2 fl(z^2) needs y^2 clear of the subnormals (and of overflow) wherever it decides a bit
-    if (rx.p_star > 0.0f && !(rx.p_star >= 0x1p-100f && rx.p_star <= 0x1p100f)) return true;
-    if (rx.d_mfma_a.alloc(mt.image.size()) != OOKD_OK) return false;
-    if (hipMemcpy(rx.d_mfma_a.p, mt.image.data(), mt.image.size() * sizeof(uint16_t), hipMemcpyHostToDevice) !=
-        hipSuccess) {
-        set_error("tap image upload failed");
-        return false;
-    }
-    rx.mfma_c = mt.c;
-    // wave tiles per wave of a workgroup: more for the long filters, whose workgroups fill a CU and
-    // fetch a 20 / 36 KB image each (config2 sweep: 474 / 545 / 599 / 623 / 635 Gsamples/s at 2 / 4 / 8 / 16 / 32)
-    rx.mfma_g = mt.ksteps <= 6 ? 4u : mt.ksteps <= 10 ? 16u : 32u;
-    if (const char *g = dev_getenv("OOKD_MFMA_G")) rx.mfma_g = (uint32_t)std::min(4096, std::max(1, atoi(g)));
-    // one contiguous run of tiles per XCD: where the halo is a good share of a tile's window -- the decimate-by-4
-    // filter (96 of 1120 samples: 3.0 -> 2.8-2.9 ms per 16 GiB) and the long 1-stage filters (272 of 1296: 1 %)
-    rx.mfma_xcd = 2u | (mt.ksteps >= 10 ? 1u : 0u);
-    if (const char *x = dev_getenv("OOKD_MFMA_XCD")) rx.mfma_xcd = (uint32_t)atoi(x);
-    return true;
-}
-
-// Guard band of the tuned kernels (1 stage / decimation 1, and 2 x decimation 2; the generic kernel
-// always computes in reference order and ignores it), and the matrix-core form where the shape has one
-// and the caller does not ask for the packed-VALU loop.
-bool setup_front_form(ookd_rx &rx, const ookd_filter &filter, uint32_t flags) {
-    std::vector<std::vector<float>> st;
-    for (const auto &f : filter.stages) st.push_back(f.taps);
-    guard_band(st, rx.p_star, rx.p_lo, rx.p_hi);
-    rx.err_valu = guard_error(st, 16.0);
-    if ((flags & OOKD_RX_FIR_VALU) || dev_getenv("OOKD_FIR_VALU")) return true;
-    MfmaTaps mt;
-    if (rx.num_stages == 2 && rx.stage[0].decim == 2 && rx.stage[1].decim == 2 &&
-        mfma_prepare_taps2(filter.stages[0].taps.data(), rx.stage[0].ntaps, filter.stages[1].taps.data(),
-                           rx.stage[1].ntaps, mt)) {
-        // the backend default shape (two decimate-by-2 stages) folded into one decimate-by-4 product
-        return setup_mfma(rx, mt, mfma_error_bound2(mt, guard_error(st, 1.0), false),
-                          mfma_error_bound2(mt, guard_error(st, 16.0), true));
-    }
-    // 1 stage, decimation 1, <= 256 taps
-    if (rx.num_stages == 1 && rx.stage[0].decim == 1 && mfma_prepare_taps(filter.stages[0].taps.data(), rx.stage[0].ntaps, mt)) {
-        return setup_mfma(rx, mt, mfma_error_bound(mt, rx.stage[0].ntaps, false), mfma_error_bound(mt, rx.stage[0].ntaps, true));
-    }
-    return true;
-}
-
-// The quiet shortcut: input levels below quiet_lsb cannot reach the threshold.
-void setup_quiet_skip(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg) {
-    if (!(cfg.threshold > 0.0f) || !std::isfinite(cfg.threshold) || (cfg.flags & OOKD_RX_NO_QUIET_SKIP)) return;
-    // |y_re|, |y_im| <= S * m with S = prod over stages of sum|h|, m = max |component| in
-    // the window, so |y| <= sqrt(2) * S * m; 0.1 % slack covers every rounding of the
-    // reference's float arithmetic (relative 1e-5 at most) many times over
-    double S = 1.0;
-    for (const auto &st : filter.stages) {
-        double ss = 0.0;
-        for (float t : st.taps) ss += std::fabs((double)t);
-        S *= ss;
-    }
-    if (S > 0.0) {
-        // |v| < quiet_lsb  <=>  |v|/2048 < level (complexf.h:68-77 scaling)
-        const double lvl = (double)cfg.threshold * 0.999 / (1.41421356237309515 * S) * 2048.0;
-        rx.quiet_lsb = lvl >= 32767.0 ? 32767 : (int)std::ceil(lvl);
-    }
-}
-
-// A tuned context's front end (fir_tuned.hip): the complex taps on the device, the guard band of the packed-FMA
-// kernel and its quiet test.  Replaces setup_front_form / setup_quiet_skip; setup_filter has run.
-//
-// Guard band.  One component of an output is a sum of 2T products (T taps, a real and an imaginary tap part
-// each), sum_k |terms| <= S x_max with S = sum_k (|re[k]| + |im[k]|) and x_max = 16 (32768 / 2048).  The fused
-// chain rounds once per step, the contract's chain twice (product, sum): both stay within gamma_{2T} resp.
-// gamma_{2T+1} of the exact sum times sum|terms| (gamma_n = n u / (1 - n u), u = 2^-24), so they differ by at most
-// (4T + 1) u S x_max (1 + O(T u)) <= 2.2 (2T + 1) u S x_max -- guard_error's form with twice the roundings per
-// tap and both tap parts in S; the 2^-140 term covers products and sums that round in the subnormals.
-// band_from_error turns it into [p_lo, p_hi) as for the real-tap kernels.  Several stages: as guard_error (each
-// stage amplifies what it is handed by at most its S and adds its own term); the generic tuned kernel computes in
-// the contract's order and needs no band, the figure is reported all the same.
-double tuned_guard_error(const std::vector<std::vector<float>> &re, const std::vector<std::vector<float>> &im, double x_max) {
-    const double u = std::ldexp(1.0, -24);
-    double S = 1.0, T = 0.0, Tsum = 0.0;
-    for (size_t s = 0; s < re.size(); ++s) {
-        double ss = 0.0;
-        for (size_t k = 0; k < re[s].size(); ++k) ss += std::fabs((double)re[s][k]) + std::fabs((double)im[s][k]);
-        S *= std::max(ss, 1.0);
-        T += 2.0 * (double)re[s].size() + 1.0;
-        Tsum += 2.0 * (double)re[s].size();
-    }
-    return 2.2 * T * u * S * x_max * (re.size() > 1 ? 1.01 : 1.0) + Tsum * std::ldexp(1.0, -140);
-}
-
-// Quiet test of fir1_tuned_kernel.  For any constant d:  y = sum_k c[k] (x[n-k] - d) + d sum_k c[k], so
-//     |y| <= A max|x - d| + G |d|,   A = sum_k |c[k]|,  G = |sum_k c[k]|  (the rounded taps' response at 0 Hz).
-// The kernel takes d = the midpoint of the window's component ranges: with a = the larger range and b = the
-// larger |min + max| (raw LSB), max|x - d| <= sqrt(2) a / 2 and |d| <= sqrt(2) b / 2.  The contract's float chain
-// is within gamma_{2T+1} S x_max of y per component (S as above, x_max <= (a + b) / 2 LSB), sqrt(2) times that in
-// magnitude.  So the computed |y| stays below the threshold when
-//     sqrt(2) / (2 * 2048) * ((A + e) a + (G + e) b) < 0.999 thr,      e = 1.01 (2T + 1) u S,
-// the 0.1 % covering the power's own three roundings and this test's float evaluation.  Only interior windows
-// are tested (every sample a capture sample), and only the 1-stage kernel has the test.
-bool tuned_quiet_weights(const std::vector<float> &re, const std::vector<float> &im, float threshold, uint32_t flags,
-                         float &quiet_a, float &quiet_b) {
-    if (!(threshold > 0.0f) || !std::isfinite(threshold) || (flags & OOKD_RX_NO_QUIET_SKIP)) return false;
-    double A = 0.0, S = 0.0, gr = 0.0, gi = 0.0;
-    for (size_t k = 0; k < re.size(); ++k) {
-        A += std::hypot((double)re[k], (double)im[k]);
-        S += std::fabs((double)re[k]) + std::fabs((double)im[k]);
-        gr += (double)re[k];
-        gi += (double)im[k];
-    }
-    if (!(A > 0.0)) return false;
-    const double G = std::hypot(gr, gi) + 1e-12 * S;        // (the double sums' own rounding)
-    const double e = 1.01 * (2.0 * (double)re.size() + 1.0) * std::ldexp(1.0, -24) * S;
-    const double scale = 1.41421356237309515 / (2.0 * 2048.0) / (0.999 * (double)threshold);
-    const double qa = (A + e) * scale, qb = (G + e) * scale;
-    if (!(qa < 1e30) || !(qb < 1e30)) return false;
-    quiet_a = nextafterf((float)qa, INFINITY);
-    quiet_b = nextafterf((float)qb, INFINITY);
-    return true;
-}
-
-// Host side of one carrier at c.nu with c.threshold / c.p_star: its taps in the device layout (stage s at
-// 2 * tap_off, zero padded to ntaps_pad pairs) and, unless the context computes in the contract's order throughout,
-// its forward bound, guard band and quiet weights.  -> the quiet test applies to this carrier
-bool tuned_carrier_host(const ookd_rx &rx, const ookd_filter &filter, uint32_t flags, std::vector<float> &dev,
-                        ookd_rx::Carrier &c) {
-    std::vector<std::vector<float>> re, im;
-    dev.clear();
-    uint64_t before = 1;
-    for (uint32_t s = 0; s < rx.num_stages; ++s) {
-        const std::vector<float> &h = filter.stages[s].taps;
-        re.emplace_back(h.size());
-        im.emplace_back(h.size());
-        tuned_stage_taps(h, c.nu, before, re[s].data(), im[s].data());
-        before *= filter.stages[s].decimation;
-        // zero padding keeps sums bit-identical, as in setup_filter
-        dev.resize(2 * (size_t)(rx.stage[s].tap_off + rx.stage[s].ntaps_pad), 0.0f);
-        for (size_t k = 0; k < h.size(); ++k) {
-            dev[2 * (rx.stage[s].tap_off + k)] = re[s][k];
-            dev[2 * (rx.stage[s].tap_off + k) + 1] = im[s][k];
-        }
-    }
-    if (rx.exact) return false;
-    c.err_valu = tuned_guard_error(re, im, 16.0);
-    band_from_error(c.err_valu, c.p_star, c.p_lo, c.p_hi);
-    // (the shape front_uses_tuned_fir1 takes: the only tuned kernels with a quiet test)
-    return rx.num_stages == 1 && rx.stage[0].decim == 1 && rx.stage[0].ntaps_pad <= 256u &&
-           tuned_quiet_weights(re[0], im[0], c.threshold, flags, c.quiet_a, c.quiet_b);
-}
-
-bool upload_ctaps(ookd_rx &rx, const std::vector<float> &dev) {
-    if (rx.d_ctaps.alloc(dev.size()) != OOKD_OK) return false;
-    if (hipMemcpy(rx.d_ctaps.p, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("tuned tap upload failed");
-        return false;
-    }
-    return true;
-}
-
-bool setup_tuned(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg) {
-    ookd_rx::Carrier c;
-    c.nu = rx.tune_nu;
-    c.threshold = cfg.threshold;
-    c.p_star = c.p_lo = c.p_hi = rx.p_star;
-    std::vector<float> dev;
-    const bool quiet = tuned_carrier_host(rx, filter, cfg.flags, dev, c);
-    if (!upload_ctaps(rx, dev)) return false;
-    rx.err_valu = c.err_valu;
-    rx.p_lo = c.p_lo;
-    rx.p_hi = c.p_hi;
-    if (quiet) {
-        rx.quiet_a = c.quiet_a;
-        rx.quiet_b = c.quiet_b;
-        rx.quiet_lsb = 1;       // "the shortcut applies": the tuned kernel tests with quiet_a / quiet_b
-    }
-    return true;
-}
-
-// A carrier context's front end: setup_tuned per carrier, the taps behind one another, the fused kernel's table.
-bool setup_carriers(ookd_rx &rx, const ookd_filter &filter, const ookd_rx_config &cfg, const ookd_rx_carrier *in,
-                    uint32_t num_carriers) {
-    std::vector<float> all, dev;
-    std::vector<TunedCarrierDev> tab(num_carriers);
-    for (uint32_t k = 0; k < num_carriers; ++k) {
-        ookd_rx::Carrier c;
-        c.nu = in[k].nu == 0.0 ? 0.0 : in[k].nu;
-        c.threshold = in[k].threshold;
-        c.p_star = c.p_lo = c.p_hi = power_threshold(c.threshold);
-        // (a carrier without a quiet test keeps its infinite weights: never quiet)
-        if (tuned_carrier_host(rx, filter, cfg.flags, dev, c)) rx.quiet_lsb = 1;
-        else c.quiet_a = c.quiet_b = INFINITY;
-        c.tap_off = (uint32_t)all.size();
-        all.insert(all.end(), dev.begin(), dev.end());
-        TunedCarrierDev &t = tab[k];
-        t = TunedCarrierDev{};
-        t.tap_off = c.tap_off;
-        t.p_star = c.p_star;
-        t.p_lo = c.p_lo;
-        t.p_hi = c.p_hi;
-        t.quiet_a = c.quiet_a;
-        t.quiet_b = c.quiet_b;
-        rx.carriers.push_back(c);
-    }
-    if (!upload_ctaps(rx, all)) return false;
-    if (rx.d_carriers.alloc(tab.size()) != OOKD_OK) return false;
-    if (hipMemcpy(rx.d_carriers.p, tab.data(), tab.size() * sizeof(TunedCarrierDev), hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("carrier table upload failed");
-        return false;
-    }
-    // what ookd_rx_get_front_info reports: carrier 0's (every carrier's: ookd_rx_get_carrier_front_info)
-    rx.p_star = rx.carriers[0].p_star;
-    rx.p_lo = rx.carriers[0].p_lo;
-    rx.p_hi = rx.carriers[0].p_hi;
-    rx.err_valu = rx.carriers[0].err_valu;
-    return true;
-}
-
 // The state machine's tables on the device
 bool setup_device_tables(ookd_rx &rx, const ookd_device &device) {
     const size_t ns = device.state_duration_us.size();
@@ -1816,7 +1425,7 @@ bool setup_run_buffers(ookd_rx &rx, const ookd_rx_config &cfg) {
     // nominal decimated samples per state machine segment (~2^19 by default;
     // segment_buffers expresses it in input buffers)
     if (cfg.segment_buffers) {
-        rx.seg_len = std::max<uint64_t>(1, (uint64_t)cfg.segment_buffers * spb / rx.total_decim);
+        rx.seg_len = std::max<uint64_t>(1, (uint64_t)cfg.segment_buffers * spb / rx.total_decim());
     } else {
         rx.seg_len = 1ull << 19;
     }
@@ -1838,7 +1447,7 @@ bool setup_run_buffers(ookd_rx &rx, const ookd_rx_config &cfg) {
     int rc = OOKD_OK;
     rc |= rx.d_bits.alloc(caps * rx.max_words + 64);
     if (cfg.flags & OOKD_RX_KEEP_FIR) rc |= rx.d_fir.alloc(2 * caps * rx.max_n_out + 2);
-    rc |= rx.d_halo.alloc(2 * (rx.halo_needed + 4));
+    rc |= rx.d_halo.alloc(2 * (rx.halo_needed() + 4));
     rc |= rx.d_blk_count.alloc(caps * blocks + 1);
     rc |= rx.d_tile_info.alloc(caps * blocks * 16 + 16);       // smallest wave tile: 256 bits
     if (const char *w = dev_getenv("OOKD_FRONT_LAUNCH_LOG2")) rx.front_launch_outputs = 1ull << std::min(40, std::max(16, atoi(w)));
@@ -1913,7 +1522,7 @@ bool setup_scan(ookd_rx &rx, const ookd_device &device, const ookd_rx_config &cf
     if (!rx.scan_ok) return true;
     const bool with_spans = !(cfg.flags & OOKD_RX_SCAN_SIMS);
     const auto t0 = std::chrono::steady_clock::now();
-    ScanTables t = build_scan_tables(*rx.h_tables, cfg.samples_per_buffer, rx.total_decim, with_spans);
+    ScanTables t = build_scan_tables(*rx.h_tables, cfg.samples_per_buffer, rx.total_decim(), with_spans);
     if (with_spans && getenv("OOKD_DEBUG")) {
         size_t zeros = 0;
         for (uint32_t v : t.pk) zeros += v == 0;
@@ -1942,9 +1551,7 @@ bool setup_scan(ookd_rx &rx, const ookd_device &device, const ookd_rx_config &cf
 bool setup_results(ookd_rx &rx) {
     // sparse front-end output (1-stage kernels with the quiet shortcut, no float dump): the bit
     // words and tile infos start out zero and every run zeroes what the run before wrote
-    FrontParams probe = rx.front_params(nullptr, 0);
-    probe.n_out = rx.max_n_out;
-    rx.sparse = front_sparse_capable(probe) && !dev_getenv("OOKD_DENSE_BITS");
+    rx.sparse = rx.front.plan.sparse_capable && !dev_getenv("OOKD_DENSE_BITS");
     if (rx.sparse &&
         (hipMemset(rx.d_bits.p, 0, rx.d_bits.n * sizeof(uint64_t)) != hipSuccess ||
          hipMemset(rx.d_tile_info.p, 0, rx.d_tile_info.n * sizeof(uint32_t)) != hipSuccess)) {
@@ -1973,9 +1580,9 @@ bool setup_pipeline(ookd_rx &rx, const ookd_rx_config &cfg) {
     uint64_t want = cfg.pipeline_chunk_samples;
     if (!want && dev_getenv("OOKD_PIPELINE")) want = kPipeDefaultChunk;
     rx.pipe_chunk_in = want ? want : kPipeDefaultChunk;
-    rx.pipe_ok = want != 0 && rx.carriers.empty() && rx.have_fsm && rx.scan_ok && rx.tile_bits != 0 && !(cfg.flags & OOKD_RX_NO_PIPELINE) &&
+    rx.pipe_ok = want != 0 && !rx.num_carriers() && rx.have_fsm && rx.scan_ok && rx.tile_bits() != 0 && !(cfg.flags & OOKD_RX_NO_PIPELINE) &&
                  cfg.pipeline_chunk_samples != ~0ull && !dev_getenv("OOKD_NO_PIPELINE") &&
-                 rx.max_n_out >= 2 * (rx.pipe_chunk_in / rx.total_decim);
+                 rx.max_n_out >= 2 * (rx.pipe_chunk_in / rx.total_decim());
     if (!rx.pipe_ok) return true;
     // every other CU of every XCD for the front end, the rest for the chain (an UNEVEN mask
     // slows the front end: the dispatcher deals workgroups evenly over the XCDs).
@@ -2018,23 +1625,20 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
     return ookd_rx_create_tuned(cfg, filter, device, nullptr);
 }
 
-double ookd_rx_tune(const ookd_rx *rx) { return rx ? rx->tune_nu : 0.0; }
+double ookd_rx_tune(const ookd_rx *rx) {
+    // (a tuned context is one carrier record and no table)
+    return rx && !rx->num_carriers() && !rx->front.plan.carriers.empty() ? rx->front.plan.carriers[0].nu : 0.0;
+}
 
 // the body of every create call: a context tuned to nu, or (num_carriers != 0) a carrier context
 static ookd_rx *create_context(const ookd_rx_config *cfg, const ookd_filter *filter, const ookd_device *device,
                                double nu, const ookd_rx_carrier *carriers, uint32_t num_carriers) {
-    if (!(std::fabs(nu) <= 0.5)) {
-        set_error("ookd_rx_create_tuned: nu must be within [-0.5, 0.5] cycles per sample");
-        return nullptr;
-    }
-    if (nu != 0.0 && !filter) {
-        set_error("ookd_rx_create_tuned: nu != 0 needs a filter: without one the slicer sees |x|, which does not depend on nu");
-        return nullptr;
-    }
     if (!cfg || cfg->samples_per_buffer == 0 || cfg->max_samples == 0) {
         set_error("ookd_rx_create: samples_per_buffer and max_samples must be non-zero");
         return nullptr;
     }
+    FrontPlan plan;
+    if (!plan_front(cfg->flags, cfg->threshold, filter, nu, carriers, num_carriers, plan)) return nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available: libookiedokie_amd has no CPU fallback");
@@ -2066,32 +1670,14 @@ static ookd_rx *create_context(const ookd_rx_config *cfg, const ookd_filter *fil
             return nullptr;
         }
     }
-    rx->exact = (cfg->flags & OOKD_RX_EXACT_FIR) != 0;
-    if ((cfg->flags & OOKD_RX_SAMPLES_CS8) && (cfg->flags & OOKD_RX_SAMPLES_CU8)) {
-        set_error("ookd_rx_create: OOKD_RX_SAMPLES_CS8 and OOKD_RX_SAMPLES_CU8 are both set: a context has one sample format");
-        return nullptr;
-    }
-    rx->sample_fmt = (cfg->flags & OOKD_RX_SAMPLES_CS8) ? kFmtCs8 : (cfg->flags & OOKD_RX_SAMPLES_CU8) ? kFmtCu8 : kFmtSc16;
     // (a carrier context's results are those of a batch of num_carriers captures)
     rx->max_captures = num_carriers ? num_carriers : cfg->max_captures ? cfg->max_captures : 1;
     rx->max_samples = cfg->max_samples;
 
-    if (filter && !setup_filter(*rx, *filter)) return nullptr;
-    rx->p_star = power_threshold(cfg->threshold);
-    rx->p_lo = rx->p_hi = rx->p_star;
-    rx->tune_nu = nu == 0.0 ? 0.0 : nu;
-    if (num_carriers) {
-        if (!setup_carriers(*rx, *filter, *cfg, carriers, num_carriers)) return nullptr;
-    } else if (rx->tune_nu != 0.0) {
-        if (!setup_tuned(*rx, *filter, *cfg)) return nullptr;
-    } else {
-        if (filter && !rx->exact && !setup_front_form(*rx, *filter, cfg->flags)) return nullptr;
-        if (filter) setup_quiet_skip(*rx, *filter, *cfg);
-    }
+    if (rx->front.upload(std::move(plan)) != OOKD_OK) return nullptr;
     if (device && !setup_device_tables(*rx, *device)) return nullptr;
     if (!setup_run_buffers(*rx, *cfg)) return nullptr;
     if (rx->have_fsm && !setup_scan(*rx, *device, *cfg)) return nullptr;
-    rx->tile_bits = front_tile_bits(rx->front_params(nullptr, 0));     // the front end's form is settled
     if (!setup_results(*rx) || !setup_pipeline(*rx, *cfg)) return nullptr;
     rx->gate = static_cast<ookd_rx_gate *>(cfg->front_gate);
     // (tests: start the tile stamp near its wrap-around)
@@ -2126,10 +1712,6 @@ ookd_rx *ookd_rx_create_carriers(const ookd_rx_config *cfg, const ookd_filter *f
             }
         }
     }
-    if (!filter) {
-        set_error("ookd_rx_create_carriers needs a filter: without one the slicer sees |x|, which does not depend on nu");
-        return nullptr;
-    }
     if (cfg && cfg->max_captures > 1) {
         set_error("ookd_rx_create_carriers: a carrier context runs one capture per run (max_captures = %u)", cfg->max_captures);
         return nullptr;
@@ -2137,23 +1719,23 @@ ookd_rx *ookd_rx_create_carriers(const ookd_rx_config *cfg, const ookd_filter *f
     return create_context(cfg, filter, device, 0.0, carriers, num_carriers);
 }
 
-uint32_t ookd_rx_num_carriers(const ookd_rx *rx) { return rx ? (uint32_t)rx->carriers.size() : 0u; }
+uint32_t ookd_rx_num_carriers(const ookd_rx *rx) { return rx ? rx->num_carriers() : 0u; }
 
 int ookd_rx_get_carrier(const ookd_rx *rx, uint32_t k, ookd_rx_carrier *out) {
     clear_error();
-    if (!rx || !out || k >= rx->carriers.size()) {
+    if (!rx || !out || k >= rx->num_carriers()) {
         set_error("ookd_rx_get_carrier: bad argument");
         return OOKD_ERR_ARG;
     }
     *out = ookd_rx_carrier{};
-    out->nu = rx->carriers[k].nu;
-    out->threshold = rx->carriers[k].threshold;
+    out->nu = rx->front.plan.carriers[k].nu;
+    out->threshold = rx->front.plan.carriers[k].threshold;
     return OOKD_OK;
 }
 
 void ookd_rx_destroy(ookd_rx *rx) { delete rx; }
 
-uint32_t ookd_rx_sample_bytes(const ookd_rx *rx) { return rx ? sample_bytes(rx->sample_fmt) : 0u; }
+uint32_t ookd_rx_sample_bytes(const ookd_rx *rx) { return rx ? sample_bytes(rx->front.base.sample_fmt) : 0u; }
 
 ookd_rx_gate *ookd_rx_gate_create(void) { return new (std::nothrow) ookd_rx_gate(); }
 
@@ -2170,7 +1752,7 @@ int ookd_rx_submit_device(ookd_rx *rx, const void *d_iq, uint32_t num_captures,
         set_error("ookd_rx_submit_device: the previous run has not been waited for");
         return OOKD_ERR_ARG;
     }
-    if (!rx->carriers.empty() && num_captures != 1) {
+    if (rx->num_carriers() && num_captures != 1) {
         set_error("a carrier context runs one capture per run (num_captures = %u)", num_captures);
         return OOKD_ERR_ARG;
     }
@@ -2186,7 +1768,7 @@ int ookd_rx_submit_device(ookd_rx *rx, const void *d_iq, uint32_t num_captures,
     }
     HIPCHK(hipSetDevice(rx->dev));
     // (behind the front end a carrier context's carriers are the captures of a batch)
-    rx->run_caps = rx->carriers.empty() ? num_captures : (uint32_t)rx->carriers.size();
+    rx->run_caps = rx->num_carriers() ? rx->num_carriers() : num_captures;
     rx->run_n_valid = samples_per_capture;
     rx->geometry(samples_per_capture, true, rx->run_n_in, rx->run_n_out, rx->run_words,
                  rx->run_blocks, rx->run_segs_per_cap);
@@ -2252,14 +1834,14 @@ int ookd_rx_process_host(ookd_rx *rx, const int16_t *iq, uint64_t num_samples) {
     }
     HIPCHK(hipSetDevice(rx->dev));
     if (!rx->d_stage_in.p) {
-        int rc = rx->d_stage_in.alloc(rx->max_samples * (sample_bytes(rx->sample_fmt) / 2) + 8);
+        int rc = rx->d_stage_in.alloc(rx->max_samples * (sample_bytes(rx->front.base.sample_fmt) / 2) + 8);
         if (rc != OOKD_OK) return rc;
     }
-    if (num_samples && rx->ingest.from_host(iq, rx->d_stage_in.p, num_samples * sample_bytes(rx->sample_fmt)) < 0) return OOKD_ERR_HIP;
+    if (num_samples && rx->ingest.from_host(iq, rx->d_stage_in.p, num_samples * sample_bytes(rx->front.base.sample_fmt)) < 0) return OOKD_ERR_HIP;
     return ookd_rx_process_device(rx, rx->d_stage_in.p, 1, num_samples, num_samples);
 }
 
-uint64_t ookd_rx_halo_samples(const ookd_rx *rx) { return rx ? rx->halo_needed : 0; }
+uint64_t ookd_rx_halo_samples(const ookd_rx *rx) { return rx ? rx->halo_needed() : 0; }
 
 int ookd_scan_domain_info(const ookd_device *device, uint32_t samples_per_buffer, uint32_t total_decimation,
                           uint32_t out[8]) {
@@ -2294,12 +1876,8 @@ int ookd_scan_tables_digest(const ookd_device *device, uint32_t samples_per_buff
     memset(g.get(), 0, sizeof(FsmTablesDev));
     fill_fsm_tables(*device, *g);
     const ScanTables t = build_scan_tables(*g, samples_per_buffer, total_decimation, true);
-    auto fnv = [](uint64_t h, const auto &v) {
-        const unsigned char *b = reinterpret_cast<const unsigned char *>(v.data());
-        for (size_t i = 0; i < v.size() * sizeof(v[0]); ++i) h = (h ^ b[i]) * 0x100000001b3ull;
-        return h;
-    };
-    const uint64_t h0 = 0xcbf29ce484222325ull;
+    auto fnv = [](uint64_t h, const auto &v) { return fnv1a(h, v.data(), v.size() * sizeof(v[0])); };
+    const uint64_t h0 = kFnvBasis;
     out[0] = fnv(fnv(fnv(h0, t.off), t.n0), t.pk);
     out[1] = fnv(fnv(h0, t.reach), t.reach_by_level);
     out[2] = fnv(h0, t.merged);
@@ -2315,29 +1893,29 @@ int ookd_rx_shard_begin(ookd_rx *rx, const void *d_iq, uint64_t num_samples, con
         set_error("ookd_rx_shard_begin: bad argument");
         return OOKD_ERR_ARG;
     }
-    if (!rx->carriers.empty()) {
+    if (rx->num_carriers()) {
         set_error("ookd_rx_shard_begin: a carrier context runs whole captures, not shards");
         return OOKD_ERR_ARG;
     }
     const uint64_t spb = rx->cfg.samples_per_buffer;
-    const uint64_t align = spb / gcd64(spb, rx->total_decim) * rx->total_decim;
+    const uint64_t align = spb / gcd64(spb, rx->total_decim()) * rx->total_decim();
     if (!last_shard && (num_samples % align) != 0) {
         set_error("shard of %llu samples is not a multiple of lcm(samples_per_buffer, decimation) = %llu",
                   (unsigned long long)num_samples, (unsigned long long)align);
         return OOKD_ERR_ARG;
     }
-    if (halo && halo_samples < rx->halo_needed) {
+    if (halo && halo_samples < rx->halo_needed()) {
         set_error("halo of %llu samples is shorter than the %llu the filter needs",
-                  (unsigned long long)halo_samples, (unsigned long long)rx->halo_needed);
+                  (unsigned long long)halo_samples, (unsigned long long)rx->halo_needed());
         return OOKD_ERR_ARG;
     }
     HIPCHK(hipSetDevice(rx->dev));
     uint32_t hl = 0;
-    if (halo && rx->halo_needed) {
-        hl = (uint32_t)rx->halo_needed;
+    if (halo && rx->halo_needed()) {
+        hl = (uint32_t)rx->halo_needed();
         // hipMemcpyDefault: the halo may be a host array or a device buffer an
         // RCCL recv landed in
-        const size_t sb = sample_bytes(rx->sample_fmt);
+        const size_t sb = sample_bytes(rx->front.base.sample_fmt);
         HIPCHK(hipMemcpyAsync(rx->d_halo.p, reinterpret_cast<const char *>(halo) + sb * (halo_samples - hl), (size_t)hl * sb,
                               hipMemcpyDefault, rx->stream));
     }
@@ -2372,7 +1950,7 @@ int ookd_rx_shard_refine(ookd_rx *rx, const ookd_fsm_state *state_in, ookd_fsm_s
         set_error("ookd_rx_shard_refine: null argument");
         return OOKD_ERR_ARG;
     }
-    if (!rx->carriers.empty()) {
+    if (rx->num_carriers()) {
         set_error("ookd_rx_shard_refine: a carrier context runs whole captures, not shards");
         return OOKD_ERR_ARG;
     }
@@ -2417,34 +1995,17 @@ int ookd_rx_get_stats(const ookd_rx *rx, ookd_rx_stats *out) {
 
 int ookd_rx_get_front_info(const ookd_rx *rx, ookd_front_info *out) {
     if (!rx || !out) return OOKD_ERR_ARG;
-    ookd_front_info f{};
-    f.form = rx->reported_form(front_form(rx->front_params(nullptr, 0), rx->exact));
-    f.mfma_ksteps = rx->mfma_ksteps;
-    f.p_star = rx->p_star;
-    f.p_lo = rx->p_lo;
-    f.p_hi = rx->p_hi;
-    f.mfma_c = rx->mfma_c;
-    f.err_nominal = rx->err_n;
-    f.err_wide = rx->err_w;
-    f.err_valu = rx->err_valu;
-    f.mfma_delta = rx->mfma_delta;
-    *out = f;
+    *out = front_info(rx->front.plan, 0);
     return OOKD_OK;
 }
 
 int ookd_rx_get_carrier_front_info(const ookd_rx *rx, uint32_t k, ookd_front_info *out) {
     clear_error();
-    if (!rx || !out || k >= rx->carriers.size()) {
+    if (!rx || !out || k >= rx->num_carriers()) {
         set_error("ookd_rx_get_carrier_front_info: bad argument");
         return OOKD_ERR_ARG;
     }
-    const int rc = ookd_rx_get_front_info(rx, out);
-    if (rc != OOKD_OK) return rc;
-    const ookd_rx::Carrier &c = rx->carriers[k];
-    out->p_star = c.p_star;
-    out->p_lo = c.p_lo;
-    out->p_hi = c.p_hi;
-    out->err_valu = c.err_valu;
+    *out = front_info(rx->front.plan, k);
     return OOKD_OK;
 }
 

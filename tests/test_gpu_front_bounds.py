@@ -1,5 +1,5 @@
 """The front end's guard band, measured: which kernel a context runs (stats["front_form"] against the dispatch
-rules of launch_front / setup_front_form), how close each kernel's floats come to the forward error bound its band
+rules of launch_front / plan_real_form), how close each kernel's floats come to the forward error bound its band
 is built from, and bits at the inputs where that bound is tight -- sign-aligned full-scale windows, cancellation at
 the threshold, wide samples placed around tile boundaries.  Every result is compared with the CPU oracle, the
 reference-order float chain."""
@@ -91,7 +91,7 @@ def _front_forms(ok):
 
 # (filter, Receiver keywords, threshold, expected form), from the rules:
 #   no stages                                                       -> none
-#   1 stage, decimation 1, taps padded to 32 <= 256                 -> mfma1 when setup_front_form prepared the
+#   1 stage, decimation 1, taps padded to 32 <= 256                 -> mfma1 when plan_real_form prepared the
 #       matrix-core image (not exact, not fir_valu, mfma_prepare_taps took the taps, every band edge scales exactly
 #       into accumulator units -- mfma_scale_band --, p_star 0 / NaN or within [2^-100, 2^100]), else fir1 / fir1x
 #   2 stages of decimation 2, <= 16 and <= 32 taps                  -> mfma2 under the same conditions, else fir2 / fir2x
@@ -462,3 +462,40 @@ def test_wide_sample_placement(ok, oracle, tmp_path, name, wide_value):
             r = float(np.abs(rx.fir_output().astype(np.float64) - want.fir.astype(np.float64)).max()) / err
             assert r <= MARGIN, (where, r)
             rx.close()
+
+
+# ---- a live context agrees with the host-side plan ----------------------------------------------------------------
+# one case of tests/golden/front_plan.json per OOKD_FRONT_* number (and carrier lists of 2 and 16)
+LIVE_PLAN_CASES = ["none-none-thr0.1", "stages3-none-thr0.1", "fs32_fs4-fir_valu-thr0.1", "fs32_fs4-exact_fir-thr0.1",
+                   "fs32_fs4-none-thr0.1", "fs128_fs16_dec4-fir_valu-thr0.1", "fs128_fs16_dec4-exact_fir-thr0.1",
+                   "fs128_fs16_dec4-none-thr0.1", "none-cs8-thr0.1", "fs32_fs4-cs8-thr0.1", "fs128_fs16_dec4-cu8-thr0.1",
+                   "stages3-none-thr0.1-nu0.25", "fs32_fs4-none-thr0.1-nu3000th", "fs32_fs4-none-thr0.1-car2",
+                   "rand255-none-thr0.1-car16"]
+
+
+def test_live_context_reports_what_the_plan_recorded(ok):
+    """What a context reports about its front end -- front_info(), carrier_front_info(k) for every carrier, and the
+    form its run launched -- is the recorded plan's, bit for bit: the context holds no numbers of its own."""
+    from tests import front_plan_cases as P
+    with open(P.GOLDEN_FILE) as f:
+        golden = json.load(f)
+    cases = P.cases()
+    n = 8192
+    rng = np.random.default_rng(21)
+    iq = rng.integers(-40, 41, size=2 * n).astype(np.int16)
+    iq[2 * 3000:2 * 3600] = 32767               # one full-scale burst
+    forms = set()
+    for cid in LIVE_PLAN_CASES:
+        case, want = cases[cid], golden[cid]
+        kw = P.receiver_kwargs(case)
+        rx = ok.Receiver(P.make_filter(case["filter"]), None, max_samples=n, samples_per_buffer=4096, **kw)
+        x = iq if kw["sample_format"] == "sc16q11" else (iq >> 8).astype(np.int8)
+        rx.rx(x if kw["sample_format"] != "cu8" else (x.astype(np.int16) + 128).astype(np.uint8))
+        assert P.info_entry(rx.front_info()) == want["info"][0], cid
+        for k in range(rx.num_carriers):
+            assert P.info_entry(rx.carrier_front_info(k)) == want["info"][k], (cid, k)
+        assert rx.num_carriers == (len(case["carriers"]) if case["carriers"] else 0)
+        assert rx.stats()["front_form"] == want["form"] == want["info"][0]["form"], cid
+        forms.add(want["form"])
+        rx.close()
+    assert forms == set(range(ok.FRONT_NO_FILTER, ok.FRONT_TUNED_MULTI + 1))

@@ -72,8 +72,8 @@ def _sync_walk_forced(on=True):
 
 
 def _form_for(ok, of, exact=False, valu=False):
-    """the front-end kernel launch_front runs for a filter (the rules of kernels.hip front_form and rx.cpp
-    setup_front_form; thresholds within [2^-50, 2^50] and taps near unit gain: the matrix cores never refuse)"""
+    """the front-end kernel launch_front runs for a filter (the rules of kernels.hip front_form and front_plan.cpp
+    plan_real_form; thresholds within [2^-50, 2^50] and taps near unit gain: the matrix cores never refuse)"""
     if of is None:
         return ok.FRONT_NO_FILTER
     n = [int(of.stage_taps(s).size) for s in range(of.num_stages)]
@@ -473,7 +473,7 @@ def test_mfma_fir_tap_magnitudes(ok, oracle, tmp_path, scale):
     assert 0.2 < want.bits.mean() < 0.8
     rx = ok.Receiver(f, None, max_samples=n, threshold=thr, edge_capacity=n + 64)
     got = rx.rx(iq)
-    # the matrix-core form unless setup_front_form refuses: tap scaling beyond 2^+-100 (mfma_prepare_taps), p_star
+    # the matrix-core form unless plan_real_form refuses: tap scaling beyond 2^+-100 (mfma_prepare_taps), p_star
     # outside [2^-100, 2^100], band edges that do not scale into normal floats in accumulator units (mfma_scale_band)
     _, e = math.frexp(float(np.abs(taps.astype(np.float64)).max()))
     sh = 15 - e
