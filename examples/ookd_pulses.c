@@ -1,0 +1,117 @@
+/*
+ * ookd_pulses.c -- a C99 host on top of libookiedokie_amd.so that answers the third question about an unknown
+ * capture, after "which carrier" and "which threshold" (examples/ookd_scan.c): which timings?  It runs the capture
+ * through a context WITHOUT a device (filter, threshold, edges), asks for the run-length histogram of its edge list
+ * (ookd_rx_pulse_hist, computed on the GPU) and prints the timing classes ookd_suggest_pulses groups it into: the
+ * pulse and gap durations somebody who writes a device JSON has to type in.
+ *
+ * Build:
+ *   gcc -std=c99 -Wall -Werror -Iinclude examples/ookd_pulses.c -o ookd_pulses \
+ *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
+ *
+ * ookd_pulses <capture.sc16q11|.cs8|.cu8> <filter.json|none> [--threshold <amplitude>] [--tune <hz>] [--rate <hz>]
+ *
+ *   --threshold  slicer level, default 0.1 (ookd_scan's stderr names one per carrier)
+ *   --tune       carrier offset in Hz (needs a filter), default 0
+ *   --rate       sample rate of the capture, default 3000000; the table's microseconds and --tune depend on it
+ *
+ * stdout: one line with the edge count and the two open runs, then per level ("on", "off") one line per class:
+ * runs, mean length in decimated samples and in microseconds, and the range of lengths its bins cover.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "ookiedokie_amd.h"
+
+static int fail(const char *what)
+{
+    fprintf(stderr, "%s: %s\n", what, ookd_last_error());
+    return EXIT_FAILURE;
+}
+
+int main(int argc, char **argv)
+{
+    double threshold = 0.1, tune_hz = 0.0, rate = 3000000.0;
+    int bad = argc < 3;
+    for (int i = 3; i < argc && !bad; i += 2) {
+        if (i + 1 >= argc) bad = 1;
+        else if (!strcmp(argv[i], "--threshold")) threshold = strtod(argv[i + 1], NULL);
+        else if (!strcmp(argv[i], "--tune")) tune_hz = strtod(argv[i + 1], NULL);
+        else if (!strcmp(argv[i], "--rate")) rate = strtod(argv[i + 1], NULL);
+        else bad = 1;
+    }
+    if (bad || !(rate > 0.0) || !(threshold > 0.0)) {
+        fprintf(stderr, "usage: %s <capture.sc16q11|.cs8|.cu8> <filter.json|none> [--threshold <amplitude>] "
+                        "[--tune <hz>] [--rate <hz>]\n", argv[0]);
+        return EXIT_FAILURE;
+    }
+    int status = EXIT_FAILURE;
+
+    ookd_host_cfg cfg;                      /* struct ookiedokie_cfg, field for field */
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.sdr_type = "hip_file";
+    cfg.direction = 0;
+    cfg.sdr_args = argv[1];
+    cfg.samplerate = (unsigned) rate;
+    cfg.rx_threshold = (float) threshold;
+    cfg.samples_per_buffer = 8192;
+
+    ookd_filter *filter = NULL;
+    ookd_rx *rx = NULL;
+    static ookd_pulse_hist hist;
+    static ookd_pulse_suggestion sug;
+
+    void *sdr = sdr_hip_file_init((const struct ookiedokie_cfg *)&cfg);   /* same layout: see ookd_host_cfg */
+    if (!sdr) return fail("sdr_hip_file_init");
+    const void *d_iq = NULL;
+    uint64_t n = 0;
+    if (sdr_hip_file_capture(sdr, &d_iq, &n) != 0) { fail("sdr_hip_file_capture"); goto out; }
+
+    unsigned decimation = 1;
+    if (strcmp(argv[2], "none") != 0) {
+        filter = ookd_filter_load(argv[2]);
+        if (!filter) { fail("ookd_filter_load"); goto out; }
+        decimation = ookd_filter_total_decimation(filter);
+    }
+
+    ookd_rx_config rc;
+    memset(&rc, 0, sizeof(rc));
+    rc.threshold = cfg.rx_threshold;
+    rc.samples_per_buffer = cfg.samples_per_buffer;
+    rc.max_samples = n ? n : 1;
+    rc.max_captures = 1;
+    rc.flags = (uint32_t) sdr_hip_file_sample_flags(sdr) | OOKD_RX_NO_PIPELINE;
+    ookd_tune tune;
+    memset(&tune, 0, sizeof(tune));
+    tune.nu = tune_hz / rate;
+    rx = ookd_rx_create_tuned(&rc, filter, NULL /* no device: edges only */, &tune);
+    if (!rx) { fail("ookd_rx_create_tuned"); goto out; }
+    if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }
+    if (ookd_rx_pulse_hist(rx, 0, &hist) != 0) { fail("ookd_rx_pulse_hist"); goto out; }
+    const double out_rate = rate / (double) decimation;     /* the rate the state machine sees (main.c:683) */
+    if (ookd_suggest_pulses(&hist, out_rate, &sug) != 0) { fail("ookd_suggest_pulses"); goto out; }
+
+    printf("%llu edges in %llu samples at %.6g Hz; before the first edge %llu samples, after the last %llu (%s)\n",
+           (unsigned long long) hist.num_edges, (unsigned long long) hist.samples, out_rate,
+           (unsigned long long) hist.open_head, (unsigned long long) hist.open_tail, hist.tail_level ? "on" : "off");
+    for (int level = 1; level >= 0; --level) {
+        printf("%s-runs: %llu in %u classes%s\n", level ? "on" : "off", (unsigned long long) hist.runs[level],
+               sug.num_classes[level], sug.found ? "" : (level ? "" : "  (no repeating timing on both levels)"));
+        printf("  %10s %14s %12s   %s\n", "runs", "mean samples", "mean us", "range samples (us)");
+        for (uint32_t c = 0; c < sug.num_classes[level]; ++c) {
+            const ookd_pulse_class *k = &sug.classes[level][c];
+            printf("  %10llu %14.2f %12.2f   %llu .. %llu (%.2f .. %.2f)\n", (unsigned long long) k->runs, k->mean,
+                   k->mean_us, (unsigned long long) k->lower, (unsigned long long) k->upper, k->lower_us, k->upper_us);
+        }
+        if (sug.dropped_runs[level])
+            printf("  %llu runs in further classes not listed\n", (unsigned long long) sug.dropped_runs[level]);
+    }
+    status = EXIT_SUCCESS;
+
+out:
+    ookd_rx_destroy(rx);
+    ookd_filter_free(filter);
+    sdr_hip_file_deinit(sdr);
+    return status;
+}

@@ -830,6 +830,126 @@ int ookd_suggest_carriers(const ookd_spectrum_result *sp, double min_ratio /* 0 
                           ookd_carrier *out, uint32_t capacity, uint32_t *count, double *floor);
 
 /* ------------------------------------------------------------------------
+ * Pulse survey: which timings does this capture want?  The slicer's output,
+ * the sorted edge list of every capture (or carrier) of a run, stays in HBM
+ * after the run; one pass over it counts how long the "on" runs and the "off"
+ * runs are into a histogram per capture and level; ookd_suggest_pulses (host
+ * only) groups a histogram into the few timing classes a device file names
+ * (devices/README.md: the pulse and gap durations of its states).  A by-product
+ * of a finished run like the recorders: nothing a run does changes, and a run
+ * nobody asks about launches and allocates nothing for it.
+ *
+ * Runs, a contract.  For capture (or carrier) c of the last run take its edge
+ * list e[0..E) as ookd_rx_get_edges returns it and n_out =
+ * stats.decimated_samples.  Closed run i, 0 <= i < E - 1, has length
+ * e[i+1] - e[i] and level 1 ("on") when i is even, 0 ("off") otherwise: sample
+ * -1 counts as 0, so the first edge rises.  The two open runs are not counted
+ * in the bins:
+ *     open_head  = e[0], or n_out when E = 0; its level is 0;
+ *     open_tail  = n_out - e[E-1], or 0 when E = 0;
+ *     tail_level = E & 1.
+ * The zero padding to whole buffers is part of the edge list (a capture that
+ * ends high falls at the first padded sample); the histogram is a function of
+ * that list and n_out and of nothing else, whatever filter, tuning, sample
+ * format or device the context has.
+ *
+ * Bins, all integer.  OOKD_PULSE_BINS = 512.  A length d of 1 .. 31 goes to bin
+ * d (bin 0 stays empty); for d >= 32, with o = floor(log2 d), to
+ *     32 + 16 (o - 5) + ((d >> (o - 4)) & 15),  clamped to 511:
+ * sixteen bins per octave, none wider than 6.25 % of its lower edge, d < 2^35
+ * covered before the clamp.  ookd_pulse_bin_lower(b) = b for b < 32, otherwise
+ * (16 + (b - 32) % 16) << (1 + (b - 32) / 16); 512 and beyond continue the
+ * series (512 gives 2^35, the upper edge of what bin 511 holds before the
+ * clamp), saturating at UINT64_MAX.  Example: 1503 goes to bin 119 = [1472, 1536).
+ *
+ * The histogram is an exact integer function of the edge list, the same
+ * whatever order the kernel's atomic adds land in.  It is computed for ALL
+ * captures (carriers) of the run by one kernel launch at the first
+ * ookd_rx_pulse_hist after the run, on the context's stream, and answered from
+ * host memory until the next run; its buffers are allocated by the first call
+ * in the life of the context.  Contexts without a device, batched runs and
+ * carrier contexts (capture = carrier index) all work.
+ * Returns OOKD_ERR_ARG for a NULL argument, capture >= the run's captures, no
+ * finished run (none yet, one submitted and not waited for, or one that failed
+ * before its edges were counted), and -- with a
+ * message naming the case -- for a pipelined run (stats.pipeline_chunks != 0:
+ * its lists are chunk-local) and for a shard run (ookd_rx_shard_begin: the level
+ * in front of the shard is unknown); OOKD_ERR_CAPACITY when the run's edge list
+ * overflowed.
+ * ---------------------------------------------------------------------- */
+#define OOKD_PULSE_BINS 512
+typedef struct ookd_pulse_hist {
+    uint64_t num_edges, samples;            /* E, n_out                              */
+    uint64_t runs[2];                       /* closed runs per level = sum of count  */
+    uint64_t count[2][OOKD_PULSE_BINS];     /* [level][bin]                          */
+    uint64_t sum[2][OOKD_PULSE_BINS];       /* sum of the lengths counted there      */
+    uint64_t open_head, open_tail;
+    uint32_t tail_level, reserved;
+} ookd_pulse_hist;
+int ookd_rx_pulse_hist(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out);
+/* HIP-event time of the pass that computed the last run's histograms: the
+ * zeroing of the result and the kernel.  0 while nobody has asked about the
+ * last run (also when the call was refused, or the run had no samples). */
+float ookd_rx_pulse_kernel_ms(const ookd_rx *rx);
+
+/* The bin rule above and its inverse, pure host code (no GPU needed).
+ * ookd_pulse_bin(0) is 0. */
+uint32_t ookd_pulse_bin(uint64_t length);
+uint64_t ookd_pulse_bin_lower(uint32_t bin);
+
+/* Timing classes, pure host code.  The rule, a contract, per level:
+ *   1. Walk the bins upwards.  A class is a maximal group of occupied bins in
+ *      which two successive occupied bins lie fewer than OOKD_PULSE_CLASS_GAP
+ *      bins apart (their indices differ by less than it: with 2, occupied bins
+ *      join a class only when they are adjacent).
+ *   2. A class reports first_bin and last_bin (its lowest and highest occupied
+ *      bin), runs = the sum of its counts, mean = (sum of its sums) / runs as a
+ *      double, lower = ookd_pulse_bin_lower(first_bin), upper =
+ *      ookd_pulse_bin_lower(last_bin + 1) - 1 (NOT a bound for a class that ends
+ *      in bin 511: that bin also holds every clamped longer run, and upper
+ *      then reads 2^35 - 1 while mean may lie above it), and mean_us / lower_us / upper_us
+ *      = x / sample_rate * 1e6, or 0 when sample_rate <= 0 (or NaN).
+ *      sample_rate is the rate of the DECIMATED samples (what ookd_device_load
+ *      takes).
+ *   3. At most OOKD_PULSE_MAX_CLASSES classes are reported per level, in
+ *      ascending order of length.  If there are more, those with the most runs
+ *      are kept -- on a tie the shorter class wins -- and dropped_runs[level]
+ *      counts the runs of the rest.
+ *   4. found = 1 when each level has a class of at least 2 runs.
+ * Only count[][] and sum[][] of the histogram are read.
+ * OOKD_PULSE_CLASS_GAP, 2 bins: measured on the golden captures (threshold 0.1,
+ * clean and with +-40 LSB of noise, through fs32_fs4 and fs128_fs16_dec4), the
+ * narrowest separation between two real timings is 11997 against 13197 samples
+ * (unknown-remote1's off-runs): bins 167 and 169, two bins apart with one empty
+ * bin between them, which a gap of 2 keeps apart; while one timing that
+ * straddles a bin edge -- the same capture's on-runs through fs128_fs16_dec4,
+ * 415 and 416 samples -- lands in two ADJACENT bins, which a gap of 2 merges (a
+ * gap of 1 would not, a gap of 3 would merge the two real timings).
+ * Limits: the rule knows nothing about coding (which class is a sync, a one or
+ * a zero is for the author of the device file); one-sample glitches show up as
+ * classes of their own (bin 1); timings closer together than two bins (6 to
+ * 12 % apart, depending on where the bin edges fall) merge into one class; only
+ * two levels exist. */
+#define OOKD_PULSE_CLASS_GAP 2
+#define OOKD_PULSE_MAX_CLASSES 16
+typedef struct ookd_pulse_class {
+    uint32_t first_bin, last_bin;
+    uint64_t runs;
+    double mean;                    /* samples                                 */
+    uint64_t lower, upper;          /* samples: the range its bins cover       */
+    double mean_us, lower_us, upper_us;
+} ookd_pulse_class;
+typedef struct ookd_pulse_suggestion {
+    int found;                      /* 1: each level has a class of >= 2 runs  */
+    uint32_t reserved;
+    uint32_t num_classes[2];        /* [level]: 0 = off-runs, 1 = on-runs      */
+    uint64_t dropped_runs[2];
+    ookd_pulse_class classes[2][OOKD_PULSE_MAX_CLASSES];
+} ookd_pulse_suggestion;
+/* 0, or OOKD_ERR_ARG for a NULL argument. */
+int ookd_suggest_pulses(const ookd_pulse_hist *h, double sample_rate, ookd_pulse_suggestion *out);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

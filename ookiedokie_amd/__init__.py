@@ -18,6 +18,8 @@ here                              reference (OOKiedokie ``src/``)
                                   (ookiedokie_cfg.c:27) from the capture
 ``Spectrum`` / ``suggest_carriers`` nothing: finds the carriers' offsets
                                   (``Receiver(tune=...)``) in the capture
+``Receiver.pulse_hist`` /         nothing: measures the pulse and gap lengths
+``suggest_pulses``                a device file's states name (devices/README.md)
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -79,6 +81,9 @@ SPECTRUM_BINS = 1024                    # OOKD_SPECTRUM_BINS: carrier survey, 10
 SPECTRUM_EPS = 12.0 * 10.0 / 16777216.0 # OOKD_SPECTRUM_EPS: the error bound's constant, 12 log2(1024) 2^-24
 CARRIER_MIN_RATIO = 64.0                # OOKD_CARRIER_MIN_RATIO
 CARRIER_MIN_SPACING = 32                # OOKD_CARRIER_MIN_SPACING
+PULSE_BINS = 512                        # OOKD_PULSE_BINS: pulse survey, sixteen bins per octave of run length
+PULSE_CLASS_GAP = 2                     # OOKD_PULSE_CLASS_GAP
+PULSE_MAX_CLASSES = 16                  # OOKD_PULSE_MAX_CLASSES
 DEFAULT_THRESHOLD = 0.1                 # ookiedokie_cfg.c:27
 DEFAULT_RATE = 3000000                  # ookiedokie_cfg.c:32
 DEFAULT_SAMPLES_PER_BUF = 8192          # ookiedokie_cfg.c:34
@@ -192,6 +197,24 @@ class SpectrumResult(C.Structure):
 class CarrierStruct(C.Structure):
     _fields_ = [("nu", C.c_double), ("bin", C.c_int32), ("at_dc", C.c_uint32), ("power", C.c_double),
                 ("ratio", C.c_double)]
+
+
+class PulseHist(C.Structure):
+    _fields_ = [("num_edges", C.c_uint64), ("samples", C.c_uint64), ("runs", C.c_uint64 * 2),
+                ("count", (C.c_uint64 * PULSE_BINS) * 2), ("sum", (C.c_uint64 * PULSE_BINS) * 2),
+                ("open_head", C.c_uint64), ("open_tail", C.c_uint64), ("tail_level", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PulseClass(C.Structure):
+    _fields_ = [("first_bin", C.c_uint32), ("last_bin", C.c_uint32), ("runs", C.c_uint64), ("mean", C.c_double),
+                ("lower", C.c_uint64), ("upper", C.c_uint64), ("mean_us", C.c_double), ("lower_us", C.c_double),
+                ("upper_us", C.c_double)]
+
+
+class PulseSuggestion(C.Structure):
+    _fields_ = [("found", C.c_int), ("reserved", C.c_uint32), ("num_classes", C.c_uint32 * 2),
+                ("dropped_runs", C.c_uint64 * 2), ("classes", (PulseClass * PULSE_MAX_CLASSES) * 2)]
 
 
 class HostCfg(C.Structure):
@@ -315,6 +338,11 @@ _PROTOTYPES = {
     "ookd_suggest_carriers": (C.c_int, [C.POINTER(SpectrumResult), C.c_double, C.c_uint32,
                                         C.POINTER(CarrierStruct), C.c_uint32, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_double)]),
+    "ookd_rx_pulse_hist": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(PulseHist)]),
+    "ookd_rx_pulse_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_pulse_bin": (C.c_uint32, [C.c_uint64]),
+    "ookd_pulse_bin_lower": (C.c_uint64, [C.c_uint32]),
+    "ookd_suggest_pulses": (C.c_int, [C.POINTER(PulseHist), C.c_double, C.POINTER(PulseSuggestion)]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
     "sdr_hip_file_deinit": (None, [C.c_void_p]),
     "sdr_hip_file_rx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
@@ -907,6 +935,21 @@ class Receiver:
         _check(lib().ookd_rx_get_errors(self._h, out.ctypes.data, cap, C.byref(n)))
         return out[:min(cap, n.value)], int(n.value)
 
+    # -- pulse survey ----------------------------------------------------------------
+    def pulse_hist(self, capture: int = 0) -> dict:
+        """Run-length histograms of one capture (or carrier) of the last run (ookd_rx_pulse_hist): `count` and `sum`
+        as uint64 arrays [2, 512] indexed [level, bin] (level 1 = "on" runs), `runs` [2], and the scalars num_edges,
+        samples, open_head, open_tail, tail_level.  Computed on the GPU for all captures at the first call after a
+        run.  Feed it to `suggest_pulses`."""
+        h = PulseHist()
+        _check(lib().ookd_rx_pulse_hist(self._h, capture, C.byref(h)))
+        return _pulse_hist_dict(h)
+
+    @property
+    def pulse_kernel_ms(self) -> float:
+        """HIP-event time of the pass behind `pulse_hist` for the last run; 0 while nobody has asked about it."""
+        return float(lib().ookd_rx_pulse_kernel_ms(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_rx_destroy(self._h)
@@ -917,6 +960,49 @@ class Receiver:
             self.close()
         except Exception:
             pass
+
+
+# --------------------------------------------------------------------------
+# pulse survey
+# --------------------------------------------------------------------------
+
+def pulse_bin(length: int) -> int:
+    """The histogram bin of a run length in decimated samples (ookd_pulse_bin): 1 .. 31 their own bin, sixteen
+    bins per octave from 32 on."""
+    return int(lib().ookd_pulse_bin(int(length)))
+
+
+def pulse_bin_lower(bin: int) -> int:
+    """The shortest run a bin holds (ookd_pulse_bin_lower)."""
+    return int(lib().ookd_pulse_bin_lower(int(bin)))
+
+
+def _pulse_hist_dict(h: PulseHist) -> dict:
+    return dict(num_edges=int(h.num_edges), samples=int(h.samples),
+                runs=np.frombuffer(bytes(h.runs), dtype=np.uint64).copy(),
+                count=np.frombuffer(bytes(h.count), dtype=np.uint64).reshape(2, PULSE_BINS).copy(),
+                sum=np.frombuffer(bytes(h.sum), dtype=np.uint64).reshape(2, PULSE_BINS).copy(),
+                open_head=int(h.open_head), open_tail=int(h.open_tail), tail_level=int(h.tail_level))
+
+
+def suggest_pulses(hist, sample_rate: float) -> dict:
+    """ookd_suggest_pulses: the timing classes of a histogram (`Receiver.pulse_hist`'s dict, or anything with `count`
+    and `sum` arrays [2, 512]).  sample_rate is that of the decimated samples; 0 leaves the *_us members 0.  Returns
+    found, dropped_runs [off, on] and classes [off, on]: lists of dicts (first_bin, last_bin, runs, mean, lower, upper,
+    mean_us, lower_us, upper_us) in ascending length.  The rule is stated in the header.  Pure host code."""
+    count = np.ascontiguousarray(hist["count"], dtype=np.uint64)
+    total = np.ascontiguousarray(hist["sum"], dtype=np.uint64)
+    if count.shape != (2, PULSE_BINS) or total.shape != (2, PULSE_BINS):
+        raise ValueError("a pulse histogram has count and sum of shape (2, %d)" % PULSE_BINS)
+    h = PulseHist()
+    C.memmove(h.count, count.ctypes.data, count.nbytes)
+    C.memmove(h.sum, total.ctypes.data, total.nbytes)
+    out = PulseSuggestion()
+    _check(lib().ookd_suggest_pulses(C.byref(h), float(sample_rate), C.byref(out)))
+    classes = [[{name: getattr(out.classes[lv][i], name) for name, _ in PulseClass._fields_}
+                for i in range(out.num_classes[lv])] for lv in range(2)]
+    return dict(found=int(out.found), dropped_runs=[int(out.dropped_runs[0]), int(out.dropped_runs[1])],
+                classes=classes)
 
 
 # --------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "front_plan.hpp"
 #include "ingest.hpp"
 #include "kernels.hpp"
+#include "pulse_run.hpp"
 
 using namespace ookd;
 
@@ -448,6 +449,11 @@ struct ookd_rx : RxHandles {
     uint32_t run_caps = 0;
     uint64_t run_n_valid = 0, run_n_in = 0, run_n_out = 0, run_words = 0;
     uint32_t run_blocks = 0, run_segs_per_cap = 0;
+    // what the pulse survey (pulses.cpp) asks about the last run, and its buffers (made by its first call)
+    uint64_t run_serial = 0;        // runs started so far
+    bool run_shard = false, run_overflow = false;
+    bool run_edges_valid = false;   // collect_results has read this run's edge count: the prefix and the list are its own
+    PulseCtx *pulse = nullptr;
     uint32_t iter_next = 0;         // next FSM iteration number (parity continues)
     uint32_t final_parity = 0;
     ookd_rx_stats stats{};
@@ -459,6 +465,7 @@ struct ookd_rx : RxHandles {
             if (gate->last == ev[1]) gate->last = nullptr;      // ev[1] is destroyed with RxHandles
         }
         (void)hipSetDevice(dev);        // for what is freed after this body: the members, then RxHandles
+        pulse_ctx_free(pulse);
     }
 
     void geometry(uint64_t n_valid, bool pad_to_buffer, uint64_t &n_in, uint64_t &n_out,
@@ -1290,6 +1297,8 @@ int ookd_rx::collect_results() {
         }
     }
     total_edges = run_n_out > 0 ? h_hdr->total_edges : 0;
+    run_overflow = h_hdr->edge_overflow != 0;
+    run_edges_valid = true;
     num_msgs = 0;
     stats.num_edges = total_edges;
     stats.num_messages = 0;
@@ -1773,6 +1782,9 @@ int ookd_rx_submit_device(ookd_rx *rx, const void *d_iq, uint32_t num_captures,
     rx->geometry(samples_per_capture, true, rx->run_n_in, rx->run_n_out, rx->run_words,
                  rx->run_blocks, rx->run_segs_per_cap);
     rx->stats = ookd_rx_stats{};
+    ++rx->run_serial;
+    rx->run_shard = false;
+    rx->run_overflow = rx->run_edges_valid = false;
     rx->last_iq = d_iq;
     rx->last_stride = capture_stride_samples;
     if (rx->plan_chunks()) {
@@ -1925,6 +1937,9 @@ int ookd_rx_shard_begin(ookd_rx *rx, const void *d_iq, uint64_t num_samples, con
                  rx->run_blocks, rx->run_segs_per_cap);
     rx->chunks.clear();
     rx->stats = ookd_rx_stats{};
+    ++rx->run_serial;
+    rx->run_shard = true;
+    rx->run_overflow = rx->run_edges_valid = false;
     int rc = rx->front_and_edges(d_iq, num_samples, hl ? rx->d_halo.p : nullptr, hl);
     if (rc != OOKD_OK) return rc;
     static_assert(sizeof(ookd_fsm_state) == sizeof(FsmStateDev), "fsm state layout");
@@ -2010,6 +2025,33 @@ int ookd_rx_get_carrier_front_info(const ookd_rx *rx, uint32_t k, ookd_front_inf
 }
 
 uint64_t ookd_rx_bit_words(const ookd_rx *rx) { return rx ? rx->run_words : 0; }
+
+}  // extern "C"
+
+// pulse_run.hpp: the last run for the pulse survey, and where the context keeps the survey's buffers
+void ookd_rx_pulse_run(const ookd_rx *rx, PulseRun *out) {
+    PulseRun r;
+    r.dev = rx->dev;
+    r.stream = rx->stream;
+    r.serial = rx->run_serial;
+    r.in_flight = rx->submitted;
+    r.valid = rx->run_edges_valid;
+    r.shard = rx->run_shard;
+    r.pipelined = !rx->chunks.empty();
+    r.overflow = rx->run_overflow;
+    r.captures = rx->run_caps;
+    r.blocks_per_cap = rx->run_blocks;
+    r.n_out = rx->run_n_out;
+    r.num_edges = rx->stats.num_edges;
+    r.edge_capacity = rx->edge_capacity;
+    r.d_edges = rx->d_edges.p;
+    r.d_blk_offset = rx->d_blk_offset.p;
+    *out = r;
+}
+
+PulseCtx **ookd_rx_pulse_ctx(ookd_rx *rx) { return &rx->pulse; }
+
+extern "C" {
 
 int ookd_rx_get_bits(const ookd_rx *rx, uint32_t capture, uint64_t *words, uint64_t capacity_words) {
     clear_error();
