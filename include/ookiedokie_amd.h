@@ -374,6 +374,15 @@ typedef struct ookd_front_info {
                                        tap pieces do not carry                 */
 } ookd_front_info;
 
+/* Filters: any ookd_filter of up to 8 stages whose shape one of the fused kernels takes (1 stage of
+ * decimation 1 with <= 256 taps; 2 decimate-by-2 stages of <= 16 and <= 32 taps).  Every other shape runs
+ * on the generic kernels, which build each level of a tile of L final outputs in LDS: level s holds
+ * len_s = D_s * (len_{s+1} - 1) + T_s samples (len_S = L; D_s, T_s: decimation and tap count of stage s),
+ * and a tile needs (max len of the even levels + max len of the odd levels + 2) * 8 bytes.  L is the
+ * largest power of two in [64, 1024] for which that is <= 163840 bytes (160 KiB).  A filter that does not
+ * fit L = 64 -- one stage: 63 * D + T > 20478, e.g. any decimation beyond 325 -- is refused here, by
+ * ookd_rx_create_tuned, ookd_rx_create_carriers and ookd_fir_create (NULL; ookd_last_error names the
+ * total decimation, the tap counts and the limit), never by a run. */
 ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
                         const ookd_device *device);
 /* A context tuned to a carrier at nu cycles per input sample (see

@@ -317,17 +317,17 @@ void fir1_tuned_multi_kernel(const FrontParams p, const TunedCarrierDev *tab,
 // ---------------------------------------------------------------------------
 // any shape, the contract's order throughout: fir_generic_kernel (kernels.hip) with complex taps
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void fir_tuned_generic_kernel(const FrontParams p, uint32_t lds_b_off) {
+__global__ __launch_bounds__(256) void fir_tuned_generic_kernel(const FrontParams p, uint32_t lds_b_off, uint32_t tile) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf[2] = {reinterpret_cast<float2 *>(smem_raw), reinterpret_cast<float2 *>(smem_raw) + lds_b_off};
 
     const uint32_t tid = threadIdx.x;
     const uint32_t cap = blockIdx.y;
     const int S = (int)p.num_stages;
-    const int64_t j0 = (int64_t)blockIdx.x * kGenTile;
+    const int64_t j0 = (int64_t)blockIdx.x * tile;
     GenLevel lv[kMaxStages + 1];
     int64_t off[kMaxStages];
-    gen_levels(p, j0, kGenTile, lv, off);
+    gen_levels(p, j0, tile, lv, off);
 
     const uint32_t *src = reinterpret_cast<const uint32_t *>(p.iq) + (uint64_t)cap * p.cap_stride;
     for (uint32_t i = tid; i < lv[0].len; i += 256) buf[0][i] = fetch_sample(p, src, nullptr, lv[0].a + (int64_t)i);
@@ -359,7 +359,8 @@ __global__ __launch_bounds__(256) void fir_tuned_generic_kernel(const FrontParam
                 const bool valid = (i < n) && o >= 0 && (uint64_t)o < p.n_out;
                 const bool bit = valid && (power_ref(ar, ai) >= p.p_star);
                 const uint64_t ball = __ballot(bit);
-                if (words && lane_id() == 0) words[((uint64_t)j0 + base + (tid & ~63u)) >> 6] = ball;
+                // (a tile below 256 outputs is one round: the waves past it own no word)
+                if (words && lane_id() == 0 && base + (tid & ~63u) < tile) words[((uint64_t)j0 + base + (tid & ~63u)) >> 6] = ball;
                 if (fout && valid) fout[o] = make_float2(ar, ai);
             }
         }
@@ -436,22 +437,18 @@ hipError_t launch_front_tuned_multi(const FrontParams &p, const TunedCarrierDev 
 
 hipError_t launch_front_tuned_generic(const FrontParams &p, uint32_t num_captures, hipStream_t stream) {
     if (!p.tune || !p.ctaps || p.iq_f32 || p.halo_f32 || p.sample_fmt != kFmtSc16) return hipErrorInvalidValue;
-    // level sizes of one tile, as launch_front_generic
-    uint32_t len[kMaxStages + 1];
-    const int S = (int)p.num_stages;
-    len[S] = kGenTile;
-    for (int s = S - 1; s >= 0; --s) len[s] = p.stage[s].decim * (len[s + 1] - 1) + p.stage[s].ntaps;
-    uint32_t even = 0;
-    for (int s = 0; s < S; s += 2) even = len[s] > even ? len[s] : even;
-    const size_t lds = generic_lds_bytes(p);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    // the tile and its level buffers, as launch_front_generic (the levels hold float2 samples whatever the taps are)
+    const GenTile g = generic_tile(p.stage, p.num_stages);
+    if (!g.tile) return hipErrorInvalidValue;       // (plan_front refuses such a filter)
+    const size_t lds = (size_t)g.lds_bytes;
     // cover every bit word of the capture so the tail words are written (as zeros)
-    uint64_t tiles = (p.n_out + kGenTile - 1) / kGenTile;
-    if (p.bits && p.words_per_cap * 64 / kGenTile > tiles) tiles = p.words_per_cap * 64 / kGenTile;
+    uint64_t tiles = (p.n_out + g.tile - 1) / g.tile;
+    if (p.bits && p.words_per_cap * 64 / g.tile > tiles) tiles = p.words_per_cap * 64 / g.tile;
     if (tiles == 0) return hipSuccess;
     const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&fir_tuned_generic_kernel), lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fir_tuned_generic_kernel, dim3((uint32_t)tiles, num_captures), dim3(256), lds, stream, p, even + 1);
+    hipLaunchKernelGGL(fir_tuned_generic_kernel, dim3((uint32_t)tiles, num_captures), dim3(256), lds, stream, p, g.lds_b_off,
+                       g.tile);
     return hipGetLastError();
 }
 

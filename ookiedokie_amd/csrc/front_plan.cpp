@@ -3,6 +3,7 @@
 // these numbers are right: tests/test_front_plan_host.py holds every one of them against recorded values.
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 #include "front_plan.hpp"
 
@@ -329,7 +330,51 @@ bool plan_front(uint32_t flags, float threshold, const ookd_filter *filter, doub
     if (pl.carrier_context()) pl.form = pl.form == OOKD_FRONT_TUNED_FIR1 ? OOKD_FRONT_TUNED_MULTI : OOKD_FRONT_TUNED_GENERIC;
     pl.tile_bits = front_tile_bits(probe);
     pl.sparse_capable = front_sparse_capable(probe);
+    // a filter only the generic kernels serve is refused here, not by every run's launch
+    if (pl.form == OOKD_FRONT_GENERIC || pl.form == OOKD_FRONT_TUNED_GENERIC) {
+        const char *who = num_carriers ? "ookd_rx_create_carriers" : nu != 0.0 ? "ookd_rx_create_tuned" : "ookd_rx_create";
+        if (!generic_tile_fits(fp.stage, fp.num_stages, who)) return false;
+        pl.gen_tile = generic_tile(fp.stage, fp.num_stages).tile;
+    }
     return true;
+}
+
+GenTile generic_tile(const FirStageDev *stage, uint32_t num_stages) {
+    GenTile g;
+    for (uint32_t tile = kGenTile; tile >= (uint32_t)kGenTileMin; tile >>= 1) {
+        // (64 bits, and a level of 2^30 samples -- 8 GiB -- stands for anything longer: a deep decimation chain
+        //  overflows 32 bits, and 64 without the cap)
+        uint64_t len = tile, even = 0, odd = 0;
+        for (int s = (int)num_stages - 1; s >= 0; --s) {    // the final level is not stored
+            len = std::min<uint64_t>((uint64_t)stage[s].decim * (len - 1) + stage[s].ntaps, 1ull << 30);
+            uint64_t &m = (s & 1) ? odd : even;
+            if (len > m) m = len;
+        }
+        g.lds_bytes = (even + odd + 2) * sizeof(float2);    // (of the smallest tile when none fits)
+        if (g.lds_bytes <= kGenLdsBytes) {
+            g.tile = tile;
+            g.lds_b_off = (uint32_t)even + 1;
+            return g;
+        }
+    }
+    return g;
+}
+
+bool generic_tile_fits(const FirStageDev *stage, uint32_t num_stages, const char *who) {
+    const GenTile g = generic_tile(stage, num_stages);
+    if (g.tile) return true;
+    uint64_t dec = 1;
+    bool more = false;          // (the product left 2^31: the text says "at least")
+    std::string taps;
+    for (uint32_t s = 0; s < num_stages; ++s) {
+        if (dec >> 31) more = true;
+        else dec *= stage[s].decim;
+        taps += (s ? ", " : "") + std::to_string(stage[s].ntaps);
+    }
+    set_error("%s: a filter of total decimation %s%llu with tap counts [%s] needs %llu bytes of LDS for the generic kernel's "
+              "smallest tile of %d outputs; the limit is %zu bytes", who, more ? "at least " : "", (unsigned long long)dec,
+              taps.c_str(), (unsigned long long)g.lds_bytes, kGenTileMin, kGenLdsBytes);
+    return false;
 }
 
 ookd_front_info front_info(const FrontPlan &pl, uint32_t k) {
@@ -367,6 +412,7 @@ extern "C" int ookd_front_plan_digest(uint32_t flags, float threshold, const ook
     d.mfma_xcd = pl.fp.mfma_xcd;
     d.quiet_lsb = pl.fp.quiet_lsb;
     d.mfma_use = (uint32_t)pl.mfma_use;
+    d.gen_tile = pl.gen_tile;
     const float bands[4] = {pl.fp.p_lo_n, pl.fp.p_hi_n, pl.fp.p_lo_w, pl.fp.p_hi_w};
     memcpy(d.band_bits, bands, sizeof(bands));
     auto fnv = [](const auto &v) { return fnv1a(kFnvBasis, v.data(), v.size() * sizeof(v[0])); };

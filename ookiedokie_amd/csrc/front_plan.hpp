@@ -54,6 +54,7 @@ struct FrontPlan {
     // wave tile (0 = a generic kernel) and whether that kernel honours FrontParams::sparse
     uint32_t form = 0, tile_bits = 0;
     bool sparse_capable = false;
+    uint32_t gen_tile = 0;      // final outputs per workgroup of a generic form (generic_tile), 0 for every other form
 
     bool carrier_context() const { return !carrier_tab.empty(); }
 };
@@ -62,6 +63,10 @@ struct FrontPlan {
 // false: the arguments are refused, error text set.
 bool plan_front(uint32_t flags, float threshold, const ookd_filter *filter, double nu, const ookd_rx_carrier *carriers,
                 uint32_t num_carriers, FrontPlan &out);
+
+// A filter the generic kernels serve must leave room for their smallest tile (generic_tile, kernels.hpp).  false:
+// it does not; the error text (starting with `who`) names the total decimation, the tap counts and the limit.
+bool generic_tile_fits(const FirStageDev *stage, uint32_t num_stages, const char *who);
 
 // ookd_rx_get_front_info / ookd_rx_get_carrier_front_info (k: the carrier, 0 without carriers)
 ookd_front_info front_info(const FrontPlan &plan, uint32_t k);
@@ -85,6 +90,7 @@ struct ookd_front_plan_digest_out {
     uint64_t image_fnv[4];              // 64-bit FNV-1a of the real taps, the A-fragment image, the complex taps, the carrier table
     ookd_front_info info[OOKD_RX_MAX_CARRIERS];
     uint32_t quiet_bits[OOKD_RX_MAX_CARRIERS][2];       // quiet_a, quiet_b as bit patterns
+    uint32_t gen_tile;                  // the generic kernels' tile for this filter, 0 when another kernel runs
 };
 extern "C" int ookd_front_plan_digest(uint32_t flags, float threshold, const ookd_filter *filter, double nu,
                                       const ookd_rx_carrier *carriers, uint32_t num_carriers,

@@ -587,14 +587,15 @@ typedef Fir2Geom<2, 1, 2, 2, 4> Fir2Dec4;      // fs128_fs16_dec4: (D 2, 16 taps
 // front end, generic: any number of stages / decimations, exact arithmetic
 // ---------------------------------------------------------------------------
 //
-// One workgroup = kGenTile final outputs.  Level 0 is the unpacked input,
+// One workgroup = `tile` final outputs (generic_tile(): kGenTile unless the
+// level buffers only hold less).  Level 0 is the unpacked input,
 // level s+1 the output of stage s; the slice of every level the tile needs
 // is produced in LDS, ping-ponging between two buffers.  Stage output J
 // (global) reads level-s inputs D*(J+1)-1-k (fir.c:290: the countdown starts
 // at D, so the first output is at input index D-1): gen_levels, front_dev.hpp.
 
 template <bool F32IN>
-__global__ __launch_bounds__(256) void fir_generic_kernel(const FrontParams p, uint32_t lds_b_off) {
+__global__ __launch_bounds__(256) void fir_generic_kernel(const FrontParams p, uint32_t lds_b_off, uint32_t tile) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2 *buf[2] = {reinterpret_cast<float2 *>(smem_raw),
                       reinterpret_cast<float2 *>(smem_raw) + lds_b_off};
@@ -602,10 +603,10 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(const FrontParams p, u
     const uint32_t tid = threadIdx.x;
     const uint32_t cap = blockIdx.y;
     const int S = (int)p.num_stages;
-    const int64_t j0 = (int64_t)blockIdx.x * kGenTile;
+    const int64_t j0 = (int64_t)blockIdx.x * tile;
     GenLevel lv[kMaxStages + 1];
     int64_t off[kMaxStages];
-    gen_levels(p, j0, kGenTile, lv, off);
+    gen_levels(p, j0, tile, lv, off);
 
     const uint32_t *src = F32IN ? nullptr
                                 : reinterpret_cast<const uint32_t *>(p.iq) + (uint64_t)cap * p.cap_stride;
@@ -650,7 +651,8 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(const FrontParams p, u
                 const bool valid = (i < n) && o >= 0 && (uint64_t)o < p.n_out;
                 const bool bit = valid && (power_ref(re, im) >= p.p_star);
                 const uint64_t ball = __ballot(bit);
-                if (words && lane_id() == 0) {
+                // (a tile below 256 outputs is one round: the waves past it own no word)
+                if (words && lane_id() == 0 && base + (tid & ~63u) < tile) {
                     words[((uint64_t)j0 + base + (tid & ~63u)) >> 6] = ball;
                 }
                 if (fout && valid) fout[o] = make_float2(re, im);
@@ -862,46 +864,30 @@ static size_t fir1_lds_bytes(const FrontParams &p) {
     return (size_t)kFirWgWaves * slots * sizeof(float2);
 }
 
-static void gen_level_sizes(const FrontParams &p, uint32_t len[kMaxStages + 1]) {
-    const int S = (int)p.num_stages;
-    len[S] = kGenTile;
-    for (int s = S - 1; s >= 0; --s) {
-        len[s] = p.stage[s].decim * (len[s + 1] - 1) + p.stage[s].ntaps;
-    }
-}
-
-size_t generic_lds_bytes(const FrontParams &p) {
-    uint32_t len[kMaxStages + 1];
-    gen_level_sizes(p, len);
-    uint32_t even = 0, odd = 0;
-    for (int s = 0; s < (int)p.num_stages; ++s) {   // the final level is not stored
-        if (s & 1) odd = len[s] > odd ? len[s] : odd;
-        else even = len[s] > even ? len[s] : even;
-    }
-    return (size_t)(even + odd + 2) * sizeof(float2);
+// the tiles of a launch: every output, and every bit word of the capture so the tail words are written (as zeros;
+// words_per_cap is a multiple of kBlockWords, a tile a power of two of at least one word)
+static uint64_t generic_tiles(const FrontParams &p, uint32_t tile) {
+    uint64_t tiles = (p.n_out + tile - 1) / tile;
+    if (p.bits && p.words_per_cap * 64 / tile > tiles) tiles = p.words_per_cap * 64 / tile;
+    return tiles;
 }
 
 hipError_t launch_front_generic(const FrontParams &p, uint32_t num_captures, hipStream_t stream) {
-    uint32_t len[kMaxStages + 1];
-    gen_level_sizes(p, len);
-    uint32_t even = 0;
-    for (int s = 0; s < (int)p.num_stages; s += 2) even = len[s] > even ? len[s] : even;
-    const size_t lds = generic_lds_bytes(p);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    // cover every bit word of the capture so the tail words are written (as zeros)
-    uint64_t tiles = (p.n_out + kGenTile - 1) / kGenTile;
-    if (p.bits && p.words_per_cap * 64 / kGenTile > tiles) tiles = p.words_per_cap * 64 / kGenTile;
+    const GenTile g = generic_tile(p.stage, p.num_stages);
+    if (!g.tile) return hipErrorInvalidValue;       // (plan_front / ookd_fir_create refuse such a filter)
+    const size_t lds = (size_t)g.lds_bytes;
+    const uint64_t tiles = generic_tiles(p, g.tile);
     if (tiles == 0) return hipSuccess;
     dim3 grid((uint32_t)tiles, num_captures);
     hipError_t e;
     if (p.iq_f32) {
         e = ensure_dynamic_lds(reinterpret_cast<const void *>(&fir_generic_kernel<true>), lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fir_generic_kernel<true>, grid, dim3(256), lds, stream, p, even + 1);
+        hipLaunchKernelGGL(fir_generic_kernel<true>, grid, dim3(256), lds, stream, p, g.lds_b_off, g.tile);
     } else {
         e = ensure_dynamic_lds(reinterpret_cast<const void *>(&fir_generic_kernel<false>), lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fir_generic_kernel<false>, grid, dim3(256), lds, stream, p, even + 1);
+        hipLaunchKernelGGL(fir_generic_kernel<false>, grid, dim3(256), lds, stream, p, g.lds_b_off, g.tile);
     }
     return hipGetLastError();
 }

@@ -27,7 +27,9 @@ constexpr int kFir1RShort = 8, kFir1RLong = 16;
 constexpr uint32_t kFir1ShortTaps = 256;        // padded tap count up to which the small tile is used (all)
 constexpr int kWaveTile = 64 * kFirR;           // 1024 outputs per wavefront
 constexpr int kQuietCounters = 1024;
-constexpr int kGenTile = 1024;          // final outputs per workgroup, generic kernel
+constexpr int kGenTile = 1024;          // final outputs per workgroup, generic kernels: the largest tile ...
+constexpr int kGenTileMin = 64;         // ... and the smallest (one bit word): generic_tile() picks between them
+constexpr size_t kGenLdsBytes = 160 * 1024;     // LDS the generic kernels' level buffers may take
 constexpr int kBlockWords = 64;         // one edge block = 64 words = 4096 bits
 constexpr int kPayloadWords = 5;        // 4 x u64 payload + 1 spare (bit index == max_bits)
 // ---- front end -------------------------------------------------------------
@@ -207,7 +209,18 @@ hipError_t launch_front_tuned_multi(const FrontParams &p, const TunedCarrierDev 
 // Generic multi-stage kernel regardless of shape (cross-check / streaming FIR).
 hipError_t launch_front_generic(const FrontParams &p, uint32_t num_captures,
                                 hipStream_t stream);
-size_t generic_lds_bytes(const FrontParams &p);
+// The tile of the generic kernels (real and complex taps alike) for a filter: the largest power of two in
+// [kGenTileMin, kGenTile] final outputs whose level buffers fit kGenLdsBytes -- level s of a tile of L outputs holds
+// len_s = D_s (len_{s+1} - 1) + T_s samples (len_S = L), even and odd levels ping-pong between two buffers of
+// float2, so a tile takes (max even len + max odd len + 2) * 8 bytes.  0: not even the smallest tile fits
+// (lds_bytes: what it would take); plan_front and ookd_fir_create refuse such a filter.  Pure host arithmetic, in
+// front_plan.cpp: the plan owns it, the launchers ask it.
+struct GenTile {
+    uint32_t tile = 0;          // final outputs per workgroup
+    uint32_t lds_b_off = 0;     // float2 offset of the second buffer
+    uint64_t lds_bytes = 0;
+};
+GenTile generic_tile(const FirStageDev *stage, uint32_t num_stages);
 
 // ---- edges -----------------------------------------------------------------
 

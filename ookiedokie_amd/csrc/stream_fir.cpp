@@ -9,6 +9,7 @@
 #include <memory>
 
 #include "common.hpp"
+#include "front_plan.hpp"
 #include "kernels.hpp"
 
 using namespace ookd;
@@ -70,6 +71,7 @@ ookd_fir *ookd_fir_create(int32_t hip_device, const ookd_filter *filter, size_t 
         f->halo_needed += (uint64_t)(d.ntaps - 1 + d.decim) * mult;
         mult *= d.decim;
     }
+    if (!generic_tile_fits(f->stage, f->num_stages, "ookd_fir_create")) return nullptr;
     const size_t out_max = max_input / 1 + 2;
     if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&f->d_taps), taps.size() * sizeof(float)) != hipSuccess ||
@@ -78,13 +80,6 @@ ookd_fir *ookd_fir_create(int32_t hip_device, const ookd_filter *filter, size_t 
         hipMalloc(reinterpret_cast<void **>(&f->d_halo), (f->halo_needed + 1) * 2 * sizeof(float)) != hipSuccess ||
         hipMemcpy(f->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("ookd_fir_create: device allocation failed");
-        return nullptr;
-    }
-    FrontParams probe{};
-    probe.num_stages = f->num_stages;
-    for (uint32_t s = 0; s < f->num_stages; ++s) probe.stage[s] = f->stage[s];
-    if (generic_lds_bytes(probe) > 160 * 1024) {
-        set_error("filter needs more than 160 KiB of LDS per tile");
         return nullptr;
     }
     ookd_fir_reset(f.get());

@@ -85,7 +85,7 @@ class PlanDigest(C.Structure):
                 ("sparse_capable", C.c_uint32), ("mfma_g", C.c_uint32), ("mfma_xcd", C.c_uint32),
                 ("quiet_lsb", C.c_int32), ("mfma_use", C.c_uint32), ("band_bits", C.c_uint32 * 4),
                 ("image_fnv", C.c_uint64 * 4), ("info", ok.FrontInfo * ok.RX_MAX_CARRIERS),
-                ("quiet_bits", (C.c_uint32 * 2) * ok.RX_MAX_CARRIERS)]
+                ("quiet_bits", (C.c_uint32 * 2) * ok.RX_MAX_CARRIERS), ("gen_tile", C.c_uint32)]
 
 
 MFMA_USE = ("taken", "not_considered", "valu_asked", "shape", "band_scale", "threshold_range")

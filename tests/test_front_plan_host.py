@@ -79,3 +79,53 @@ def test_refused_arguments_keep_their_error_texts():
         with pytest.raises(AssertionError) as e:
             P.plan_digest(case, filt)
         assert text in str(e.value)
+
+
+# ---- filters the generic kernels' smallest tile does not hold --------------------------------------------------------
+# (kernels.hip generic_tile: len_s = D_s (len_{s+1} - 1) + T_s from len_S = 64; (max even + max odd + 2) * 8 B <= 160 KiB)
+
+def _plan_of(stages, **kw):
+    case = dict(flags=0, threshold=0.1, nu=None, carriers=None)
+    case.update(kw)
+    return P.plan_digest(case, ok.Filter.from_stages([(d, [1.0 / t] * t) for d, t in stages]))
+
+
+@pytest.mark.parametrize("kw, form", [({}, ok.FRONT_GENERIC), (dict(nu=0.2), ok.FRONT_TUNED_GENERIC),
+                                      (dict(carriers=[(0.2, 0.1), (-0.31, 0.05)]), ok.FRONT_TUNED_GENERIC)],
+                         ids=["untuned", "tuned", "carriers"])
+def test_a_filter_that_fits_no_generic_tile_is_refused_by_the_plan(kw, form):
+    """the context, the tuned context and the carrier context refuse where they are created, with the total
+    decimation, the tap counts and the limit in the text; what fits a smaller tile than 1024 is accepted"""
+    for stages, dec, taps, need in (([(4096, 8)], 4096, "[8]", (63 * 4096 + 8 + 2) * 8),
+                                    ([(326, 1)], 326, "[1]", (63 * 326 + 1 + 2) * 8),
+                                    ([(325, 4)], 325, "[4]", (63 * 325 + 4 + 2) * 8),
+                                    # two stages: levels 0 and 1 lie in different buffers
+                                    ([(16, 16), (20, 5)], 320, "[16, 5]", (16 * (63 * 20 + 5 - 1) + 16 + 63 * 20 + 5 + 2) * 8)):
+        assert need > 160 * 1024
+        with pytest.raises(AssertionError) as e:
+            _plan_of(stages, **kw)
+        text = str(e.value)
+        assert ("ookd_rx_create_carriers:" if "carriers" in kw else "ookd_rx_create_tuned:" if "nu" in kw
+                else "ookd_rx_create:") in text, text
+        assert "total decimation %d " % dec in text and "tap counts %s" % taps in text, text
+        assert "%d bytes" % need in text and "163840 bytes" in text and "64 outputs" in text, text
+    for stages in ([(64, 64)], [(19, 64)], [(20, 19)], [(325, 3)], [(2, 8)] * 4, [(3, 21), (2, 9), (5, 40)],
+                   [(16, 16), (19, 5)]):
+        assert _plan_of(stages, **kw).form == form, stages
+
+
+def test_the_generic_kernels_tile_per_shape():
+    """the largest power of two in [64, 1024] whose level buffers fit, worked out by hand in
+    tests/front_shapes_inputs.py: the GPU tests of the smaller tiles run the tiles they name"""
+    from tests import front_shapes_inputs as S
+    for name, shape in dict(S.GENERIC_SHAPES, **S.LARGE_SHAPES).items():
+        for kw in ({}, dict(nu=0.2), dict(carriers=[(0.2, 0.1), (-0.31, 0.05)])):
+            assert _plan_of(shape, **kw).gen_tile == S.TILES[name], (name, kw)
+    assert sorted(set(S.TILES.values())) == [64, 128, 256, 512, 1024]
+    assert _plan_of([(1, 256)]).gen_tile == 0 and _plan_of([(325, 3)]).gen_tile == 64
+
+
+def test_the_fused_shapes_are_never_refused():
+    """(their kernels do not build levels in LDS: the limit is the generic kernels' alone)"""
+    assert _plan_of([(1, 256)]).form == ok.FRONT_FIR1_MFMA
+    assert _plan_of([(2, 16), (2, 32)]).form == ok.FRONT_FIR2_MFMA

@@ -128,12 +128,24 @@ DISPATCH = [
     ("tiny_taps_scale", "tiny60", {}, 2.0 ** -20, "fir1"),
     # taps beyond 2^100 of scaling: mfma_prepare_taps refuses
     ("taps_1e-35", "tiny116", {}, 1e-30, "fir1"),
+    # where the two-stage family ends: one tap more than (16, 32), any decimations but 2 x 2, any other stage count
+    ("fir2_17x32", "st:2x17,2x32", {}, 0.1, "generic"),
+    ("fir2_16x33", "st:2x16,2x33", {}, 0.1, "generic"),
+    ("dec2x1", "st:2x16,1x32", {}, 0.1, "generic"),
+    ("dec1x2", "st:1x16,2x32", {}, 0.1, "generic"),
+    ("dec2x4", "st:2x16,4x32", {}, 0.1, "generic"),
+    ("dec4_one_stage", "st:4x32", {}, 0.1, "generic"),
+    ("dec2x2x2", "st:2x16,2x32,2x8", {}, 0.1, "generic"),
 ]
 
 
 def _dispatch_filter(oracle, tmp_path, spec):
     if spec is None:
         return None
+    if spec.startswith("st:"):              # "st:2x17,2x32": (decimation x taps) per stage
+        shape = [tuple(int(v) for v in stage.split("x")) for stage in spec[3:].split(",")]
+        rng = np.random.default_rng(sum(d * 100 + t for d, t in shape))
+        return _write(tmp_path, spec[3:].replace(",", "_"), [(d, _taps(rng, t, "rand24", 1.2)) for d, t in shape])
     if spec.startswith("taps"):
         n = int(spec[4:])
         return _write(tmp_path, spec, [(1, _taps(np.random.default_rng(n), n, "rand24"))])
@@ -262,12 +274,20 @@ def _margin_capture(stages, A, rng, seg_out=4096):
     return _iq(i.astype(np.int16), q.astype(np.int16)), ("aligned", "cancel", "tones", "noise"), seg_out
 
 
-MARGIN_FILTERS = ["t32", "t64", "t128", "t256", "t255", "dec4"]
+MARGIN_FILTERS = ["t32", "t64", "t128", "t256", "t255", "dec4", "dec4_3x5", "dec4_16x1", "dec4_1x32", "dec4_15x31"]
+
+
+def _two_stage_taps(name):
+    """(n1, n2) of a two-stage name: "dec4" is the family's largest shape, "dec4_3x5" has (3, 5) taps; None for any other name"""
+    if not name.startswith("dec4"):
+        return None
+    return (16, 32) if name == "dec4" else tuple(int(v) for v in name[5:].split("x"))
 
 
 def _margin_stages(name, kind, rng):
-    if name == "dec4":
-        return [(2, _taps(rng, 16, kind, 1.2)), (2, _taps(rng, 32, kind, 1.2))]
+    if _two_stage_taps(name):
+        n1, n2 = _two_stage_taps(name)
+        return [(2, _taps(rng, n1, kind, 1.2)), (2, _taps(rng, n2, kind, 1.2))]
     return [(1, _taps(rng, int(name[1:]), kind))]
 
 
@@ -283,15 +303,16 @@ def test_error_bound_margin(ok, oracle, tmp_path, record_property, name, kind):
     path = _write(tmp_path, "%s_%s" % (name, kind), stages)
     f = ok.Filter.load(path)
     of = oracle.load_filter_json(path)
-    mfma = forms["mfma2"] if name == "dec4" else forms["mfma1"]
-    valu = forms["fir2"] if name == "dec4" else forms["fir1"]
+    two = _two_stage_taps(name) is not None
+    mfma = forms["mfma2"] if two else forms["mfma1"]
+    valu = forms["fir2"] if two else forms["fir1"]
     worst = {}
     for amp, A in (("nominal", 2047), ("wide", 32767)):
         iq, segs, seg_out = _margin_capture(stages, A, rng)
         n = iq.size // 2
         want = oracle.rx(iq, of, 0.1, None, 8192, want_bits=True, want_fir=True)
         g, D = _folded(stages)
-        if name != "dec4":
+        if not two:
             # the construction does what it says: the aligned outputs reach sum|h| A
             y64 = _sum64(iq, g, D)
             assert np.abs(y64.real[:seg_out]).max() >= 0.999 * np.abs(g).sum() * A / 2048.0
@@ -307,7 +328,7 @@ def test_error_bound_margin(ok, oracle, tmp_path, record_property, name, kind):
             assert (rx.bits() == want.bits).all(), (amp, valu_leg)
             err = info["err_valu"] if valu_leg else info["err_wide" if amp == "wide" else "err_nominal"]
             assert err > 0
-            if not valu_leg and kind == "exact22" and name != "dec4":
+            if not valu_leg and kind == "exact22" and not two:
                 assert info["mfma_delta"] == 0.0
             if not valu_leg and kind == "rand24":
                 assert info["mfma_delta"] > 0.0
@@ -348,7 +369,7 @@ def _tight_capture(stages, err, A, n_out, rng):
 
 
 @pytest.mark.parametrize("amp", ["nominal", "wide"])
-@pytest.mark.parametrize("name", ["fs32_fs4", "sinc255", "fs128_fs16_dec4"])
+@pytest.mark.parametrize("name", ["fs32_fs4", "sinc255", "fs128_fs16_dec4", "dec4_3x5", "dec4_1x32"])
 def test_tight_bits_at_threshold(ok, oracle, tmp_path, name, amp):
     """Full-scale partial sums that cancel to an output at the threshold, thousands of times: bits and edges are the
     oracle's, the matrix-core form ran, and every output the bound cannot place went through the exact recompute --
@@ -359,6 +380,9 @@ def test_tight_bits_at_threshold(ok, oracle, tmp_path, name, amp):
         k = np.arange(255) - 127
         h = np.sinc(k / 32.0) * np.hamming(255)
         stages = [(1, (h / h.sum()).astype(np.float32))]
+        path = _write(tmp_path, name, stages)
+    elif _two_stage_taps(name):
+        stages = _margin_stages(name, "rand24", np.random.default_rng(sum(_two_stage_taps(name))))
         path = _write(tmp_path, name, stages)
     else:
         stages = _golden_stages(oracle, name)
@@ -415,7 +439,7 @@ def _placements(n):
 
 
 @pytest.mark.parametrize("wide_value", [32760, -32760])
-@pytest.mark.parametrize("name", ["t32", "t255", "fs128_fs16_dec4"])
+@pytest.mark.parametrize("name", ["t32", "t255", "fs128_fs16_dec4", "dec4_3x5"])
 def test_wide_sample_placement(ok, oracle, tmp_path, name, wide_value):
     """One wide sample (beyond +-2048, low five bits non-zero) in an otherwise nominal loud capture, placed in the
     history of the next tile only, at a tile's first / last sample, in the first and in the last (partial) tile: the
@@ -426,6 +450,12 @@ def test_wide_sample_placement(ok, oracle, tmp_path, name, wide_value):
     if name == "fs128_fs16_dec4":
         stages = _golden_stages(oracle, name)
         path = golden_path("filters", name)
+        want_form = forms["mfma2"]
+    elif _two_stage_taps(name):
+        # (large leading taps in both stages, as _spiky_taps: the folded filter's first taps weigh a sample heavily)
+        n1, n2 = _two_stage_taps(name)
+        stages = [(2, _spiky_taps(rng, 4 + n1)[:n1]), (2, _spiky_taps(rng, 4 + n2)[:n2])]
+        path = _write(tmp_path, name, stages)
         want_form = forms["mfma2"]
     else:
         stages = [(1, _spiky_taps(rng, int(name[1:])))]
