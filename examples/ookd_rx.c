@@ -171,6 +171,9 @@ int main(int argc, char **argv)
     rc.samples_per_buffer = cfg.samples_per_buffer;
     rc.max_samples = n ? n : 1;
     rc.flags = (uint32_t) sdr_hip_file_sample_flags(sdr);   /* a .cs8 / .cu8 capture: an 8-bit context */
+    /* a tuned decode of a 2 x decimate-by-2 filter (the backend default) runs the fused kernel; without effect on
+     * every other context */
+    rc.flags |= OOKD_RX_TUNED_FIR2;
     ookd_tune tune;
     memset(&tune, 0, sizeof(tune));
     tune.nu = rate ? tune_hz / (double) rate : 0.0;     /* cycles per input sample; 0 = ookd_rx_create */

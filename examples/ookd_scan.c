@@ -153,7 +153,8 @@ int main(int argc, char **argv)
         memset(&rc, 0, sizeof(rc));
         rc.samples_per_buffer = cfg.samples_per_buffer;
         rc.max_samples = n ? n : 1;
-        rc.flags = sample_flags;
+        /* (a 2 x decimate-by-2 filter, the backend default, runs the fused tuned kernel once per carrier) */
+        rc.flags = sample_flags | OOKD_RX_TUNED_FIR2;
         rx = ookd_rx_create_carriers(&rc, filter, device[d], carrier, ncar);
         if (!rx) { fail("ookd_rx_create_carriers"); goto out; }
         if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }

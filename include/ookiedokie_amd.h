@@ -235,7 +235,16 @@ enum {
      * capture in HBM first.  Zero padding is value 0 of the format (the byte 128 for CU8).  Both
      * bits set: ookd_rx_create fails. */
     OOKD_RX_SAMPLES_CS8 = 1u << 10,
-    OOKD_RX_SAMPLES_CU8 = 1u << 11
+    OOKD_RX_SAMPLES_CU8 = 1u << 11,
+    /* Tuned and carrier contexts (ookd_rx_create_tuned with nu != 0, ookd_rx_create_carriers) on a
+     * filter of two decimate-by-2 stages with <= 16 and <= 32 taps (the backend default
+     * fs128_fs16_dec4): run the fused kernel OOKD_FRONT_TUNED_FIR2 -- packed FMAs, guard band with
+     * recompute in the contract's order, quiet shortcut, sparse output -- in place of
+     * OOKD_FRONT_TUNED_GENERIC.  The contract is unchanged: bits, edges, messages and error
+     * positions are those of ookd_filter_tuned_taps's contract, exactly; OOKD_RX_KEEP_FIR floats are
+     * within err_valu per component.  Accepted and without effect on every other context: untuned
+     * ones, nu = 0, other filter shapes, OOKD_RX_EXACT_FIR. */
+    OOKD_RX_TUNED_FIR2 = 1u << 12
 };
 
 /* Contexts created with the same gate (and on the same device) queue their front-end kernels one
@@ -339,8 +348,8 @@ enum {
     OOKD_FRONT_FIR1_MFMA_8 = 10,
     OOKD_FRONT_FIR2_MFMA_8 = 11,
     /* Tuned contexts (ookd_rx_create_tuned, nu != 0): complex taps on the raw
-     * samples.  Both read SC16Q11; an 8-bit tuned context runs them on a widened
-     * staging copy of the capture, like the non-fused forms above. */
+     * samples.  All of them read SC16Q11; an 8-bit tuned context runs them on a
+     * widened staging copy of the capture, like the non-fused forms above. */
     OOKD_FRONT_TUNED_GENERIC = 12,  /* any shape, the contract's order throughout
                                        (also what OOKD_RX_EXACT_FIR selects):
                                        KEEP_FIR floats are the contract's       */
@@ -350,7 +359,12 @@ enum {
     /* Carrier contexts (ookd_rx_create_carriers): OOKD_FRONT_TUNED_FIR1's shape for
      * all carriers in one pass over the capture.  Every other shape, and
      * OOKD_RX_EXACT_FIR, runs OOKD_FRONT_TUNED_GENERIC once per carrier and reports 12. */
-    OOKD_FRONT_TUNED_MULTI = 14
+    OOKD_FRONT_TUNED_MULTI = 14,
+    /* Tuned and carrier contexts created with OOKD_RX_TUNED_FIR2: 2 x decimate-by-2
+     * (<= 16, <= 32 taps), packed-VALU FMA (four per sample-tap) in both stages +
+     * guard band, recompute in contract order from the raw window.  A carrier
+     * context runs it once per carrier and reports 15 too. */
+    OOKD_FRONT_TUNED_FIR2 = 15
 };
 
 /* The front end a context settled on at create time, and the forward error
@@ -363,13 +377,15 @@ typedef struct ookd_front_info {
     uint32_t mfma_ksteps;           /* K-steps of the matrix-core product (0 = none prepared) */
     float p_star;                   /* smallest power whose sqrtf >= threshold */
     float p_lo, p_hi;               /* the packed-VALU kernels' band (tuned
-                                       context: OOKD_FRONT_TUNED_FIR1's)       */
+                                       context: OOKD_FRONT_TUNED_FIR1's or
+                                       OOKD_FRONT_TUNED_FIR2's)                */
     float mfma_c;                   /* matrix-core accumulator -> output scale */
     double err_nominal;             /* matrix-core form, samples in [-2048, 2047] */
     double err_wide;                /* matrix-core form, any int16 samples     */
     double err_valu;                /* packed-VALU form, any int16 samples
-                                       (tuned context: OOKD_FRONT_TUNED_FIR1
-                                       against the contract's order)           */
+                                       (tuned context: OOKD_FRONT_TUNED_FIR1 or
+                                       OOKD_FRONT_TUNED_FIR2 against the
+                                       contract's order)                       */
     double mfma_delta;              /* sum |h - (h1 + h2)|: what the two fp16
                                        tap pieces do not carry                 */
 } ookd_front_info;
@@ -393,9 +409,15 @@ ookd_rx *ookd_rx_create(const ookd_rx_config *cfg, const ookd_filter *filter,
  * every run entry point below works.  OOKD_RX_FIR_VALU is accepted and changes
  * nothing.  Fails for NaN or |nu| > 0.5, and for nu != 0 without a filter:
  * |x| of the unfiltered samples does not depend on nu, there is nothing to tune.
- * Not tuned (yet): the matrix-core forms, the folded decimate-by-4 kernel (a
- * tuned fs128_fs16_dec4 runs OOKD_FRONT_TUNED_GENERIC), ookd_fir_*.  (The
- * envelope survey has its own tuned entry point: ookd_survey_create_tuned.) */
+ * Not tuned (yet): the matrix-core forms, ookd_fir_*.  (The envelope survey has
+ * its own tuned entry point: ookd_survey_create_tuned.)
+ * Two decimate-by-2 stages (<= 16 and <= 32 taps, e.g. fs128_fs16_dec4) run
+ * OOKD_FRONT_TUNED_GENERIC unless cfg->flags holds OOKD_RX_TUNED_FIR2: then the
+ * fused kernel OOKD_FRONT_TUNED_FIR2 runs, unless OOKD_RX_EXACT_FIR is set too.
+ * The contract does not change with the flag: bits, edges, messages and error
+ * positions are those of ookd_filter_tuned_taps's contract, exactly, and
+ * OOKD_RX_KEEP_FIR floats are within err_valu per component (bitwise the
+ * contract's without the flag).  On every other shape the flag changes nothing. */
 typedef struct ookd_tune {
     double nu;                      /* cycles per input sample, |nu| <= 0.5     */
     uint64_t reserved[3];           /* zero                                     */
@@ -441,7 +463,12 @@ double ookd_rx_tune(const ookd_rx *rx);    /* nu of the context, 0 for an untune
  * one (decimating or multi-stage filters, more than 256 taps) or with
  * OOKD_RX_EXACT_FIR: then the generic kernel runs once per carrier.  8-bit
  * contexts (OOKD_RX_SAMPLES_CS8 / _CU8) widen the capture ONCE into a staging
- * copy and run either form on it.
+ * copy and run either form on it.  With OOKD_RX_TUNED_FIR2 and a filter of two
+ * decimate-by-2 stages (<= 16, <= 32 taps), without OOKD_RX_EXACT_FIR, the
+ * fused kernel OOKD_FRONT_TUNED_FIR2 runs once per carrier in place of the
+ * generic one and 15 is reported; the contract above is unchanged (carrier k is
+ * the tuned context created with the flag, bits exactly the contract's, floats
+ * within err_valu per component).
  *
  * Fails, with a message: num_carriers == 0 or > OOKD_RX_MAX_CARRIERS,
  * carriers == NULL, a NaN nu, |nu| > 0.5, no filter, non-zero reserved words,

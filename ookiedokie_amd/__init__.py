@@ -54,6 +54,7 @@ RX_SCAN_TABLES = 512
 # CU8 u = SC16Q11 16 (u - 128) (rtl_sdr .cu8)
 RX_SAMPLES_CS8 = 1024
 RX_SAMPLES_CU8 = 2048
+RX_TUNED_FIR2 = 4096                    # tuned / carrier contexts: the fused kernel for 2 x decimate-by-2 filters
 SAMPLE_FORMATS = {"sc16q11": (0, np.int16), "cs8": (RX_SAMPLES_CS8, np.int8), "cu8": (RX_SAMPLES_CU8, np.uint8)}
 # front-end forms (stats["front_form"], Receiver.front_info()["form"]): OOKD_FRONT_*
 FRONT_NO_FILTER = 1
@@ -70,6 +71,7 @@ FRONT_FIR2_MFMA_8 = 11
 FRONT_TUNED_GENERIC = 12                # a tuned context (Receiver(tune=...)): any shape, the contract's order
 FRONT_TUNED_FIR1 = 13                   # ... 1 stage, decimation 1, <= 256 taps: packed FMAs + guard band
 FRONT_TUNED_MULTI = 14                  # a carrier context (Receiver(carriers=[...])): that shape, all carriers in one pass
+FRONT_TUNED_FIR2 = 15                   # Receiver(..., tuned_fir2=True): 2 x decimate-by-2, packed FMAs + guard band
 RX_MAX_CARRIERS = 16
 SURVEY_GENERIC = 1                      # survey forms (Survey.form): OOKD_SURVEY_*; what an untuned Survey runs
 SURVEY_TUNED_GENERIC = 2                # a tuned Survey (Survey(tune=...)): any shape, the contract's order
@@ -687,7 +689,7 @@ class Receiver:
                  scan_tables: bool = False, sample_format: str = "sc16q11",
                  tune: Optional[float] = None, tune_hz: Optional[float] = None,
                  sample_rate: Optional[float] = None,
-                 carriers: Optional[Sequence] = None):
+                 carriers: Optional[Sequence] = None, tuned_fir2: bool = False):
         """tune: carrier offset in cycles per input sample (|tune| <= 0.5), or tune_hz with sample_rate -- one
         of the two forms.  The context then filters with the taps `Filter.tuned_taps` returns (ookd_rx_create_tuned);
         0 is an untuned context.
@@ -695,7 +697,11 @@ class Receiver:
         carriers: several carriers of ONE capture decoded in one pass (ookd_rx_create_carriers): entries are `nu`
         (cycles per input sample, with this receiver's `threshold`) or `(nu, threshold)`.  Not together with tune /
         tune_hz.  Such a context runs one capture per run; wherever a method takes a capture index it takes the
-        carrier index, and a result's `captures` field holds each message's carrier."""
+        carrier index, and a result's `captures` field holds each message's carrier.
+
+        tuned_fir2: a tuned or carrier context on a filter of two decimate-by-2 stages (<= 16 and <= 32 taps, the
+        backend default fs128_fs16_dec4) runs the fused kernel FRONT_TUNED_FIR2 instead of FRONT_TUNED_GENERIC
+        (OOKD_RX_TUNED_FIR2): same bits, floats within err_valu.  Changes nothing for any other context."""
         if carriers is not None and (tune is not None or tune_hz is not None):
             raise ValueError("carriers and tune / tune_hz are mutually exclusive: a carrier list names every nu")
         if tune is not None and (tune_hz is not None or sample_rate is not None):
@@ -716,7 +722,8 @@ class Receiver:
                      | (RX_FSM_ROUNDS if fsm_rounds else 0) | (0 if quiet_skip else RX_NO_QUIET_SKIP)
                      | (RX_COUNT_QUIET if count_quiet else 0) | (RX_SCAN_SIMS if scan_sims else 0)
                      | (0 if pipeline else RX_NO_PIPELINE)
-                     | (RX_FIR_VALU if fir_valu else 0) | (RX_SCAN_TABLES if scan_tables else 0) | fmt_flag)
+                     | (RX_FIR_VALU if fir_valu else 0) | (RX_SCAN_TABLES if scan_tables else 0) | fmt_flag
+                     | (RX_TUNED_FIR2 if tuned_fir2 else 0))
         cfg.threshold = threshold
         cfg.samples_per_buffer = samples_per_buffer
         cfg.max_samples = max_samples

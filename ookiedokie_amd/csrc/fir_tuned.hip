@@ -16,6 +16,10 @@
 //                              recompute in the contract's order
 //   fir1_tuned_multi_kernel  : the same shape for K carriers in one pass over the capture (OOKD_FRONT_TUNED_MULTI):
 //                              loads, quiet statistics and unpack once per tile, accumulation and epilogue per carrier
+//   fir2_tuned_kernel        : 2 stages of decimation 2, <= 16 and <= 32 taps, on request (OOKD_FRONT_TUNED_FIR2):
+//                              fir2_bits_kernel's tile (kernels.hip) with complex taps -- level 0 raw in LDS, level 1
+//                              float2, fused packed FMAs in both stages, quiet test, guard band, recompute in the
+//                              contract's order from the raw window
 //   fir_tuned_generic_kernel : the contract for every shape (OOKD_FRONT_TUNED_GENERIC)
 //
 // Compiled with -ffp-contract=off (see kernels.hip).
@@ -315,6 +319,229 @@ void fir1_tuned_multi_kernel(const FrontParams p, const TunedCarrierDev *tab,
 }
 
 // ---------------------------------------------------------------------------
+// two decimate-by-2 stages (the backend default fs128_fs16_dec4), fused: fir2_bits_kernel's tile with complex taps
+// ---------------------------------------------------------------------------
+// One wavefront = one tile of G::F final outputs, working alone, in Fir2Geom's LDS layout (front_dev.hpp): level 0
+// stays raw (4 B per sample, lane stride P1 + 1), stage 1 leaves the L1 level-1 outputs stage 2 needs as float2
+// (lane stride P2 + 1).  Stage output J reads inputs D (J + 1) - 1 - k; tap k of a chunk of 16 complex taps sits in
+// one SGPR pair, every output receives its taps in ascending order (the contract's), fused: two v_pk_fma_f32 per
+// sample-tap (cmac_tuned<false>).  tuned_guard_error over both stages bounds what that differs from the contract by.
+__device__ __forceinline__ v2f tuned2_sample(const v2f *base, int i) { return base[i]; }
+__device__ __forceinline__ v2f tuned2_sample(const uint32_t *base, int i) {        // the raw SC16Q11 level
+    const float2 v = unpack_iq(base[i]);
+    return (v2f){v.x, v.y};
+}
+
+// Window position W (newest first) feeds output r with tap kk = D r - D (R - 1) + W of the chunk when 0 <= kk < 16.
+template <int D, int R, int P, int CHUNK_OFF, int W, typename In, int... Rs>
+__device__ __forceinline__ void tuned2_wstep(v2f *acc, const v2f *tpair, const In *base,
+                                             std::integer_sequence<int, Rs...>) {
+    // sample index inside the lane's window: c = Tpad - 1 + D (R - 1) - 16 chunk - W
+    constexpr int c = CHUNK_OFF + D * (R - 1) - W;
+    static_assert(c >= 0, "window underflow");
+    const v2f x = tuned2_sample(base, c + c / P);
+    ((void)((D * Rs - D * (R - 1) + W >= 0 && D * Rs - D * (R - 1) + W < kTunedChunk)
+                ? (cmac_tuned<false>(acc[Rs], tpair[(D * Rs - D * (R - 1) + W) & 15], x), 0)
+                : 0),
+     ...);
+}
+
+// chunk CH of a stage's taps (16 pairs at ct + 32 CH): tap k = 16 CH + kk of output r reads window sample
+// (TPAD - 1) + D r - k
+template <int D, int R, int P, int TPAD, int CH, typename In, int... Ws>
+__device__ __forceinline__ void tuned2_chunk(v2f *acc, const float *ct, const In *base, std::integer_sequence<int, Ws...>) {
+    v2f tpair[16];
+    load_tap_chunk32(ct + 2 * kTunedChunk * CH, tpair);
+    (tuned2_wstep<D, R, P, TPAD - 1 - kTunedChunk * CH, Ws>(acc, tpair, base, std::make_integer_sequence<int, R>{}), ...);
+}
+
+template <int D, int R, int P, int TPAD, typename In, int... CHs>
+__device__ __forceinline__ void tuned2_stage(v2f *acc, const float *ct, const In *base, std::integer_sequence<int, CHs...>) {
+    (tuned2_chunk<D, R, P, TPAD, CHs>(acc, ct, base, std::make_integer_sequence<int, D * (R - 1) + kTunedChunk>{}), ...);
+}
+
+// The contract's value of one final output (guard-band path): the ntaps2 level-1 values it reads, each from the raw
+// level-0 window, then stage 2 -- tuned_step's four statements per tap per stage.  `j` = final output inside the tile.
+template <typename G>
+__device__ __noinline__ float2 fir2_tuned_exact_output(const uint32_t *lds0, const float *ct1, uint32_t ntaps1,
+                                                       const float *ct2, uint32_t ntaps2, uint32_t j) {
+    float ar2 = 0.0f, ai2 = 0.0f;
+    for (uint32_t k2 = 0; k2 < ntaps2; ++k2) {
+        const uint32_t j1 = G::D2 * j + (G::T2 - 1) - k2;               // local level-1 index
+        float ar1 = 0.0f, ai1 = 0.0f;
+        for (uint32_t k1 = 0; k1 < ntaps1; ++k1) {
+            const uint32_t i = G::D1 * j1 + (G::T1 - 1) - k1;           // local input index
+            tuned_step(ar1, ai1, ct1[2 * k1], ct1[2 * k1 + 1], unpack_iq(lds0[i + i / G::P1]));
+        }
+        tuned_step(ar2, ai2, ct2[2 * k2], ct2[2 * k2 + 1], make_float2(ar1, ai1));
+    }
+    return make_float2(ar2, ai2);
+}
+
+template <typename G>
+__global__ __launch_bounds__(64) void fir2_tuned_kernel(const FrontParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    static_assert(G::T1 == kTunedChunk && G::T2 % kTunedChunk == 0, "whole chunks of complex taps");
+    const uint32_t tid = threadIdx.x & 63u;
+    const uint32_t cap = blockIdx.y;
+    const uint64_t J0 = ((uint64_t)blockIdx.x + p.tile_base) * G::F;       // first final output
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(p.iq) + (uint64_t)cap * p.cap_stride;
+    uint32_t *lds0 = reinterpret_cast<uint32_t *>(smem_raw);               // raw I,Q pairs
+    float2 *lds1 = reinterpret_cast<float2 *>(lds0 + G::slots0);
+    uint64_t *words = p.bits + (uint64_t)cap * p.words_per_cap;
+    const float *ct1 = p.ctaps + 2u * p.stage[0].tap_off, *ct2 = p.ctaps + 2u * p.stage[1].tap_off;
+
+    // global index of local input sample 0: D1 j1_0 + D1 - 1 - (T1 - 1) with j1_0 = D2 J0 + D2 - 1 - (T2 - 1).  J0 is
+    // a multiple of F, so the window starts the same kShift samples into a 16-byte vector in every tile and the
+    // vectors end with the window
+    constexpr int kA0 = G::D1 * ((G::D2 - 1) - (G::T2 - 1)) + (G::D1 - 1) - (G::T1 - 1);
+    constexpr int kShift = ((kA0 % 4) + 4) % 4;
+    constexpr int kVecs = (G::L0 + kShift) / 4;
+    constexpr int kRounds = (kVecs + 63) / 64;
+    static_assert((G::D1 * G::D2 * G::F) % 4 == 0 && (G::L0 + kShift) % 4 == 0 && kShift == 2 && kVecs >= 64,
+                  "the window is whole vectors but for its first two samples; the first load round is a full one");
+    const int64_t a0 = (int64_t)(G::D1 * G::D2) * (int64_t)J0 + kA0;
+
+    // ---- load + quiet test + store raw (as in fir2_bits_kernel, the test as in fir1_tuned_kernel) ----------
+    const bool aligned16 = ((reinterpret_cast<uintptr_t>(src) & 15u) == 0);
+    const bool interior = aligned16 && a0 >= kShift && (uint64_t)(a0 + G::L0) <= p.n_valid;
+    if (interior) {
+        const uint4 *src4 = reinterpret_cast<const uint4 *>(src + (a0 - kShift));
+        uint4 q[kRounds];
+#pragma unroll
+        for (int i = 0; i < kRounds; ++i) {
+            const uint32_t v = tid + 64u * i;
+            // (a lane without a vector in this round repeats its first one: the quiet test takes minima too)
+            q[i] = (64 * (i + 1) <= kVecs || v < (uint32_t)kVecs) ? ld_nt4(src4 + v) : q[0];
+        }
+        // ---- quiet test: fir1_tuned_kernel's bound over both stages --------------------------------------------
+        // For any constant d:  y1 = sum c1 (x - d) + d C1,  y2 = sum c2 (y1 - d C1) + d C1 C2,  hence
+        //     |y2| <= A1 A2 max|x - d| + |C1| |C2| |d|
+        // with A_s = sum |c_s[k]| and C_s = sum c_s[k]: the window's spread against all the taps, its offset against
+        // the chain's response at 0 Hz only.  The host folds the sums, the threshold and the float chains' rounding
+        // into quiet_a / quiet_b (front_plan.cpp: tuned_quiet_weights2); a, b as in fir1_tuned_kernel, over the L0
+        // samples of the window (the first vector's first two samples lie in front of it).
+        if (!p.fir_out && p.quiet_lsb > 0) {
+            uint4 f = q[0];
+            if (tid == 0) f.x = f.y = f.z;
+            v2s mx = __builtin_elementwise_max(__builtin_elementwise_max(as_v2s(f.x), as_v2s(f.y)),
+                                               __builtin_elementwise_max(as_v2s(f.z), as_v2s(f.w)));
+            v2s mn = __builtin_elementwise_min(__builtin_elementwise_min(as_v2s(f.x), as_v2s(f.y)),
+                                               __builtin_elementwise_min(as_v2s(f.z), as_v2s(f.w)));
+#pragma unroll
+            for (int i = 1; i < kRounds; ++i) {
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2s(q[i].x), as_v2s(q[i].y)));
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(as_v2s(q[i].z), as_v2s(q[i].w)));
+                mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2s(q[i].x), as_v2s(q[i].y)));
+                mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(as_v2s(q[i].z), as_v2s(q[i].w)));
+            }
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                mx = __builtin_elementwise_max(mx, as_v2s(__shfl_xor(__builtin_bit_cast(uint32_t, mx), d)));
+                mn = __builtin_elementwise_min(mn, as_v2s(__shfl_xor(__builtin_bit_cast(uint32_t, mn), d)));
+            }
+            const int ri = (int)mx.x - (int)mn.x, rq = (int)mx.y - (int)mn.y;
+            const int si = abs((int)mx.x + (int)mn.x), sq = abs((int)mx.y + (int)mn.y);
+            const float a = (float)max(ri, rq), b = (float)max(si, sq);
+            if (a * p.quiet_a + b * p.quiet_b < 1.0f) {
+                // (sparse output: nothing is stored -- see fir2_bits_kernel)
+                if (!p.sparse) {
+                    if (tid < G::F / 64) words[(J0 >> 6) + tid] = 0;
+                    if (tid == 0) p.tile_info[(uint64_t)cap * p.tiles_per_cap + J0 / G::F] = 0;
+                }
+                if (p.quiet_count && tid == 0) atomicAdd(p.quiet_count + (blockIdx.x % kQuietCounters), 1u);
+                return;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kRounds; ++i) {
+            const uint32_t v = tid + 64u * i;
+            if (64 * (i + 1) <= kVecs || v < (uint32_t)kVecs) {
+                const int i0 = 4 * (int)v - kShift;                 // local index of q[i].x
+                const uint32_t w4[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int li = i0 + e;
+                    if (li >= 0) lds0[li + li / G::P1] = w4[e];
+                }
+            }
+        }
+    } else {
+        // first / last tiles, halo, unaligned pointers: values outside the capture are zeros or the previous shard's
+        // samples -- all of them int16, so the level stays raw
+        for (int li = (int)tid; li < G::L0; li += 64) lds0[li + li / G::P1] = fetch_raw(p, src, a0 + li);
+    }
+    // both windows are private to this wavefront and the LDS executes one wave's accesses in order
+    wave_lds_fence();
+
+    // ---- stage 1: lane t -> local level-1 outputs R1 t .. R1 t + R1 - 1 ------------------------------------------
+    {
+        v2f acc[G::R1];
+#pragma unroll
+        for (int r = 0; r < G::R1; ++r) acc[r] = (v2f){0.0f, 0.0f};
+        tuned2_stage<G::D1, G::R1, G::P1, G::T1>(acc, ct1, lds0 + (G::P1 + 1) * tid, std::make_integer_sequence<int, G::N1>{});
+#pragma unroll
+        for (int r = 0; r < G::R1; ++r) {
+            const int j = G::R1 * (int)tid + r;
+            lds1[j + j / G::P2] = make_float2(acc[r].x, acc[r].y);
+        }
+    }
+    wave_lds_fence();
+
+    // ---- stage 2: lane t -> final outputs J0 + R2 t .. + R2 - 1 --------------------------------------------------
+    v2f acc[G::R2];
+#pragma unroll
+    for (int r = 0; r < G::R2; ++r) acc[r] = (v2f){0.0f, 0.0f};
+    tuned2_stage<G::D2, G::R2, G::P2, G::T2>(acc, ct2, reinterpret_cast<const v2f *>(lds1 + (G::P2 + 1) * tid),
+                                             std::make_integer_sequence<int, G::N2>{});
+
+    // ---- threshold, guard band, pack: R2 bits per lane, 64 / R2 lanes per word (fir2_bits_kernel's epilogue) ------
+    static_assert(G::R2 == 4, "bit packing below assumes 4 outputs per lane");
+    const uint64_t o0 = J0 + (uint64_t)tid * G::R2;
+    uint32_t nib = 0;
+    float2 *fout = p.fir_out ? reinterpret_cast<float2 *>(p.fir_out) + (uint64_t)cap * p.n_out : nullptr;
+#pragma unroll
+    for (int r = 0; r < G::R2; ++r) {
+        const bool valid = o0 + r < p.n_out;
+        const float pw = power_ref(acc[r].x, acc[r].y);
+        bool bit = pw >= p.p_hi;
+        if (valid && !bit && pw >= p.p_lo) {
+            // inside the guard band: redo this output in the contract's order
+            const float2 y = fir2_tuned_exact_output<G>(lds0, ct1, p.stage[0].ntaps, ct2, p.stage[1].ntaps, G::R2 * tid + r);
+            bit = power_ref(y.x, y.y) >= p.p_star;
+            if (p.recompute_count) atomicAdd(p.recompute_count, 1ull);
+        }
+        nib |= ((valid && bit) ? 1u : 0u) << r;
+        if (fout && valid) fout[o0 + r] = make_float2(acc[r].x, acc[r].y);
+    }
+    {
+        // level changes inside the tile, as in the 1-stage kernels
+        const uint32_t keep = o0 >= p.n_out ? 0u : (o0 + G::R2 <= p.n_out ? (uint32_t)G::R2 : (uint32_t)(p.n_out - o0));
+        const uint32_t prev_top = __shfl_up(nib >> (G::R2 - 1), 1);
+        uint32_t ch = (nib ^ (nib << 1)) & ((1u << G::R2) - 2u);
+        if (tid != 0) ch |= (nib ^ prev_top) & 1u;
+        ch &= (1u << keep) - 1u;
+        uint32_t cnt = __popc(ch);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nib & 1u));
+        const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)((nib >> (G::R2 - 1)) & 1u), 63);
+        const uint64_t chl = __ballot(ch != 0);         // (the word that holds the first change: R2 bits per lane)
+        const uint32_t widx = chl ? ((uint32_t)__builtin_ctzll(chl) * (uint32_t)G::R2) >> 6 : 0u;
+        if (tid == 0) {
+            p.tile_info[(uint64_t)cap * p.tiles_per_cap + J0 / G::F] =
+                cnt | (widx << kTileWordShift) | (first << 30) | (last << 31) | p.stamp_bits;
+        }
+    }
+    uint32_t half = nib << (4u * (tid & 7u));
+    half |= __shfl_xor(half, 1);
+    half |= __shfl_xor(half, 2);
+    half |= __shfl_xor(half, 4);                // lanes 8g..8g+7 hold outputs 32g..32g+31
+    const uint32_t hi = __shfl_down(half, 8);
+    if ((tid & 15u) == 0) words[(J0 >> 6) + (tid >> 4)] = (uint64_t)half | ((uint64_t)hi << 32);
+}
+
+// ---------------------------------------------------------------------------
 // any shape, the contract's order throughout: fir_generic_kernel (kernels.hip) with complex taps
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fir_tuned_generic_kernel(const FrontParams p, uint32_t lds_b_off, uint32_t tile) {
@@ -407,6 +634,31 @@ hipError_t launch_front_tuned_fir1(const FrontParams &p, uint32_t num_captures, 
     hipError_t e = ensure_dynamic_lds(fn, lds);
     if (e != hipSuccess) return e;
     e = hipExtLaunchKernel(fn, dim3((uint32_t)grid, num_captures), dim3(64), args, lds, stream, t0, t1, 0);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+bool front_uses_tuned_fir2(const FrontParams &p) {
+    // use_fir2's shape (kernels.hip: every level's phase is D - 1 when the origin is a multiple of the total
+    // decimation), tuned, asked for, and not forced to the contract's order (tune == 2)
+    return p.tune == 1 && p.tuned_fir2 && p.ctaps && p.num_stages == 2 && !p.iq_f32 && !p.halo_f32 &&
+           p.stage[0].decim == 2 && p.stage[1].decim == 2 && p.stage[0].ntaps <= (uint32_t)Fir2Dec4::T1 &&
+           p.stage[1].ntaps <= (uint32_t)Fir2Dec4::T2 && p.origin % 4 == 0;
+}
+
+hipError_t launch_front_tuned_fir2(const FrontParams &p, uint32_t num_captures, hipStream_t stream, hipEvent_t t0,
+                                   hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count) {
+    static_assert(kTunedFir2Tile == (uint32_t)Fir2Dec4::F, "the tile front_tile_bits reports");
+    if (!front_uses_tuned_fir2(p) || p.sample_fmt != kFmtSc16) return hipErrorInvalidValue;
+    const uint64_t all = (p.n_out + Fir2Dec4::F - 1) / Fir2Dec4::F;
+    const uint64_t b = tile_begin < all ? tile_begin : all;
+    const uint64_t grid = tile_count < all - b ? tile_count : all - b;
+    if (grid == 0) return hipSuccess;
+    FrontParams pp = p;
+    pp.tile_base = (uint32_t)b;
+    void *args[] = {&pp};
+    const void *fn = reinterpret_cast<const void *>(&fir2_tuned_kernel<Fir2Dec4>);
+    const hipError_t e = hipExtLaunchKernel(fn, dim3((uint32_t)grid, num_captures), dim3(64), args, Fir2Dec4::wave_bytes,
+                                            stream, t0, t1, 0);
     return e != hipSuccess ? e : hipGetLastError();
 }
 

@@ -43,6 +43,39 @@ __device__ __forceinline__ float2 fetch_sample(const FrontParams &p, const uint3
     return unpack_iq(src[n]);
 }
 
+// fetch_sample for int16 inputs, returned raw (packed I | Q << 16).
+__device__ __forceinline__ uint32_t fetch_raw(const FrontParams &p, const uint32_t *src, int64_t n) {
+    if (n < 0) {
+        const int64_t h = (int64_t)p.halo_len + n;
+        if (h < 0 || !p.halo) return 0u;
+        return reinterpret_cast<const uint32_t *>(p.halo)[h];
+    }
+    if ((uint64_t)n >= p.n_valid) return 0u;
+    return src[n];
+}
+
+// ---- geometry of the kernels for two decimating stages (fir2_bits_kernel, kernels.hip; fir2_tuned_kernel,
+// fir_tuned.hip): one wave = one tile of F final outputs; lane t's block of P = D * R consecutive samples of a level
+// starts at slot t * (P + 1) ----
+template <int D1_, int N1_, int D2_, int N2_, int R2_>
+struct Fir2Geom {
+    static constexpr int D1 = D1_, D2 = D2_, R2 = R2_;
+    static constexpr int T1 = 16 * N1_, T2 = 16 * N2_;         // padded tap counts
+    static constexpr int N1 = N1_, N2 = N2_;
+    static constexpr int F = 64 * R2;                           // final outputs per wave
+    static constexpr int L1need = D2 * (F - 1) + T2;            // stage-1 outputs stage 2 reads
+    static constexpr int R1 = (L1need + 63) / 64;
+    static constexpr int L1 = 64 * R1;                          // stage-1 outputs computed
+    static constexpr int L0 = D1 * (L1 - 1) + T1;               // input samples read
+    static constexpr int P1 = D1 * R1, P2 = D2 * R2;
+    static constexpr int kVecs = (L0 + 3 + 3) / 4;              // 16 B loads (the window may start mid-vector)
+    static constexpr int kVecRounds = (kVecs + 63) / 64;
+    static constexpr int slots0 = (L0 + L0 / P1 + 2 + 1) & ~1;  // level 0 stays RAW: 4 B per sample
+    static constexpr int slots1 = L1 + L1 / P2 + 2;             // level 1: float2
+    static constexpr int wave_bytes = ((slots0 * 4 + slots1 * 8) + 15) & ~15;
+};
+typedef Fir2Geom<2, 1, 2, 2, 4> Fir2Dec4;      // fs128_fs16_dec4: (D 2, 16 taps), (D 2, 32 taps)
+
 // ookiedokie.c:171-179: bit = sqrtf(re*re + im*im) >= thr.  sqrtf is
 // correctly rounded and monotone, so this equals power >= P*, P* being the
 // smallest float whose sqrtf is >= thr (host computes it).  The power keeps

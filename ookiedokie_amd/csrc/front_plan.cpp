@@ -233,6 +233,43 @@ bool tuned_quiet_weights(const std::vector<float> &re, const std::vector<float> 
     return true;
 }
 
+// Quiet test of fir2_tuned_kernel: the same bound through two stages.  For any constant d and exact arithmetic
+//     y1 = sum_k c1[k] (x - d) + d C1,      y2 = sum_k c2[k] (y1 - d C1) + d C1 C2,
+// so |y2| <= A1 A2 max|x - d| + |C1| |C2| |d| with A_s = sum_k |c_s[k]|, C_s = sum_k c_s[k] over the rounded taps of
+// stage s: the window's spread against all the taps, its offset against the chain's response at 0 Hz.  With a, b of
+// the tile's whole input window as above the tile is quiet when
+//     sqrt(2) / (2 * 2048) * ((A + e) a + (G + e) b) < 0.999 thr,
+//     A = A1 A2,  G = |C1| |C2| + 1e-12 S,  e = 1.01 (2 T1 + 1 + 2 T2 + 1) u S,  S = prod_s max(sum_k (|re| + |im|), 1)
+// (e: the contract's float chain against the exact one, as tuned_guard_error counts it).  Folded into the two
+// weights exactly as tuned_quiet_weights does.
+bool tuned_quiet_weights2(const std::vector<std::vector<float>> &re, const std::vector<std::vector<float>> &im, float threshold,
+                          uint32_t flags, float &quiet_a, float &quiet_b) {
+    if (!(threshold > 0.0f) || !std::isfinite(threshold) || (flags & OOKD_RX_NO_QUIET_SKIP)) return false;
+    double A = 1.0, G = 1.0, S = 1.0, T = 0.0;
+    for (size_t s = 0; s < re.size(); ++s) {
+        double as = 0.0, ss = 0.0, gr = 0.0, gi = 0.0;
+        for (size_t k = 0; k < re[s].size(); ++k) {
+            as += std::hypot((double)re[s][k], (double)im[s][k]);
+            ss += std::fabs((double)re[s][k]) + std::fabs((double)im[s][k]);
+            gr += (double)re[s][k];
+            gi += (double)im[s][k];
+        }
+        A *= as;
+        G *= std::hypot(gr, gi);
+        S *= std::max(ss, 1.0);
+        T += 2.0 * (double)re[s].size() + 1.0;
+    }
+    if (!(A > 0.0)) return false;
+    G += 1e-12 * S;                                         // (the double sums' own rounding)
+    const double e = 1.01 * T * std::ldexp(1.0, -24) * S;
+    const double scale = 1.41421356237309515 / (2.0 * 2048.0) / (0.999 * (double)threshold);
+    const double qa = (A + e) * scale, qb = (G + e) * scale;
+    if (!(qa < 1e30) || !(qb < 1e30)) return false;
+    quiet_a = nextafterf((float)qa, INFINITY);
+    quiet_b = nextafterf((float)qb, INFINITY);
+    return true;
+}
+
 // One carrier at c.nu with c.threshold / c.p_star: its taps appended to pl.ctaps in the device layout (stage s at
 // 2 * tap_off, zero padded to ntaps_pad pairs) and, unless the context computes in the contract's order throughout,
 // its forward bound, guard band and quiet weights.  -> the quiet test applies to this carrier
@@ -257,7 +294,12 @@ bool plan_carrier(FrontPlan &pl, const ookd_filter &filter, uint32_t flags, Carr
     if (pl.exact) return false;
     c.err_valu = tuned_guard_error(re, im, 16.0);
     band_from_error(c.err_valu, c.p_star, c.p_lo, c.p_hi);
-    // (the shape front_uses_tuned_fir1 takes: the only tuned kernels with a quiet test)
+    // (the shapes front_uses_tuned_fir1 and, where asked for, front_uses_tuned_fir2 take: the tuned kernels with a
+    //  quiet test)
+    if (fp.tuned_fir2 && fp.num_stages == 2 && fp.stage[0].decim == 2 && fp.stage[1].decim == 2 &&
+        fp.stage[0].ntaps <= 16u && fp.stage[1].ntaps <= 32u) {
+        return tuned_quiet_weights2(re, im, c.threshold, flags, c.quiet_a, c.quiet_b);
+    }
     return fp.num_stages == 1 && fp.stage[0].decim == 1 && fp.stage[0].ntaps_pad <= 256u &&
            tuned_quiet_weights(re[0], im[0], c.threshold, flags, c.quiet_a, c.quiet_b);
 }
@@ -293,6 +335,8 @@ bool plan_front(uint32_t flags, float threshold, const ookd_filter *filter, doub
     // A tuned context is one carrier, a carrier context K of them (fir_tuned.hip): each with the packed-FMA kernel's
     // guard band and quiet test in place of the real-tap ones; a carrier context also gets the fused kernel's table.
     const uint32_t K = num_carriers ? num_carriers : nu != 0.0 ? 1u : 0u;
+    // (OOKD_RX_TUNED_FIR2 says something to a tuned or carrier context only; the shape: front_uses_tuned_fir2)
+    fp.tuned_fir2 = (K && filter && (flags & OOKD_RX_TUNED_FIR2)) ? 1u : 0u;
     for (uint32_t k = 0; k < K; ++k) {
         CarrierPlan c;
         c.nu = num_carriers ? carriers[k].nu : nu;
@@ -326,8 +370,10 @@ bool plan_front(uint32_t flags, float threshold, const ookd_filter *filter, doub
     probe.ctaps = pl.ctaps.empty() ? nullptr : pl.ctaps.data();
     probe.fir_out = (flags & OOKD_RX_KEEP_FIR) ? pl.taps.data() : nullptr;      // (no filter: no sparse form either)
     pl.form = front_form(probe, pl.exact);
-    // (a carrier context's fused form has its own number)
-    if (pl.carrier_context()) pl.form = pl.form == OOKD_FRONT_TUNED_FIR1 ? OOKD_FRONT_TUNED_MULTI : OOKD_FRONT_TUNED_GENERIC;
+    // (a carrier context's fused 1-stage form has its own number; OOKD_FRONT_TUNED_FIR2 runs once per carrier)
+    if (pl.carrier_context() && pl.form != OOKD_FRONT_TUNED_FIR2) {
+        pl.form = pl.form == OOKD_FRONT_TUNED_FIR1 ? OOKD_FRONT_TUNED_MULTI : OOKD_FRONT_TUNED_GENERIC;
+    }
     pl.tile_bits = front_tile_bits(probe);
     pl.sparse_capable = front_sparse_capable(probe);
     // a filter only the generic kernels serve is refused here, not by every run's launch

@@ -29,19 +29,8 @@
 namespace ookd {
 
 // ---------------------------------------------------------------------------
-// small helpers (the ones shared with fir_tuned.hip and survey_tuned.hip: front_dev.hpp)
+// small helpers (the ones shared with fir_tuned.hip and survey_tuned.hip, fetch_raw among them: front_dev.hpp)
 // ---------------------------------------------------------------------------
-
-// fetch_sample for int16 inputs, returned raw (packed I | Q << 16).
-__device__ __forceinline__ uint32_t fetch_raw(const FrontParams &p, const uint32_t *src, int64_t n) {
-    if (n < 0) {
-        const int64_t h = (int64_t)p.halo_len + n;
-        if (h < 0 || !p.halo) return 0u;
-        return reinterpret_cast<const uint32_t *>(p.halo)[h];
-    }
-    if ((uint64_t)n >= p.n_valid) return 0u;
-    return src[n];
-}
 
 // ---------------------------------------------------------------------------
 // front end, 1 stage / decimation 1 (fs32_fs4, the 255-tap config)
@@ -340,23 +329,7 @@ __global__ __launch_bounds__(64 * kFirWgWaves) void fir1_bits_kernel(const Front
 // at slot t*(P+1) -- one pad per block makes the lane stride odd, i.e.
 // conflict free for ds_read_b64.
 
-template <int D1_, int N1_, int D2_, int N2_, int R2_>
-struct Fir2Geom {
-    static constexpr int D1 = D1_, D2 = D2_, R2 = R2_;
-    static constexpr int T1 = 16 * N1_, T2 = 16 * N2_;         // padded tap counts
-    static constexpr int N1 = N1_, N2 = N2_;
-    static constexpr int F = 64 * R2;                           // final outputs per wave
-    static constexpr int L1need = D2 * (F - 1) + T2;            // stage-1 outputs stage 2 reads
-    static constexpr int R1 = (L1need + 63) / 64;
-    static constexpr int L1 = 64 * R1;                          // stage-1 outputs computed
-    static constexpr int L0 = D1 * (L1 - 1) + T1;               // input samples read
-    static constexpr int P1 = D1 * R1, P2 = D2 * R2;
-    static constexpr int kVecs = (L0 + 3 + 3) / 4;              // 16 B loads (the window may start mid-vector)
-    static constexpr int kVecRounds = (kVecs + 63) / 64;
-    static constexpr int slots0 = (L0 + L0 / P1 + 2 + 1) & ~1;  // level 0 stays RAW: 4 B per sample
-    static constexpr int slots1 = L1 + L1 / P2 + 2;             // level 1: float2
-    static constexpr int wave_bytes = ((slots0 * 4 + slots1 * 8) + 15) & ~15;
-};
+// (Fir2Geom, the geometry both this kernel and fir2_tuned_kernel are built on: front_dev.hpp)
 
 // One 16-tap chunk of a decimating stage: window position W (newest first)
 // feeds output r with tap kk = D*r - D*(R-1) + W when 0 <= kk < 16.
@@ -581,7 +554,7 @@ __global__ __launch_bounds__(64 * kFir2Waves) void fir2_bits_kernel(const FrontP
     if ((tid & 15u) == 0) words[(J0 >> 6) + (tid >> 4)] = (uint64_t)half | ((uint64_t)hi << 32);
 }
 
-typedef Fir2Geom<2, 1, 2, 2, 4> Fir2Dec4;      // fs128_fs16_dec4: (D 2, 16 taps), (D 2, 32 taps)
+// (Fir2Dec4, the one geometry it is instantiated for: front_dev.hpp)
 
 // ---------------------------------------------------------------------------
 // front end, generic: any number of stages / decimations, exact arithmetic
@@ -930,8 +903,11 @@ static bool use_fir2(const FrontParams &p) {
 //  number, on a widened copy)
 uint32_t front_form(const FrontParams &p, bool exact) {
     const bool s8 = p.sample_fmt != kFmtSc16;
-    // a tuned context (fir_tuned.hip): its two forms, both on SC16Q11 samples (8-bit captures are widened first)
-    if (p.tune && p.num_stages) return front_uses_tuned_fir1(p) && !exact ? OOKD_FRONT_TUNED_FIR1 : OOKD_FRONT_TUNED_GENERIC;
+    // a tuned context (fir_tuned.hip): its forms, all on SC16Q11 samples (8-bit captures are widened first)
+    if (p.tune && p.num_stages) {
+        if (front_uses_tuned_fir1(p) && !exact) return OOKD_FRONT_TUNED_FIR1;
+        return front_uses_tuned_fir2(p) && !exact ? OOKD_FRONT_TUNED_FIR2 : OOKD_FRONT_TUNED_GENERIC;
+    }
     if (p.num_stages == 0) return s8 ? OOKD_FRONT_NO_FILTER_8 : OOKD_FRONT_NO_FILTER;
     if (use_fir1(p)) {
         if (front_uses_mfma(p) && !exact) return s8 ? OOKD_FRONT_FIR1_MFMA_8 : OOKD_FRONT_FIR1_MFMA;
@@ -946,6 +922,7 @@ uint32_t front_form(const FrontParams &p, bool exact) {
 
 uint64_t front_wave_tiles(const FrontParams &p) {
     if (p.tune && p.num_stages) {
+        if (front_uses_tuned_fir2(p)) return (p.n_out + kTunedFir2Tile - 1) / kTunedFir2Tile;
         return front_uses_tuned_fir1(p) ? ((p.n_out + kFirTile - 1) / kFirTile) * (kFirTile / tuned_fir1_tile_bits(p)) : 0;
     }
     if (p.num_stages == 0) return ((p.n_out + kFirTile - 1) / kFirTile) * (kFirTile / kWaveTile);
@@ -958,7 +935,10 @@ uint64_t front_wave_tiles(const FrontParams &p) {
 }
 
 uint32_t front_tile_bits(const FrontParams &p) {
-    if (p.tune && p.num_stages) return front_uses_tuned_fir1(p) ? tuned_fir1_tile_bits(p) : 0;
+    if (p.tune && p.num_stages) {
+        if (front_uses_tuned_fir2(p)) return kTunedFir2Tile;
+        return front_uses_tuned_fir1(p) ? tuned_fir1_tile_bits(p) : 0;
+    }
     if (p.num_stages == 0) return kWaveTile;
     if (use_fir1(p)) return 64 * fir1_R(p);
     if (use_fir2(p)) return Fir2Dec4::F;
@@ -991,6 +971,7 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
         return hipErrorInvalidValue;        // no 8-bit kernel of this form: the caller widens first
     }
     if (form == OOKD_FRONT_TUNED_FIR1) return launch_front_tuned_fir1(p, num_captures, stream, t0, t1, tile_begin, tile_count);
+    if (form == OOKD_FRONT_TUNED_FIR2) return launch_front_tuned_fir2(p, num_captures, stream, t0, t1, tile_begin, tile_count);
     if (form == OOKD_FRONT_TUNED_GENERIC) {
         if (tile_begin != 0 || tile_count != ~0ull) return hipErrorInvalidValue;     // whole captures only
         if (t0 && hipEventRecord(t0, stream) != hipSuccess) return hipGetLastError();
@@ -1059,7 +1040,7 @@ hipError_t launch_front(const FrontParams &p, uint32_t num_captures, bool exact,
 bool front_sparse_capable(const FrontParams &p) {
     // (round 3: the two-stage kernels too -- their quiet tiles stored 36 bytes each, 150 MB of small stores per
     //  16 GiB capture beside the read stream: the backend default filter ran 15 % behind the 1-stage one for it)
-    if (p.tune && p.num_stages) return front_uses_tuned_fir1(p) && p.quiet_lsb > 0 && !p.fir_out;
+    if (p.tune && p.num_stages) return (front_uses_tuned_fir1(p) || front_uses_tuned_fir2(p)) && p.quiet_lsb > 0 && !p.fir_out;
     return (use_fir1(p) || use_fir2(p)) && p.quiet_lsb > 0 && !p.fir_out;
 }
 

@@ -88,6 +88,9 @@ struct FrontParams {
     // frequency-tuned front end (fir_tuned.hip): complex taps c[k] = h[k] e^{j 2 pi nu P_s k} on the raw samples
     uint32_t tune;              // 0: real taps (everything above); 1: tuned; 2: tuned, the contract's order for every
                                 // shape (OOKD_RX_EXACT_FIR): the generic tuned kernel
+    uint32_t tuned_fir2;        // OOKD_RX_TUNED_FIR2: a tuned 2 x decimate-by-2 filter runs fir2_tuned_kernel
+                                // (front_uses_tuned_fir2), not the generic tuned kernel.  (It sits in what was padding
+                                // in front of the pointer: no other field moves, no kernel's argument offsets change.)
     const float *ctaps;         // (re, im) pairs, stage s at ctaps + 2 * tap_off, zero padded to ntaps_pad pairs
     float quiet_a, quiet_b;     // tuned quiet test (quiet_lsb > 0): a window with component ranges up to `a` and
                                 // |min + max| up to `b` (raw LSB) is quiet when a * quiet_a + b * quiet_b < 1
@@ -191,6 +194,12 @@ uint32_t tuned_fir1_tile_bits(const FrontParams &p);
 hipError_t launch_front_tuned_fir1(const FrontParams &p, uint32_t num_captures, hipStream_t stream, hipEvent_t t0,
                                    hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count);
 hipError_t launch_front_tuned_generic(const FrontParams &p, uint32_t num_captures, hipStream_t stream);
+// 2 x decimate-by-2 (<= 16, <= 32 taps), origin a multiple of 4, asked for (FrontParams::tuned_fir2) and not forced
+// to the contract's order: fir2_tuned_kernel (OOKD_FRONT_TUNED_FIR2), tiles of kTunedFir2Tile final outputs
+constexpr uint32_t kTunedFir2Tile = 256;
+bool front_uses_tuned_fir2(const FrontParams &p);
+hipError_t launch_front_tuned_fir2(const FrontParams &p, uint32_t num_captures, hipStream_t stream, hipEvent_t t0,
+                                   hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count);
 // Several carriers in one pass over ONE capture (fir1_tuned_multi_kernel; the shape front_uses_tuned_fir1 takes, no
 // halo).  What depends on the carrier travels in a table beside FrontParams (whose p_star / p_lo / p_hi / quiet_a /
 // quiet_b are not read): carrier k's taps at p.ctaps + tap_off, its results where capture k's would be

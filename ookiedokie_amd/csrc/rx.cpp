@@ -819,13 +819,34 @@ int ookd_rx::run_pipelined(const void *d_iq) {
     return OOKD_OK;
 }
 
-// The front end of a carrier context: the fused kernel for all carriers (OOKD_FRONT_TUNED_MULTI), or the generic
-// tuned kernel once per carrier, each launch with that carrier's taps, threshold and result planes.
+// The front end of a carrier context: the fused kernel for all carriers (OOKD_FRONT_TUNED_MULTI), or the fused
+// two-stage kernel (OOKD_FRONT_TUNED_FIR2) or the generic tuned kernel once per carrier, each launch with that
+// carrier's taps, threshold (band, quiet weights) and result planes.
 hipError_t ookd_rx::launch_carriers(const FrontParams &fp, hipEvent_t t0, hipEvent_t t1, uint64_t tile_begin,
                                     uint64_t tile_count) {
     const uint32_t K = num_carriers();
     if (fp.n_out != 0 && front.plan.form == OOKD_FRONT_TUNED_MULTI) {
         return launch_front_tuned_multi(fp, front.d_carriers.p, K, stream, t0, t1, tile_begin, tile_count);
+    }
+    if (fp.n_out != 0 && front.plan.form == OOKD_FRONT_TUNED_FIR2) {
+        // carrier k is the tuned context's launch on capture plane k; the time stamps ride on the first and the last
+        for (uint32_t k = 0; k < K; ++k) {
+            const CarrierPlan &c = front.plan.carriers[k];
+            FrontParams pk = fp;
+            pk.ctaps = fp.ctaps + c.tap_off;
+            pk.p_star = c.p_star;
+            pk.p_lo = c.p_lo;
+            pk.p_hi = c.p_hi;
+            pk.quiet_a = c.quiet_a;
+            pk.quiet_b = c.quiet_b;
+            pk.bits = fp.bits + (size_t)k * run_words;
+            pk.tile_info = fp.tile_info + (size_t)k * fp.tiles_per_cap;
+            if (fp.fir_out) pk.fir_out = fp.fir_out + 2 * (size_t)k * run_n_out;
+            const hipError_t e = launch_front_tuned_fir2(pk, 1, stream, k == 0 ? t0 : nullptr, k + 1 == K ? t1 : nullptr,
+                                                         tile_begin, tile_count);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
     }
     if (tile_begin != 0 || tile_count != ~0ull) return hipErrorInvalidValue;    // the generic kernel runs whole captures
     if (t0 && hipEventRecord(t0, stream) != hipSuccess) return hipGetLastError();
