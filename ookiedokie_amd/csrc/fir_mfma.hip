@@ -645,12 +645,14 @@ void fir1_mfma_kernel(const FrontParams p) {
             uint32_t m32 = (m16 & 0xfu) | ((m16 & 0xf0u) << 4) | ((m16 & 0xf00u) << 8) | ((m16 & 0xf000u) << 12);
             m32 <<= 4u * hh;
             uint32_t w32 = m32 | (uint32_t)__shfl_xor((int)m32, 32);
+            uint32_t exist = 0xffffffffu;
             {
                 // outputs past the end of the (padded) capture do not exist
                 const uint64_t c0 = t0 + 32u * n;
                 if (c0 + 32u > p.n_out) {
                     const uint32_t keep = c0 >= p.n_out ? 0u : (uint32_t)(p.n_out - c0);
-                    w32 &= (1u << keep) - 1u;       // keep < 32 here
+                    exist = (1u << keep) - 1u;      // keep < 32 here
+                    w32 &= exist;
                 }
             }
             // level changes inside the tile (the tile's first bit against the tile before NOT included)
@@ -659,6 +661,9 @@ void fir1_mfma_kernel(const FrontParams p) {
                 uint32_t ch = w32 ^ (w32 << 1);
                 if (n != 0) ch ^= prev_top & 1u;
                 else ch &= ~1u;
+                // nor do changes at or beyond n_out: a capture that ends high does not fall where the zeroed bits begin
+                // (the lane that holds n_out and every lane behind it)
+                ch &= exist;
                 uint32_t cnt = hh == 0 ? (uint32_t)__popc(ch) : 0u;
 #pragma unroll
                 for (int d = 16; d >= 1; d >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, d);
@@ -1025,6 +1030,11 @@ void fir2_mfma_kernel(const FrontParams p) {
                 const uint32_t top_prev = (uint32_t)__shfl((int)(uint32_t)(w64 >> 63), (int)((wq ? wq - 1u : 0u) << 2));   // lane 4 (wq - 1)
                 uint64_t ch = w64 ^ ((w64 << 1) | (wq ? (uint64_t)(top_prev & 1u) : 0ull));
                 if (wq == 0) ch &= ~1ull;
+                // changes at or beyond n_out do not exist: a capture that ends high does not fall where the zeroed bits begin
+                if (M0 + 64u * (wq + 1u) > p.n_out) {
+                    const uint64_t base = M0 + 64u * wq;
+                    ch &= base >= p.n_out ? 0ull : (1ull << (p.n_out - base)) - 1ull;       // fewer than 64 bits here
+                }
                 uint32_t cnt = ((n & 3u) == 0 && g == 0) ? (uint32_t)__popcll(ch) : 0u;
 #pragma unroll
                 for (int d = 32; d >= 1; d >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, d);

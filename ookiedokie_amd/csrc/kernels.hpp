@@ -248,7 +248,7 @@ struct EdgeParams {
     uint64_t edge_capacity;
     uint32_t *overflow;         // set to 1 when total edges > capacity
     const uint32_t *tile_info;  // per wave tile counts from the tuned front-end kernels, or null
-    uint32_t tiles_per_block;   // wave tiles per 4096-bit block (4 or 16)
+    uint32_t tiles_per_block;   // wave tiles per 4096-bit block (4, 8 or 16)
     // chunked (pipelined) runs: this launch covers one chunk of a capture, positions are chunk-local
     uint32_t *total_acc;        // += the chunk's level changes, or null
     uint32_t has_prev;          // bits / tile_info continue in front of the chunk: the level before its first
