@@ -10,13 +10,18 @@
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
  * ookd_pulses <capture.sc16q11|.cs8|.cu8> <filter.json|none> [--threshold <amplitude>] [--tune <hz>] [--rate <hz>]
+ *             [--suggest-device <file.json>]
  *
  *   --threshold  slicer level, default 0.1 (ookd_scan's stderr names one per carrier)
  *   --tune       carrier offset in Hz (needs a filter), default 0
  *   --rate       sample rate of the capture, default 3000000; the table's microseconds and --tune depend on it
+ *   --suggest-device  the fourth question, which device: count the capture's pulse/gap symbols and the distances
+ *                between its sync symbols (ookd_rx_symbol_survey, on the GPU), print the device ookd_suggest_coding and
+ *                ookd_suggest_device make of them and write it as a device JSON -- or say why there is none
  *
  * stdout: one line with the edge count and the two open runs, then per level ("on", "off") one line per class:
- * runs, mean length in decimated samples and in microseconds, and the range of lengths its bins cover.
+ * runs, mean length in decimated samples and in microseconds, and the range of lengths its bins cover.  With
+ * --suggest-device one more line: the suggested device, or the reason for none.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,20 +35,71 @@ static int fail(const char *what)
     return EXIT_FAILURE;
 }
 
+static const char *reason_text(uint32_t reason)
+{
+    switch (reason) {
+    case OOKD_CODING_KINDS: return "fewer than three kinds of pulse/gap symbols";
+    case OOKD_CODING_NOT_DISTANCE: return "the two commonest symbols differ in their pulse: not distance coded";
+    case OOKD_CODING_AMBIGUOUS: return "the two data gaps lie too close together for +-15 % windows";
+    case OOKD_CODING_NO_SYNC: return "no third kind of symbol occurs at least twice: no sync";
+    case OOKD_CODING_NO_FRAMES: return "no distance between syncs that half of the frames of 3 to 510 symbols share";
+    case OOKD_CODING_TOO_LONG: return "more bits between two syncs than a message holds";
+    default: return "unknown";
+    }
+}
+
+/* symbols -> coding -> frames -> device; prints it and writes the JSON.  0 when the file was written. */
+static int suggest_device(ookd_rx *rx, const ookd_pulse_suggestion *sug, double out_rate, const char *path)
+{
+    static ookd_symbol_table table;
+    static ookd_symbol_roles roles;
+    static ookd_symbol_survey survey;
+    static char json[16384];
+    ookd_coding coding;
+    ookd_device_suggestion dev;
+    if (ookd_symbol_table_from_pulses(sug, &table) != 0) return fail("ookd_symbol_table_from_pulses");
+    if (ookd_rx_symbol_survey(rx, 0, &table, NULL, &survey) != 0) return fail("ookd_rx_symbol_survey");
+    if (ookd_suggest_coding(sug, &survey, &roles, &coding) != 0) return fail("ookd_suggest_coding");
+    if (coding.found && ookd_rx_symbol_survey(rx, 0, &table, &roles, &survey) != 0) return fail("ookd_rx_symbol_survey");
+    if (ookd_suggest_device(sug, &survey, &coding, out_rate, &dev) != 0) return fail("ookd_suggest_device");
+    if (!dev.found) {
+        printf("no device suggested: %s\n", reason_text(dev.reason));
+        return EXIT_FAILURE;
+    }
+    printf("device: %u bits; sync %llu us on, %llu us off; bit %llu us on, then %llu us (0) or %llu us (1); "
+           "%llu syncs, %llu frames of 3 to 510 symbols, %llu of them clean and %u symbols long\n", dev.num_bits,
+           (unsigned long long) dev.sync_on_us, (unsigned long long) dev.sync_off_us, (unsigned long long) dev.bit_on_us,
+           (unsigned long long) dev.zero_off_us, (unsigned long long) dev.one_off_us, (unsigned long long) dev.num_syncs,
+           (unsigned long long) dev.frames_counted, (unsigned long long) dev.frames_clean, dev.frame_symbols);
+    size_t n = ookd_device_suggestion_json(&dev, "suggested", json, sizeof(json));
+    if (n == 0 || n >= sizeof(json)) return fail("ookd_device_suggestion_json");
+    FILE *f = fopen(path, "w");
+    if (!f || fwrite(json, 1, n, f) != n) {
+        fprintf(stderr, "cannot write %s\n", path);
+        if (f) fclose(f);
+        return EXIT_FAILURE;
+    }
+    fclose(f);
+    printf("written to %s\n", path);
+    return EXIT_SUCCESS;
+}
+
 int main(int argc, char **argv)
 {
     double threshold = 0.1, tune_hz = 0.0, rate = 3000000.0;
+    const char *suggest_path = NULL;
     int bad = argc < 3;
     for (int i = 3; i < argc && !bad; i += 2) {
         if (i + 1 >= argc) bad = 1;
         else if (!strcmp(argv[i], "--threshold")) threshold = strtod(argv[i + 1], NULL);
         else if (!strcmp(argv[i], "--tune")) tune_hz = strtod(argv[i + 1], NULL);
         else if (!strcmp(argv[i], "--rate")) rate = strtod(argv[i + 1], NULL);
+        else if (!strcmp(argv[i], "--suggest-device")) suggest_path = argv[i + 1];
         else bad = 1;
     }
     if (bad || !(rate > 0.0) || !(threshold > 0.0)) {
         fprintf(stderr, "usage: %s <capture.sc16q11|.cs8|.cu8> <filter.json|none> [--threshold <amplitude>] "
-                        "[--tune <hz>] [--rate <hz>]\n", argv[0]);
+                        "[--tune <hz>] [--rate <hz>] [--suggest-device <file.json>]\n", argv[0]);
         return EXIT_FAILURE;
     }
     int status = EXIT_FAILURE;
@@ -107,7 +163,7 @@ int main(int argc, char **argv)
         if (sug.dropped_runs[level])
             printf("  %llu runs in further classes not listed\n", (unsigned long long) sug.dropped_runs[level]);
     }
-    status = EXIT_SUCCESS;
+    status = suggest_path ? suggest_device(rx, &sug, out_rate, suggest_path) : EXIT_SUCCESS;
 
 out:
     ookd_rx_destroy(rx);

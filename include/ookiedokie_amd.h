@@ -986,6 +986,179 @@ typedef struct ookd_pulse_suggestion {
 int ookd_suggest_pulses(const ookd_pulse_hist *h, double sample_rate, ookd_pulse_suggestion *out);
 
 /* ------------------------------------------------------------------------
+ * Symbol survey: which device does this capture want?  The timing classes above
+ * name the pulse and gap lengths; what is still missing for a device file is the
+ * coding: which (pulse, gap) pair is a sync, which a zero, which a one, and how
+ * many bits lie between two syncs.  One more pass over the edge list that a run
+ * leaves in HBM counts pulse/gap SYMBOLS and measures the distance between sync
+ * symbols; two host-only rules (ookd_suggest_coding, ookd_suggest_device) turn
+ * the counts into a device of the family both device files of the reference
+ * belong to: a sync pulse and a sync gap, then num_bits bits, each a fixed pulse
+ * followed by a short or a long gap, then a closing pulse.  The decoder runs the
+ * suggested device like any other.  A by-product of a finished run: nothing a
+ * run does changes, and a run nobody asks about launches and allocates nothing.
+ *
+ * Symbols, a contract.  Take capture (or carrier) c of the last run, its edge
+ * list e[0..E) and the closed runs of the pulse survey's contract (run i is "on"
+ * when i is even).  Symbol j, 0 <= j < S = (E - 1) / 2 (integer division; 0
+ * when E < 3), is the pair (on-run 2j, off-run 2j + 1); both runs are closed.
+ * Indices are relative to the capture's own list.
+ *
+ * Classes.  ookd_symbol_table holds per level (0 = off-runs, 1 = on-runs, as in
+ * ookd_pulse_suggestion) num_classes[level] <= 16 inclusive ranges
+ * lower[level][k] <= d <= upper[level][k], ascending and disjoint
+ * (lower[k] <= upper[k] < lower[k+1]).  A run length inside no range has class
+ * 16 ("none", OOKD_SYMBOL_NONE).  ookd_symbol_table_from_pulses copies the
+ * classes' lower / upper: a class that ends in bin 511 keeps upper = 2^35 - 1,
+ * so longer runs get class 16.  A table that is not ascending and disjoint, or
+ * has more than 16 classes on a level, is OOKD_ERR_ARG.
+ *
+ * Kinds.  kind(j) = (on class, off class) lies in [0,16]^2; kinds[on][off]
+ * counts the symbols of every kind.
+ *
+ * Roles and frames.  ookd_symbol_roles gives every kind a role, role[on][off],
+ * one byte: OOKD_ROLE_OTHER 0, _SYNC 1, _ZERO 2, _ONE 3 (a larger value is
+ * OOKD_ERR_ARG).  Let p_0 < ... < p_{m-1} be the symbols whose kind has role
+ * SYNC.  Then
+ *     num_syncs    = m;
+ *     head_symbols = p_0, or S when m = 0;
+ *     tail_symbols = S - p_{m-1}, or 0 when m = 0;
+ *     frame i, 0 <= i < m - 1, has distance D_i = p_{i+1} - p_i and is CLEAN
+ *     when every symbol p_i + 1 ... p_{i+1} - 2 has role ZERO or ONE: the symbol
+ *     just before the next sync is free, because its off-run is the pause between
+ *     two messages; an empty interior (D <= 2) is clean;
+ *     frames[clean][min(D_i, 511)] is incremented (OOKD_FRAME_BINS = 512).
+ * With roles == NULL only num_symbols and kinds are computed; the frame members
+ * are zero.  Everything is an exact integer function of the edge list, the table
+ * and the roles, the same whatever order the kernels' atomic adds land in.
+ *
+ * ookd_rx_symbol_survey computes this on the GPU for the ONE capture asked
+ * about, at every call (table and roles differ from call to call: nothing is
+ * cached), on the context's stream; its buffers are allocated by the first call
+ * in the life of the context.  It refuses what ookd_rx_pulse_hist refuses, with
+ * the same codes: OOKD_ERR_ARG for a NULL rx, table or out, capture >= the run's
+ * captures, no finished run, a pipelined run, a shard run; OOKD_ERR_CAPACITY for
+ * an overflowed edge list; and OOKD_ERR_ARG for a bad table or role.
+ * ---------------------------------------------------------------------- */
+#define OOKD_SYMBOL_MAX_CLASSES 16
+#define OOKD_SYMBOL_NONE 16             /* the class of a length inside no range  */
+#define OOKD_SYMBOL_KINDS 17            /* classes 0 .. 15 and "none", per level  */
+#define OOKD_FRAME_BINS 512
+enum { OOKD_ROLE_OTHER = 0, OOKD_ROLE_SYNC = 1, OOKD_ROLE_ZERO = 2, OOKD_ROLE_ONE = 3 };
+typedef struct ookd_symbol_table {
+    uint32_t num_classes[2];                            /* [level]: 0 = off, 1 = on */
+    uint64_t lower[2][OOKD_SYMBOL_MAX_CLASSES];
+    uint64_t upper[2][OOKD_SYMBOL_MAX_CLASSES];
+} ookd_symbol_table;
+typedef struct ookd_symbol_roles {
+    uint8_t role[OOKD_SYMBOL_KINDS][OOKD_SYMBOL_KINDS]; /* [on class][off class]   */
+    uint8_t reserved[7];
+} ookd_symbol_roles;
+typedef struct ookd_symbol_survey {
+    uint64_t num_symbols;                               /* S                        */
+    uint64_t kinds[OOKD_SYMBOL_KINDS][OOKD_SYMBOL_KINDS];   /* [on class][off class] */
+    uint64_t num_syncs, head_symbols, tail_symbols;
+    uint64_t frames[2][OOKD_FRAME_BINS];                /* [clean][min(D, 511)]     */
+} ookd_symbol_survey;
+/* 0, or OOKD_ERR_ARG for a NULL argument.  Pure host code. */
+int ookd_symbol_table_from_pulses(const ookd_pulse_suggestion *pulses, ookd_symbol_table *out);
+int ookd_rx_symbol_survey(ookd_rx *rx, uint32_t capture, const ookd_symbol_table *table,
+                          const ookd_symbol_roles *roles /* may be NULL */, ookd_symbol_survey *out);
+/* HIP-event time of the last ookd_rx_symbol_survey call: the zeroing of the
+ * result and its kernels.  0 when that call was refused or had nothing to
+ * launch, and after a new run until somebody asks about it. */
+float ookd_rx_symbol_kernel_ms(const ookd_rx *rx);
+
+/* The coding rule, pure host code.  From the timing classes and the kind counts:
+ *   1. Kinds with a class 16 never take a role.
+ *   2. The others with a count > 0 are ordered by count descending, ties to the
+ *      smaller (on class, off class).  Fewer than 3: found = 0, reason
+ *      OOKD_CODING_KINDS.
+ *   3. The first two are the data kinds.  They must share their on class,
+ *      otherwise OOKD_CODING_NOT_DISTANCE (pulse-width coding is outside this
+ *      family).  ZERO is the one with the shorter off class.  With t0 < t1 the
+ *      mean_us of the two off classes (give ookd_suggest_pulses the sample
+ *      rate), 1.15 t0 < 0.85 t1 must hold -- the state machine's +-15 % windows
+ *      must not meet --, otherwise OOKD_CODING_AMBIGUOUS.
+ *   4. SYNC is the first kind after those two in the same order whose count is
+ *      >= 2; if there is none: OOKD_CODING_NO_SYNC.
+ * roles receives the three roles (all OTHER when found = 0).  Which of the two
+ * gaps means 0 cannot be known from a capture: shorter = 0 is the convention of
+ * both reference devices. */
+enum {
+    OOKD_CODING_OK = 0,
+    OOKD_CODING_KINDS = 1,          /* fewer than three kinds of symbols         */
+    OOKD_CODING_NOT_DISTANCE = 2,   /* the two data kinds differ in their pulse  */
+    OOKD_CODING_AMBIGUOUS = 3,      /* the two gaps lie too close together       */
+    OOKD_CODING_NO_SYNC = 4,        /* no third kind that occurs at least twice  */
+    OOKD_CODING_NO_FRAMES = 5,      /* no frame length that half the frames have */
+    OOKD_CODING_TOO_LONG = 6        /* more bits than OOKD_MAX_PAYLOAD_BYTES hold */
+};
+typedef struct ookd_coding {
+    int found;
+    uint32_t reason;                /* OOKD_CODING_*                             */
+    uint32_t data_on_class, zero_off_class, one_off_class;
+    uint32_t sync_on_class, sync_off_class, reserved;
+    uint64_t zero_count, one_count, sync_count;
+    double t0_us, t1_us;            /* mean gap of a zero and of a one           */
+} ookd_coding;
+/* 0, or OOKD_ERR_ARG for a NULL argument.  Only survey->kinds is read. */
+int ookd_suggest_coding(const ookd_pulse_suggestion *pulses, const ookd_symbol_survey *survey,
+                        ookd_symbol_roles *roles, ookd_coding *out);
+
+/* The device rule, pure host code.  survey is one computed WITH the roles of
+ * ookd_suggest_coding; sample_rate is that of the decimated samples.
+ *   5. Among the distances 3 <= D < 511 -- a frame of 1 or 2 symbols holds no
+ *      bit, and bin 511 holds every longer distance: neither can be a message --
+ *      L = the distance with the most clean frames, ties to the smaller D.
+ *      frames[1][L] >= 1 and 2 frames[1][L] >= the number of all frames of those
+ *      distances, clean or not, must hold, otherwise OOKD_CODING_NO_FRAMES.
+ *      num_bits = L - 2 (the sync symbol and the closing pulse's symbol); more
+ *      than 8 OOKD_MAX_PAYLOAD_BYTES: OOKD_CODING_TOO_LONG.
+ *   6. Durations in microseconds are llround(class mean / sample_rate * 1e6).
+ *   7. The device has six states, in this order:
+ *      reset:      always -> idle.
+ *      idle:       pulse_start -> sync_pulse.
+ *      sync_pulse: duration = sync on, timeout = twice that; pulse_end ->
+ *                  sync_gap; timeout -> reset.
+ *      sync_gap:   duration = sync off, timeout = twice that; pulse_start ->
+ *                  bit_pulse; timeout -> reset.
+ *      bit_pulse:  duration = data on, timeout = twice that; msg_complete ->
+ *                  reset with output_data; pulse_end -> bit_gap; timeout -> reset.
+ *      bit_gap:    timeout = 2 t1; pulse_start with duration t0 -> bit_pulse,
+ *                  append_0; pulse_start with duration t1 -> bit_pulse, append_1;
+ *                  timeout -> reset.
+ * A coding with found = 0 is passed through: found = 0 with its reason.
+ * Limits: this family only; one device per capture; two levels; fields are not
+ * inferred; the zero / one polarity is a convention; a capture whose pauses fall
+ * into the sync gap's class (its closing symbols then count as syncs, and frames
+ * of 1 and of L - 1 symbols appear beside the true ones) is answered only while
+ * the modal-frame test of step 5 holds. */
+typedef struct ookd_device_suggestion {
+    int found;
+    uint32_t reason;                /* OOKD_CODING_*                             */
+    uint32_t num_bits, frame_symbols;       /* L - 2, L                          */
+    uint64_t sync_on_us, sync_off_us, bit_on_us, zero_off_us, one_off_us;
+    uint64_t frames_seen;           /* all frames, every distance, clean or not  */
+    uint64_t frames_counted;        /* those with 3 <= D < 511, clean or not     */
+    uint64_t frames_clean;          /* clean frames at distance L                */
+    uint64_t num_syncs;
+} ookd_device_suggestion;
+/* 0, or OOKD_ERR_ARG for a NULL argument or a sample_rate that is not > 0. */
+int ookd_suggest_device(const ookd_pulse_suggestion *pulses, const ookd_symbol_survey *survey,
+                        const ookd_coding *coding, double sample_rate, ookd_device_suggestion *out);
+/* The suggested device through ookd_device_create (state names reset, s1 .. s5);
+ * NULL for a suggestion with found = 0. */
+ookd_device *ookd_device_from_suggestion(const ookd_device_suggestion *s, uint32_t sample_rate);
+/* A device JSON that ookd_device_load accepts, with the states above, no ts_mode
+ * and hex fields over all bits: one field "Payload" up to 64 bits, otherwise
+ * "Payload0", "Payload1", ... of 64 bits each (a field holds 64 bits at most).
+ * snprintf convention: returns the number of characters the full text has and
+ * stores at most size - 1 of them plus a NUL; 0 for a NULL suggestion or name or
+ * a suggestion with found = 0. */
+size_t ookd_device_suggestion_json(const ookd_device_suggestion *s, const char *name, char *buf, size_t size);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

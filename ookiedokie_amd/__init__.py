@@ -20,6 +20,8 @@ here                              reference (OOKiedokie ``src/``)
                                   (``Receiver(tune=...)``) in the capture
 ``Receiver.pulse_hist`` /         nothing: measures the pulse and gap lengths
 ``suggest_pulses``                a device file's states name (devices/README.md)
+``Receiver.suggest_device`` /     nothing: writes that device file's state
+``Device.from_suggestion``        machine for a sync + distance-coded remote
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -86,6 +88,15 @@ CARRIER_MIN_SPACING = 32                # OOKD_CARRIER_MIN_SPACING
 PULSE_BINS = 512                        # OOKD_PULSE_BINS: pulse survey, sixteen bins per octave of run length
 PULSE_CLASS_GAP = 2                     # OOKD_PULSE_CLASS_GAP
 PULSE_MAX_CLASSES = 16                  # OOKD_PULSE_MAX_CLASSES
+SYMBOL_MAX_CLASSES = 16                 # OOKD_SYMBOL_MAX_CLASSES: symbol survey, ranges per level of a class table
+SYMBOL_NONE = 16                        # OOKD_SYMBOL_NONE: the class of a run length inside no range
+SYMBOL_KINDS = 17                       # OOKD_SYMBOL_KINDS: classes 0 .. 15 and "none", per level
+FRAME_BINS = 512                        # OOKD_FRAME_BINS: distances between sync symbols, clamped to 511
+ROLE_OTHER, ROLE_SYNC, ROLE_ZERO, ROLE_ONE = 0, 1, 2, 3         # OOKD_ROLE_*
+CODING_OK, CODING_KINDS, CODING_NOT_DISTANCE, CODING_AMBIGUOUS, CODING_NO_SYNC, CODING_NO_FRAMES, CODING_TOO_LONG = range(7)
+CODING_REASONS = ("ok", "fewer than three kinds of symbols", "the two data kinds differ in their pulse",
+                  "the two gaps lie too close together", "no third kind that occurs at least twice",
+                  "no frame length that half the frames have", "more bits than a message holds")
 DEFAULT_THRESHOLD = 0.1                 # ookiedokie_cfg.c:27
 DEFAULT_RATE = 3000000                  # ookiedokie_cfg.c:32
 DEFAULT_SAMPLES_PER_BUF = 8192          # ookiedokie_cfg.c:34
@@ -219,6 +230,35 @@ class PulseSuggestion(C.Structure):
                 ("dropped_runs", C.c_uint64 * 2), ("classes", (PulseClass * PULSE_MAX_CLASSES) * 2)]
 
 
+class SymbolTable(C.Structure):
+    _fields_ = [("num_classes", C.c_uint32 * 2), ("lower", (C.c_uint64 * SYMBOL_MAX_CLASSES) * 2),
+                ("upper", (C.c_uint64 * SYMBOL_MAX_CLASSES) * 2)]
+
+
+class SymbolRoles(C.Structure):
+    _fields_ = [("role", (C.c_uint8 * SYMBOL_KINDS) * SYMBOL_KINDS), ("reserved", C.c_uint8 * 7)]
+
+
+class SymbolSurvey(C.Structure):
+    _fields_ = [("num_symbols", C.c_uint64), ("kinds", (C.c_uint64 * SYMBOL_KINDS) * SYMBOL_KINDS),
+                ("num_syncs", C.c_uint64), ("head_symbols", C.c_uint64), ("tail_symbols", C.c_uint64),
+                ("frames", (C.c_uint64 * FRAME_BINS) * 2)]
+
+
+class Coding(C.Structure):
+    _fields_ = [("found", C.c_int), ("reason", C.c_uint32), ("data_on_class", C.c_uint32),
+                ("zero_off_class", C.c_uint32), ("one_off_class", C.c_uint32), ("sync_on_class", C.c_uint32),
+                ("sync_off_class", C.c_uint32), ("reserved", C.c_uint32), ("zero_count", C.c_uint64),
+                ("one_count", C.c_uint64), ("sync_count", C.c_uint64), ("t0_us", C.c_double), ("t1_us", C.c_double)]
+
+
+class DeviceSuggestion(C.Structure):
+    _fields_ = [("found", C.c_int), ("reason", C.c_uint32), ("num_bits", C.c_uint32), ("frame_symbols", C.c_uint32),
+                ("sync_on_us", C.c_uint64), ("sync_off_us", C.c_uint64), ("bit_on_us", C.c_uint64),
+                ("zero_off_us", C.c_uint64), ("one_off_us", C.c_uint64), ("frames_seen", C.c_uint64),
+                ("frames_counted", C.c_uint64), ("frames_clean", C.c_uint64), ("num_syncs", C.c_uint64)]
+
+
 class HostCfg(C.Structure):
     """struct ookiedokie_cfg (ookiedokie_cfg.h:50-91), field for field."""
     _fields_ = [
@@ -345,6 +385,16 @@ _PROTOTYPES = {
     "ookd_pulse_bin": (C.c_uint32, [C.c_uint64]),
     "ookd_pulse_bin_lower": (C.c_uint64, [C.c_uint32]),
     "ookd_suggest_pulses": (C.c_int, [C.POINTER(PulseHist), C.c_double, C.POINTER(PulseSuggestion)]),
+    "ookd_symbol_table_from_pulses": (C.c_int, [C.POINTER(PulseSuggestion), C.POINTER(SymbolTable)]),
+    "ookd_rx_symbol_survey": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SymbolTable), C.POINTER(SymbolRoles),
+                                        C.POINTER(SymbolSurvey)]),
+    "ookd_rx_symbol_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_suggest_coding": (C.c_int, [C.POINTER(PulseSuggestion), C.POINTER(SymbolSurvey), C.POINTER(SymbolRoles),
+                                      C.POINTER(Coding)]),
+    "ookd_suggest_device": (C.c_int, [C.POINTER(PulseSuggestion), C.POINTER(SymbolSurvey), C.POINTER(Coding), C.c_double,
+                                      C.POINTER(DeviceSuggestion)]),
+    "ookd_device_from_suggestion": (C.c_void_p, [C.POINTER(DeviceSuggestion), C.c_uint32]),
+    "ookd_device_suggestion_json": (C.c_size_t, [C.POINTER(DeviceSuggestion), C.c_char_p, C.c_char_p, C.c_size_t]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
     "sdr_hip_file_deinit": (None, [C.c_void_p]),
     "sdr_hip_file_rx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
@@ -481,6 +531,12 @@ class Device:
         t.trig_next = keep[5].ctypes.data_as(C.POINTER(C.c_uint32))
         t.trig_duration_us = keep[6].ctypes.data_as(C.POINTER(C.c_uint64))
         return cls(lib().ookd_device_create(C.byref(t)))
+
+    @classmethod
+    def from_suggestion(cls, suggestion, sample_rate: int) -> "Device":
+        """The device `suggest_device` (or `Receiver.suggest_device`) found, for the decoder: its six states through
+        ookd_device_create.  sample_rate is that of the decimated samples, as for `load`."""
+        return cls(lib().ookd_device_from_suggestion(C.byref(_device_suggestion_struct(suggestion)), int(sample_rate)))
 
     @property
     def num_bits(self) -> int:
@@ -957,6 +1013,42 @@ class Receiver:
         """HIP-event time of the pass behind `pulse_hist` for the last run; 0 while nobody has asked about it."""
         return float(lib().ookd_rx_pulse_kernel_ms(self._h))
 
+    # -- symbol survey ---------------------------------------------------------------
+    def symbol_survey(self, table, roles=None, capture: int = 0) -> dict:
+        """Pulse/gap symbols of one capture (or carrier) of the last run, counted on the GPU at every call
+        (ookd_rx_symbol_survey).  `table` is a class table (`symbol_table_from_pulses`, or a dict with `lower` and
+        `upper`: per level -- 0 = off, 1 = on -- a list of inclusive bounds); `roles` a uint8 array [17, 17] indexed
+        [on class, off class] (`suggest_coding` makes one), or None for the kind counts alone.  Returns num_symbols,
+        kinds (uint64 [17, 17]), num_syncs, head_symbols, tail_symbols and frames (uint64 [2, 512], [clean, distance])."""
+        t = _symbol_table_struct(table)
+        r = None
+        if roles is not None:
+            a = np.ascontiguousarray(roles, dtype=np.uint8)
+            if a.shape != (SYMBOL_KINDS, SYMBOL_KINDS):
+                raise ValueError("roles have shape (%d, %d)" % (SYMBOL_KINDS, SYMBOL_KINDS))
+            r = SymbolRoles()
+            C.memmove(r.role, a.ctypes.data, a.nbytes)
+        out = SymbolSurvey()
+        _check(lib().ookd_rx_symbol_survey(self._h, capture, C.byref(t), C.byref(r) if r is not None else None,
+                                           C.byref(out)))
+        return _symbol_survey_dict(out)
+
+    @property
+    def symbol_kernel_ms(self) -> float:
+        """HIP-event time of the last `symbol_survey` call's pass; 0 when it was refused or had nothing to launch."""
+        return float(lib().ookd_rx_symbol_kernel_ms(self._h))
+
+    def suggest_device(self, sample_rate: float, capture: int = 0) -> dict:
+        """The whole chain for one capture of the last run: pulse_hist -> suggest_pulses -> class table -> kind
+        counts -> suggest_coding -> frames -> `suggest_device`'s dict (found = 0 with a reason when the capture does
+        not look like a sync + distance-coded device).  sample_rate is that of the decimated samples."""
+        pulses = suggest_pulses(self.pulse_hist(capture), sample_rate)
+        table = symbol_table_from_pulses(pulses)
+        coding = suggest_coding(pulses, self.symbol_survey(table, None, capture))
+        survey = self.symbol_survey(table, coding["roles"], capture) if coding["found"] else \
+            dict(num_syncs=0, frames=np.zeros((2, FRAME_BINS), dtype=np.uint64))
+        return suggest_device(pulses, survey, coding, sample_rate)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_rx_destroy(self._h)
@@ -1010,6 +1102,117 @@ def suggest_pulses(hist, sample_rate: float) -> dict:
                 for i in range(out.num_classes[lv])] for lv in range(2)]
     return dict(found=int(out.found), dropped_runs=[int(out.dropped_runs[0]), int(out.dropped_runs[1])],
                 classes=classes)
+
+
+# --------------------------------------------------------------------------
+# symbol survey
+# --------------------------------------------------------------------------
+
+def _pulse_suggestion_struct(pulses) -> PulseSuggestion:
+    """`suggest_pulses`'s dict back into the C structure"""
+    s = PulseSuggestion()
+    s.found = int(pulses["found"])
+    for lv in range(2):
+        classes = pulses["classes"][lv]
+        if len(classes) > PULSE_MAX_CLASSES:
+            raise ValueError("at most %d classes per level" % PULSE_MAX_CLASSES)
+        s.num_classes[lv] = len(classes)
+        s.dropped_runs[lv] = int(pulses["dropped_runs"][lv])
+        for i, k in enumerate(classes):
+            for name, _ in PulseClass._fields_:
+                setattr(s.classes[lv][i], name, k[name])
+    return s
+
+
+def _symbol_table_struct(table) -> SymbolTable:
+    t = SymbolTable()
+    for lv in range(2):
+        lower, upper = list(table["lower"][lv]), list(table["upper"][lv])
+        if len(lower) != len(upper):
+            raise ValueError("a class table has as many lower as upper bounds")
+        t.num_classes[lv] = len(lower)              # (more than 16: the library refuses it)
+        for k in range(min(len(lower), SYMBOL_MAX_CLASSES)):
+            t.lower[lv][k] = int(lower[k])
+            t.upper[lv][k] = int(upper[k])
+    return t
+
+
+def _symbol_survey_dict(s: SymbolSurvey) -> dict:
+    return dict(num_symbols=int(s.num_symbols),
+                kinds=np.frombuffer(bytes(s.kinds), dtype=np.uint64).reshape(SYMBOL_KINDS, SYMBOL_KINDS).copy(),
+                num_syncs=int(s.num_syncs), head_symbols=int(s.head_symbols), tail_symbols=int(s.tail_symbols),
+                frames=np.frombuffer(bytes(s.frames), dtype=np.uint64).reshape(2, FRAME_BINS).copy())
+
+
+def _symbol_survey_struct(survey) -> SymbolSurvey:
+    s = SymbolSurvey()
+    for name in ("num_symbols", "num_syncs", "head_symbols", "tail_symbols"):
+        setattr(s, name, int(survey.get(name, 0)))
+    for name, shape in (("kinds", (SYMBOL_KINDS, SYMBOL_KINDS)), ("frames", (2, FRAME_BINS))):
+        if name in survey:
+            a = np.ascontiguousarray(survey[name], dtype=np.uint64)
+            if a.shape != shape:
+                raise ValueError("%s has shape %s" % (name, shape))
+            C.memmove(getattr(s, name), a.ctypes.data, a.nbytes)
+    return s
+
+
+def _coding_struct(coding) -> Coding:
+    c = Coding()
+    for name, _ in Coding._fields_:
+        if name != "reserved":
+            setattr(c, name, coding[name])
+    return c
+
+
+def _device_suggestion_struct(suggestion) -> DeviceSuggestion:
+    s = DeviceSuggestion()
+    for name, _ in DeviceSuggestion._fields_:
+        setattr(s, name, int(suggestion[name]))
+    return s
+
+
+def symbol_table_from_pulses(pulses) -> dict:
+    """ookd_symbol_table_from_pulses: the class table of `suggest_pulses`'s classes, {lower, upper}: per level (0 =
+    off, 1 = on) the inclusive bounds of every class, ascending."""
+    t = SymbolTable()
+    _check(lib().ookd_symbol_table_from_pulses(C.byref(_pulse_suggestion_struct(pulses)), C.byref(t)))
+    return dict(lower=[[int(t.lower[lv][k]) for k in range(t.num_classes[lv])] for lv in range(2)],
+                upper=[[int(t.upper[lv][k]) for k in range(t.num_classes[lv])] for lv in range(2)])
+
+
+def suggest_coding(pulses, survey) -> dict:
+    """ookd_suggest_coding: which kinds of symbols are the zero, the one and the sync, from `suggest_pulses`'s dict
+    and the kind counts of `Receiver.symbol_survey`.  Returns found, reason (CODING_*), the classes and counts of the
+    three kinds, t0_us / t1_us, and `roles` (uint8 [17, 17]) for the second `symbol_survey`.  Pure host code."""
+    roles, out = SymbolRoles(), Coding()
+    _check(lib().ookd_suggest_coding(C.byref(_pulse_suggestion_struct(pulses)), C.byref(_symbol_survey_struct(survey)),
+                                     C.byref(roles), C.byref(out)))
+    d = {name: getattr(out, name) for name, _ in Coding._fields_ if name != "reserved"}
+    d["roles"] = np.frombuffer(bytes(roles.role), dtype=np.uint8).reshape(SYMBOL_KINDS, SYMBOL_KINDS).copy()
+    return d
+
+
+def suggest_device(pulses, survey, coding, sample_rate: float) -> dict:
+    """ookd_suggest_device: the device of a coding and of the frames a `symbol_survey` with its roles counted: found,
+    reason (CODING_*), num_bits, frame_symbols, the five durations in microseconds (sync_on_us, sync_off_us, bit_on_us,
+    zero_off_us, one_off_us), frames_seen, frames_counted, frames_clean, num_syncs.  `Device.from_suggestion` and
+    `device_suggestion_json` take the dict.  Pure host code."""
+    out = DeviceSuggestion()
+    _check(lib().ookd_suggest_device(C.byref(_pulse_suggestion_struct(pulses)), C.byref(_symbol_survey_struct(survey)),
+                                     C.byref(_coding_struct(coding)), float(sample_rate), C.byref(out)))
+    return {name: int(getattr(out, name)) for name, _ in DeviceSuggestion._fields_}
+
+
+def device_suggestion_json(suggestion, name: str) -> str:
+    """ookd_device_suggestion_json: the suggestion as a device file `Device.load` accepts."""
+    s = _device_suggestion_struct(suggestion)
+    n = lib().ookd_device_suggestion_json(C.byref(s), name.encode(), None, 0)
+    if n == 0:
+        raise OokdError(-1, last_error())
+    buf = C.create_string_buffer(n + 1)
+    lib().ookd_device_suggestion_json(C.byref(s), name.encode(), buf, n + 1)
+    return buf.value.decode()
 
 
 # --------------------------------------------------------------------------

@@ -19,6 +19,7 @@
 #include "ingest.hpp"
 #include "kernels.hpp"
 #include "pulse_run.hpp"
+#include "symbol_run.hpp"
 
 using namespace ookd;
 
@@ -454,6 +455,7 @@ struct ookd_rx : RxHandles {
     bool run_shard = false, run_overflow = false;
     bool run_edges_valid = false;   // collect_results has read this run's edge count: the prefix and the list are its own
     PulseCtx *pulse = nullptr;
+    SymbolCtx *symbols = nullptr;   // the symbol survey's buffers (symbols.cpp), made by its first call
     uint32_t iter_next = 0;         // next FSM iteration number (parity continues)
     uint32_t final_parity = 0;
     ookd_rx_stats stats{};
@@ -466,6 +468,7 @@ struct ookd_rx : RxHandles {
         }
         (void)hipSetDevice(dev);        // for what is freed after this body: the members, then RxHandles
         pulse_ctx_free(pulse);
+        symbol_ctx_free(symbols);
     }
 
     void geometry(uint64_t n_valid, bool pad_to_buffer, uint64_t &n_in, uint64_t &n_out,
@@ -2071,6 +2074,9 @@ void ookd_rx_pulse_run(const ookd_rx *rx, PulseRun *out) {
 }
 
 PulseCtx **ookd_rx_pulse_ctx(ookd_rx *rx) { return &rx->pulse; }
+
+// symbol_run.hpp: where the context keeps the symbol survey's buffers
+SymbolCtx **ookd_rx_symbol_ctx(ookd_rx *rx) { return &rx->symbols; }
 
 extern "C" {
 
