@@ -14,79 +14,13 @@ static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "histogram word");
 
 namespace ookd {
 
-struct PulseCtx {
-    unsigned long long *d_result = nullptr;     // [captures][kPulseWords]
-    uint32_t capacity = 0;                      // captures d_result holds
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    uint64_t serial = 0;                        // the run `host` belongs to (PulseRun::serial), 0 = none
-    float kernel_ms = 0.0f;
-    std::vector<uint64_t> host;                 // its results
+struct PulseCtx : EdgePass {
+    std::vector<uint64_t> host;     // the results of run `serial`: [captures][kPulseWords]
 };
-
-void pulse_ctx_free(PulseCtx *p) {
-    if (!p) return;
-    if (p->d_result) (void)hipFree(p->d_result);
-    if (p->t0) (void)hipEventDestroy(p->t0);
-    if (p->t1) (void)hipEventDestroy(p->t1);
-    delete p;
-}
 
 }  // namespace ookd
 
 namespace {
-
-// one launch for all captures of the run; the results stay in c.host until the next run
-int compute(PulseCtx &c, const PulseRun &run) {
-    c.serial = 0;
-    c.kernel_ms = 0.0f;
-    c.host.assign((size_t)run.captures * kPulseWords, 0);
-    if (run.n_out == 0) {               // no buffer was processed: nothing was written for the kernel to read
-        c.serial = run.serial;
-        return OOKD_OK;
-    }
-    if (hipSetDevice(run.dev) != hipSuccess) {
-        set_error("ookd_rx_pulse_hist: hipSetDevice failed");
-        return OOKD_ERR_HIP;
-    }
-    if (c.capacity < run.captures) {
-        if (c.d_result) (void)hipFree(c.d_result);
-        c.d_result = nullptr;
-        c.capacity = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c.d_result), (size_t)run.captures * kPulseWords * 8) != hipSuccess) {
-            set_error("ookd_rx_pulse_hist: device allocation failed: %s", hipGetErrorString(hipGetLastError()));
-            return OOKD_ERR_NOMEM;
-        }
-        c.capacity = run.captures;
-    }
-    if (!c.t0 && (hipEventCreate(&c.t0) != hipSuccess || hipEventCreate(&c.t1) != hipSuccess)) {
-        set_error("ookd_rx_pulse_hist: hipEventCreate failed");
-        return OOKD_ERR_HIP;
-    }
-    PulseParams p{};
-    p.edges = run.d_edges;
-    p.edge_capacity = run.edge_capacity;
-    p.blk_offset = run.d_blk_offset;
-    p.blocks_per_cap = run.blocks_per_cap;
-    p.num_captures = run.captures;
-    p.result = c.d_result;
-    const size_t bytes = c.host.size() * 8;
-    bool ok = hipEventRecord(c.t0, run.stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(c.d_result, 0, bytes, run.stream) == hipSuccess;
-    ok = ok && launch_pulse_hist(p, run.num_edges, run.stream) == hipSuccess;
-    ok = ok && hipEventRecord(c.t1, run.stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(c.host.data(), c.d_result, bytes, hipMemcpyDeviceToHost, run.stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(run.stream) == hipSuccess;
-    if (!ok) {
-        set_error("ookd_rx_pulse_hist: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-        return OOKD_ERR_HIP;
-    }
-    if (hipEventElapsedTime(&c.kernel_ms, c.t0, c.t1) != hipSuccess) {
-        set_error("ookd_rx_pulse_hist: hipEventElapsedTime failed: %s", hipGetErrorString(hipGetLastError()));
-        return OOKD_ERR_HIP;
-    }
-    c.serial = run.serial;
-    return OOKD_OK;
-}
 
 struct ClassAcc {
     uint32_t first = 0, last = 0;
@@ -115,40 +49,26 @@ int ookd_rx_pulse_hist(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
         set_error("ookd_rx_pulse_hist: NULL argument");
         return OOKD_ERR_ARG;
     }
-    PulseRun run;
-    ookd_rx_pulse_run(rx, &run);
-    if (run.serial == 0 || run.in_flight || !run.valid) {
-        set_error("ookd_rx_pulse_hist: no finished run to look at%s",
-                  run.in_flight ? " (ookd_rx_wait first)" : run.serial ? " (the last run failed before its edges were counted)" : "");
-        return OOKD_ERR_ARG;
-    }
-    if (run.shard) {
-        set_error("ookd_rx_pulse_hist: the last run was a shard run: the level in front of a shard is not known here");
-        return OOKD_ERR_ARG;
-    }
-    if (run.pipelined) {
-        set_error("ookd_rx_pulse_hist: the last run was pipelined in chunks: its edge lists are chunk-local "
-                  "(OOKD_RX_NO_PIPELINE, or pipeline_chunk_samples = 0)");
-        return OOKD_ERR_ARG;
-    }
-    if (capture >= run.captures) {
-        set_error("ookd_rx_pulse_hist: capture %u of %u", capture, run.captures);
-        return OOKD_ERR_ARG;
-    }
-    if (run.overflow) {
-        set_error("ookd_rx_pulse_hist: the run's edge list overflowed (%llu level changes, capacity %llu): raise "
-                  "ookd_rx_config.edge_capacity", (unsigned long long)run.num_edges, (unsigned long long)run.edge_capacity);
-        return OOKD_ERR_CAPACITY;
-    }
-    PulseCtx *&ctx = *ookd_rx_pulse_ctx(rx);
-    if (!ctx) ctx = new (std::nothrow) PulseCtx();
+    EdgeRun run;
+    if (const int rc = edge_run_check("ookd_rx_pulse_hist", rx, capture, run); rc != OOKD_OK) return rc;
+    std::unique_ptr<EdgePass> &slot = ookd_rx_edge_pass(rx, kEdgePassPulse);
+    if (!slot) slot.reset(new (std::nothrow) PulseCtx());
+    PulseCtx *ctx = static_cast<PulseCtx *>(slot.get());
     if (!ctx) {
         set_error("ookd_rx_pulse_hist: out of memory");
         return OOKD_ERR_NOMEM;
     }
-    if (ctx->serial != run.serial) {
-        const int rc = compute(*ctx, run);
-        if (rc != OOKD_OK) return rc;
+    if (ctx->serial != run.serial) {    // one launch for all captures of the run; ctx->host keeps them until the next run
+        ctx->host.assign((size_t)run.captures * kPulseWords, 0);
+        if (run.n_out == 0) {           // no buffer was processed: nothing was written for the kernel to read
+            ctx->serial = run.serial;
+            ctx->kernel_ms = 0.0f;
+        } else {
+            const int rc = ctx->run("ookd_rx_pulse_hist", run, ctx->host.size(), ctx->host.data(), [&](unsigned long long *d) {
+                return launch_pulse_hist(PulseParams{edge_list_view(run), d}, run.num_edges, run.stream);
+            });
+            if (rc != OOKD_OK) return rc;
+        }
     }
     const uint64_t *r = ctx->host.data() + (size_t)capture * kPulseWords;
     memset(out, 0, sizeof *out);
@@ -168,13 +88,7 @@ int ookd_rx_pulse_hist(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
     return OOKD_OK;
 }
 
-float ookd_rx_pulse_kernel_ms(const ookd_rx *rx) {
-    if (!rx) return 0.0f;
-    PulseRun run;
-    ookd_rx_pulse_run(rx, &run);
-    const PulseCtx *ctx = *ookd_rx_pulse_ctx(const_cast<ookd_rx *>(rx));
-    return ctx && run.serial != 0 && ctx->serial == run.serial ? ctx->kernel_ms : 0.0f;
-}
+float ookd_rx_pulse_kernel_ms(const ookd_rx *rx) { return edge_pass_kernel_ms(rx, kEdgePassPulse); }
 
 int ookd_suggest_pulses(const ookd_pulse_hist *h, double sample_rate, ookd_pulse_suggestion *out) {
     clear_error();

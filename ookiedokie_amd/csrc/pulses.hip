@@ -11,61 +11,17 @@ namespace ookd {
 
 namespace {
 
-constexpr int kPulsePeelRounds = 6;     // distinct (level, bin) keys a wave looks at before its lanes add for themselves
-constexpr uint32_t kPulsePeelMin = 8;   // a key held by fewer lanes is not worth the reduction: its lanes add for themselves
-
-// sum over the wave (every lane calls it; lanes outside the group pass 0)
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, s);
-    return v;
-}
-
-// Every lane of the wave calls this together.  An OOK capture puts nearly all runs of a level into a handful of
-// bins, so most lanes of a wave hold the same key: the wave finds the lanes that share the first pending lane's
-// key, sums their lengths across lanes, and that lane alone adds (count, sum) to the workgroup's histogram -- one
-// LDS add per distinct key instead of up to 64 on one address.  A key held by few lanes (a rare timing; a capture
-// whose runs spread over many bins) gains nothing from the reduction: its lanes step aside to add for themselves
-// and the rounds go on with the next pending key, so a rare key in the first lane does not end them.
-__device__ __forceinline__ void wave_add_runs(unsigned long long *hist, bool valid, uint32_t key, uint64_t len) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint64_t todo = __ballot(valid), self = 0ull;
-#pragma unroll 1
-    for (int r = 0; r < kPulsePeelRounds && todo; ++r) {
-        const int leader = __ffsll((unsigned long long)todo) - 1;
-        const uint32_t lk = (uint32_t)__shfl((int)key, leader);
-        const bool mine = valid && key == lk;
-        const uint64_t same = __ballot(mine) & todo;
-        const uint32_t n = (uint32_t)__popcll(same);
-        todo &= ~same;
-        if (n < kPulsePeelMin) {                // (wave-uniform)
-            self |= same;
-            continue;
-        }
-        const uint64_t total = wave_sum_u64(mine ? len : 0ull);
-        if ((int)lane == leader) {
-            atomicAdd(&hist[2u * lk], (unsigned long long)n);
-            atomicAdd(&hist[2u * lk + 1u], (unsigned long long)total);
-        }
-    }
-    self |= todo;
-    if ((self >> lane) & 1ull) {
-        atomicAdd(&hist[2u * key], 1ull);
-        atomicAdd(&hist[2u * key + 1u], (unsigned long long)len);
-    }
-}
-
 // the capture that owns global edge index g: moves (c, lo, hi) forward until lo <= g < hi.  g only grows from call to
 // call, and g < off[num_captures * B], so the loop ends inside the table.
 struct CapCursor {
     uint32_t c;
     uint64_t lo, hi;
 };
-__device__ __forceinline__ void cursor_seek(CapCursor &k, const PulseParams &p, uint64_t g) {
-    while (g >= k.hi && k.c + 1u < p.num_captures) {
+__device__ __forceinline__ void cursor_seek(CapCursor &k, const EdgeListView &v, uint64_t g) {
+    while (g >= k.hi && k.c + 1u < v.num_captures) {
         ++k.c;
         k.lo = k.hi;
-        k.hi = p.blk_offset[(size_t)(k.c + 1u) * p.blocks_per_cap];
+        k.hi = v.blk_offset[(size_t)(k.c + 1u) * v.blocks_per_cap];
     }
 }
 
@@ -83,30 +39,26 @@ __global__ __launch_bounds__(kPulseThreads) void pulse_hist_kernel(PulseParams p
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t i = tid; i < 2u * kPulseKeys; i += kPulseThreads) hist[i] = 0ull;
 
-    // the list's end: the prefix's last word, and never beyond what the list can hold (the host refuses a run whose
-    // list overflowed; this keeps the loads inside the allocation whatever it was given)
-    uint64_t total = p.blk_offset[(size_t)p.num_captures * p.blocks_per_cap];
-    if (total > p.edge_capacity) total = p.edge_capacity;
+    const EdgeListView &list = p.list;
+    const uint64_t total = edge_list_total(list);
 
     // E, first and last edge of every capture: the open runs are the host's to derive
     if (blockIdx.x == 0) {
-        for (uint32_t c = tid; c < p.num_captures; c += kPulseThreads) {
-            uint64_t lo = p.blk_offset[(size_t)c * p.blocks_per_cap];
-            uint64_t hi = p.blk_offset[(size_t)(c + 1u) * p.blocks_per_cap];
-            if (hi > total) hi = total;
-            if (lo > hi) lo = hi;
+        for (uint32_t c = tid; c < list.num_captures; c += kPulseThreads) {
+            uint64_t lo, hi;
+            edge_list_range(list, c, total, lo, hi);
             unsigned long long *m = p.result + (size_t)c * kPulseWords + kPulseMetaWord;
             m[0] = hi - lo;
-            m[1] = hi > lo ? p.edges[lo] : 0ull;
-            m[2] = hi > lo ? p.edges[hi - 1u] : 0ull;
+            m[1] = hi > lo ? list.edges[lo] : 0ull;
+            m[2] = hi > lo ? list.edges[hi - 1u] : 0ull;
         }
     }
     __syncthreads();
 
     const uint64_t steps = (total + kPulseEdgesPerStep - 1u) / kPulseEdgesPerStep;
     CapCursor cur{0u, 0ull, 0ull};
-    cur.lo = p.blk_offset[0];
-    cur.hi = p.blk_offset[p.blocks_per_cap];
+    cur.lo = list.blk_offset[0];
+    cur.hi = list.blk_offset[list.blocks_per_cap];
     uint32_t flushed_c = 0u;            // the capture whose runs the LDS histogram holds
     bool dirty = false;
     for (uint64_t step = blockIdx.x; step < steps; step += gridDim.x) {
@@ -114,7 +66,7 @@ __global__ __launch_bounds__(kPulseThreads) void pulse_hist_kernel(PulseParams p
         // The histogram in LDS belongs to one capture at a time: flush it before a step that collects for another
         // capture.  A step with a boundary inside adds straight to the results and leaves the LDS histogram alone.
         CapCursor first = cur;
-        cursor_seek(first, p, base);
+        cursor_seek(first, list, base);
         const uint64_t last_g = (base + kPulseEdgesPerStep < total ? base + kPulseEdgesPerStep : total) - 1u;
         const bool one_capture = last_g < first.hi;     // uniform: every edge of the step lies in first.c
         if (dirty && one_capture && first.c != flushed_c) {
@@ -130,23 +82,23 @@ __global__ __launch_bounds__(kPulseThreads) void pulse_hist_kernel(PulseParams p
         const uint64_t g = base + 2ull * tid;           // this lane's two edges: g, g + 1
         uint64_t e0 = 0ull, e1 = 0ull;
         if (g + 1u < total) {
-            const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(p.edges + g);     // g is even: 16-byte aligned
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(list.edges + g);  // g is even: 16-byte aligned
             e0 = v.x;
             e1 = v.y;
         } else if (g < total) {
-            e0 = p.edges[g];
+            e0 = list.edges[g];
         }
         // the edge to the right of the pair: the next lane's first; the wave's last lane fetches it
         uint64_t e2 = (uint64_t)__shfl_down((unsigned long long)e0, 1);
-        if (lane == 63u) e2 = g + 2u < total ? p.edges[g + 2u] : 0ull;
+        if (lane == 63u) e2 = g + 2u < total ? list.edges[g + 2u] : 0ull;
 
         if (one_capture) {
             // run g -> g + 1 and run g + 1 -> g + 2, both inside first.c when their right edge is
             const bool va = g + 1u <= last_g, vb = g + 2u < first.hi;
             const uint32_t la = (uint32_t)((g - first.lo) & 1ull) ^ 1u;     // run i is "on" when i is even
             const uint64_t da = e1 - e0, db = e2 - e1;
-            wave_add_runs(hist, va, la * kPulseBins + pulse_bin_of(va ? da : 0ull), da);
-            wave_add_runs(hist, vb, (la ^ 1u) * kPulseBins + pulse_bin_of(vb ? db : 0ull), db);
+            wave_peel_add<true>(hist, va, la * kPulseBins + pulse_bin_of(va ? da : 0ull), da);
+            wave_peel_add<true>(hist, vb, (la ^ 1u) * kPulseBins + pulse_bin_of(vb ? db : 0ull), db);
             flushed_c = first.c;
             dirty = true;
         } else {
@@ -157,7 +109,7 @@ __global__ __launch_bounds__(kPulseThreads) void pulse_hist_kernel(PulseParams p
             for (int h = 0; h < 2; ++h) {
                 const uint64_t gl = g + (uint64_t)h;
                 if (gl < total) {
-                    cursor_seek(k, p, gl);
+                    cursor_seek(k, list, gl);
                     if (gl >= k.lo && gl + 1u < k.hi && gl + 1u < total) {
                         const uint64_t d = h == 0 ? e1 - e0 : e2 - e1;
                         const uint32_t lv = (uint32_t)((gl - k.lo) & 1ull) ^ 1u;

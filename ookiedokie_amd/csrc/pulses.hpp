@@ -1,6 +1,6 @@
 // pulses.hpp -- pulse survey: what pulses.hip (the kernel) and pulses.cpp (its C ABI and the host-only class rule)
 // share: the bin rule, the kernel's parameters and its launch.  The contract is in include/ookiedokie_amd.h; what
-// rx.cpp shares with pulses.cpp is in pulse_run.hpp.
+// rx.cpp shares with pulses.cpp is in edge_pass.hpp.
 #pragma once
 
 #include <cstdint>
@@ -8,7 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
-#include "pulse_run.hpp"
+#include "edge_list_dev.hpp"
 
 namespace ookd {
 
@@ -27,12 +27,8 @@ __host__ __device__ __forceinline__ uint32_t pulse_bin_of(uint64_t d) {
 }
 
 struct PulseParams {
-    const uint64_t *edges;          // the run's one edge list, capture-major
-    uint64_t edge_capacity;         // elements of it that exist: nothing at or beyond is read
-    const uint32_t *blk_offset;     // capture c's edges are [blk_offset[c * blocks_per_cap], blk_offset[(c + 1) * blocks_per_cap])
-    uint32_t blocks_per_cap;
-    uint32_t num_captures;
-    unsigned long long *result;     // [num_captures][kPulseWords], zero at launch
+    EdgeListView list;
+    unsigned long long *result;     // [list.num_captures][kPulseWords], zero at launch
 };
 constexpr uint32_t kPulseThreads = 256;
 constexpr uint32_t kPulseEdgesPerStep = 2u * kPulseThreads;     // a workgroup's step: two edges per lane

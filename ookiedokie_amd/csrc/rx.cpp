@@ -18,8 +18,7 @@
 #include "front_plan.hpp"
 #include "ingest.hpp"
 #include "kernels.hpp"
-#include "pulse_run.hpp"
-#include "symbol_run.hpp"
+#include "edge_pass.hpp"
 
 using namespace ookd;
 
@@ -450,12 +449,11 @@ struct ookd_rx : RxHandles {
     uint32_t run_caps = 0;
     uint64_t run_n_valid = 0, run_n_in = 0, run_n_out = 0, run_words = 0;
     uint32_t run_blocks = 0, run_segs_per_cap = 0;
-    // what the pulse survey (pulses.cpp) asks about the last run, and its buffers (made by its first call)
+    // what the edge-list readers (pulses.cpp, symbols.cpp) ask about the last run, and their passes (edge_pass.hpp)
     uint64_t run_serial = 0;        // runs started so far
     bool run_shard = false, run_overflow = false;
     bool run_edges_valid = false;   // collect_results has read this run's edge count: the prefix and the list are its own
-    PulseCtx *pulse = nullptr;
-    SymbolCtx *symbols = nullptr;   // the symbol survey's buffers (symbols.cpp), made by its first call
+    std::unique_ptr<EdgePass> edge_pass[kEdgePasses];   // each made by its reader's first call
     uint32_t iter_next = 0;         // next FSM iteration number (parity continues)
     uint32_t final_parity = 0;
     ookd_rx_stats stats{};
@@ -467,8 +465,6 @@ struct ookd_rx : RxHandles {
             if (gate->last == ev[1]) gate->last = nullptr;      // ev[1] is destroyed with RxHandles
         }
         (void)hipSetDevice(dev);        // for what is freed after this body: the members, then RxHandles
-        pulse_ctx_free(pulse);
-        symbol_ctx_free(symbols);
     }
 
     void geometry(uint64_t n_valid, bool pad_to_buffer, uint64_t &n_in, uint64_t &n_out,
@@ -2052,9 +2048,9 @@ uint64_t ookd_rx_bit_words(const ookd_rx *rx) { return rx ? rx->run_words : 0; }
 
 }  // extern "C"
 
-// pulse_run.hpp: the last run for the pulse survey, and where the context keeps the survey's buffers
-void ookd_rx_pulse_run(const ookd_rx *rx, PulseRun *out) {
-    PulseRun r;
+// edge_pass.hpp: the last run for the edge-list readers, and where the context keeps their passes
+void ookd_rx_edge_run(const ookd_rx *rx, EdgeRun *out) {
+    EdgeRun r;
     r.dev = rx->dev;
     r.stream = rx->stream;
     r.serial = rx->run_serial;
@@ -2073,10 +2069,7 @@ void ookd_rx_pulse_run(const ookd_rx *rx, PulseRun *out) {
     *out = r;
 }
 
-PulseCtx **ookd_rx_pulse_ctx(ookd_rx *rx) { return &rx->pulse; }
-
-// symbol_run.hpp: where the context keeps the symbol survey's buffers
-SymbolCtx **ookd_rx_symbol_ctx(ookd_rx *rx) { return &rx->symbols; }
+std::unique_ptr<EdgePass> &ookd_rx_edge_pass(ookd_rx *rx, EdgePassId id) { return rx->edge_pass[id]; }
 
 extern "C" {
 

@@ -7,7 +7,6 @@
 #include <string>
 #include <vector>
 
-#include "symbol_run.hpp"
 #include "symbols.hpp"
 
 using namespace ookd;
@@ -21,25 +20,15 @@ static_assert(sizeof(ookd_symbol_roles) == kSymKinds + 7u, "roles by key");
 
 namespace ookd {
 
-struct SymbolCtx {
-    unsigned long long *d_result = nullptr;     // [kSymWords]
-    SymAgg *d_agg = nullptr;                    // [tiles]
-    SymCarry *d_carry = nullptr;                // [tiles]
-    uint32_t tiles = 0;                         // what d_agg / d_carry hold: every tile the context's edge list can have
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    uint64_t serial = 0;                        // the run the last call was about (PulseRun::serial), 0 = none
-    float kernel_ms = 0.0f;
+struct SymbolCtx : EdgePass {
+    SymAgg *d_agg = nullptr;        // [tiles]
+    SymCarry *d_carry = nullptr;    // [tiles]
+    uint32_t tiles = 0;             // what d_agg / d_carry hold: every tile the context's edge list can have
+    ~SymbolCtx() override {
+        if (d_agg) (void)hipFree(d_agg);
+        if (d_carry) (void)hipFree(d_carry);
+    }
 };
-
-void symbol_ctx_free(SymbolCtx *p) {
-    if (!p) return;
-    if (p->d_result) (void)hipFree(p->d_result);
-    if (p->d_agg) (void)hipFree(p->d_agg);
-    if (p->d_carry) (void)hipFree(p->d_carry);
-    if (p->t0) (void)hipEventDestroy(p->t0);
-    if (p->t1) (void)hipEventDestroy(p->t1);
-    delete p;
-}
 
 }  // namespace ookd
 
@@ -56,42 +45,30 @@ bool table_ok(const ookd_symbol_table &t) {
     return true;
 }
 
-int compute(SymbolCtx &c, const PulseRun &run, uint32_t capture, const ookd_symbol_table &table,
+// the capture's pass: d_agg / d_carry on the first call, then the kernels' parameters and the timed sequence
+int compute(SymbolCtx &c, const EdgeRun &run, uint32_t capture, const ookd_symbol_table &table,
             const ookd_symbol_roles *roles, std::vector<uint64_t> &host) {
-    if (hipSetDevice(run.dev) != hipSuccess) {
-        set_error("ookd_rx_symbol_survey: hipSetDevice failed");
-        return OOKD_ERR_HIP;
-    }
-    const uint32_t tiles = std::max<uint32_t>(sym_tiles_of(run.edge_capacity), 1u);
-    if (!c.d_result) {
-        bool ok = hipMalloc(reinterpret_cast<void **>(&c.d_result), (size_t)kSymWords * 8) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void **>(&c.d_agg), (size_t)tiles * sizeof(SymAgg)) == hipSuccess;
+    if (!c.d_agg) {
+        if (hipSetDevice(run.dev) != hipSuccess) {
+            set_error("ookd_rx_symbol_survey: hipSetDevice failed");
+            return OOKD_ERR_HIP;
+        }
+        const uint32_t tiles = std::max<uint32_t>(sym_tiles_of(run.edge_capacity), 1u);
+        bool ok = hipMalloc(reinterpret_cast<void **>(&c.d_agg), (size_t)tiles * sizeof(SymAgg)) == hipSuccess;
         ok = ok && hipMalloc(reinterpret_cast<void **>(&c.d_carry), (size_t)tiles * sizeof(SymCarry)) == hipSuccess;
         if (!ok) {
             set_error("ookd_rx_symbol_survey: device allocation failed: %s", hipGetErrorString(hipGetLastError()));
-            if (c.d_result) (void)hipFree(c.d_result);
             if (c.d_agg) (void)hipFree(c.d_agg);
-            if (c.d_carry) (void)hipFree(c.d_carry);
-            c.d_result = nullptr;
             c.d_agg = nullptr;
             c.d_carry = nullptr;
             return OOKD_ERR_NOMEM;
         }
         c.tiles = tiles;
     }
-    if (!c.t0 && (hipEventCreate(&c.t0) != hipSuccess || hipEventCreate(&c.t1) != hipSuccess)) {
-        set_error("ookd_rx_symbol_survey: hipEventCreate failed");
-        return OOKD_ERR_HIP;
-    }
     SymParams p{};
-    p.edges = run.d_edges;
-    p.edge_capacity = run.edge_capacity;
-    p.blk_offset = run.d_blk_offset;
-    p.blocks_per_cap = run.blocks_per_cap;
-    p.num_captures = run.captures;
+    p.list = edge_list_view(run);
     p.capture = capture;
     p.num_tiles_cap = c.tiles;
-    p.result = c.d_result;
     p.agg = c.d_agg;
     p.carry = c.d_carry;
     for (uint32_t lv = 0; lv < 2; ++lv) {
@@ -102,23 +79,10 @@ int compute(SymbolCtx &c, const PulseRun &run, uint32_t capture, const ookd_symb
         }
     }
     if (roles) memcpy(p.role, roles->role, kSymKinds);
-    const size_t bytes = host.size() * 8;
-    bool ok = hipEventRecord(c.t0, run.stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(c.d_result, 0, bytes, run.stream) == hipSuccess;
-    ok = ok && launch_symbol_survey(p, roles != nullptr, run.num_edges, run.stream) == hipSuccess;
-    ok = ok && hipEventRecord(c.t1, run.stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(host.data(), c.d_result, bytes, hipMemcpyDeviceToHost, run.stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(run.stream) == hipSuccess;
-    if (!ok) {
-        set_error("ookd_rx_symbol_survey: HIP failure: %s", hipGetErrorString(hipGetLastError()));
-        return OOKD_ERR_HIP;
-    }
-    if (hipEventElapsedTime(&c.kernel_ms, c.t0, c.t1) != hipSuccess) {
-        set_error("ookd_rx_symbol_survey: hipEventElapsedTime failed: %s", hipGetErrorString(hipGetLastError()));
-        return OOKD_ERR_HIP;
-    }
-    c.serial = run.serial;
-    return OOKD_OK;
+    return c.run("ookd_rx_symbol_survey", run, host.size(), host.data(), [&](unsigned long long *d_result) {
+        p.result = d_result;
+        return launch_symbol_survey(p, roles != nullptr, run.num_edges, run.stream);
+    });
 }
 
 struct Kind {
@@ -209,8 +173,8 @@ int ookd_rx_symbol_survey(ookd_rx *rx, uint32_t capture, const ookd_symbol_table
         set_error("ookd_rx_symbol_survey: NULL argument");
         return OOKD_ERR_ARG;
     }
-    if (rx) {
-        if (SymbolCtx *c = *ookd_rx_symbol_ctx(rx)) {   // whatever happens below, the last call's time is no finished pass's
+    if (rx) {                   // whatever happens below, the last call's time is no finished pass's
+        if (EdgePass *c = ookd_rx_edge_pass(rx, kEdgePassSymbol).get()) {
             c->serial = 0;
             c->kernel_ms = 0.0f;
         }
@@ -233,35 +197,13 @@ int ookd_rx_symbol_survey(ookd_rx *rx, uint32_t capture, const ookd_symbol_table
         set_error("ookd_rx_symbol_survey: NULL argument");
         return OOKD_ERR_ARG;
     }
-    SymbolCtx *&ctx = *ookd_rx_symbol_ctx(rx);
-    PulseRun run;
-    ookd_rx_pulse_run(rx, &run);
-    if (run.serial == 0 || run.in_flight || !run.valid) {
-        set_error("ookd_rx_symbol_survey: no finished run to look at%s",
-                  run.in_flight ? " (ookd_rx_wait first)" : run.serial ? " (the last run failed before its edges were counted)" : "");
-        return OOKD_ERR_ARG;
-    }
-    if (run.shard) {
-        set_error("ookd_rx_symbol_survey: the last run was a shard run: the level in front of a shard is not known here");
-        return OOKD_ERR_ARG;
-    }
-    if (run.pipelined) {
-        set_error("ookd_rx_symbol_survey: the last run was pipelined in chunks: its edge lists are chunk-local "
-                  "(OOKD_RX_NO_PIPELINE, or pipeline_chunk_samples = 0)");
-        return OOKD_ERR_ARG;
-    }
-    if (capture >= run.captures) {
-        set_error("ookd_rx_symbol_survey: capture %u of %u", capture, run.captures);
-        return OOKD_ERR_ARG;
-    }
-    if (run.overflow) {
-        set_error("ookd_rx_symbol_survey: the run's edge list overflowed (%llu level changes, capacity %llu): raise "
-                  "ookd_rx_config.edge_capacity", (unsigned long long)run.num_edges, (unsigned long long)run.edge_capacity);
-        return OOKD_ERR_CAPACITY;
-    }
+    EdgeRun run;
+    if (const int rc = edge_run_check("ookd_rx_symbol_survey", rx, capture, run); rc != OOKD_OK) return rc;
     memset(out, 0, sizeof *out);
     if (run.n_out == 0) return OOKD_OK;         // no buffer was processed: nothing was written for the kernels to read
-    if (!ctx) ctx = new (std::nothrow) SymbolCtx();
+    std::unique_ptr<EdgePass> &slot = ookd_rx_edge_pass(rx, kEdgePassSymbol);
+    if (!slot) slot.reset(new (std::nothrow) SymbolCtx());
+    SymbolCtx *ctx = static_cast<SymbolCtx *>(slot.get());
     if (!ctx) {
         set_error("ookd_rx_symbol_survey: out of memory");
         return OOKD_ERR_NOMEM;
@@ -280,13 +222,7 @@ int ookd_rx_symbol_survey(ookd_rx *rx, uint32_t capture, const ookd_symbol_table
     return OOKD_OK;
 }
 
-float ookd_rx_symbol_kernel_ms(const ookd_rx *rx) {
-    if (!rx) return 0.0f;
-    PulseRun run;
-    ookd_rx_pulse_run(rx, &run);
-    const SymbolCtx *ctx = *ookd_rx_symbol_ctx(const_cast<ookd_rx *>(rx));
-    return ctx && run.serial != 0 && ctx->serial == run.serial ? ctx->kernel_ms : 0.0f;
-}
+float ookd_rx_symbol_kernel_ms(const ookd_rx *rx) { return edge_pass_kernel_ms(rx, kEdgePassSymbol); }
 
 int ookd_suggest_coding(const ookd_pulse_suggestion *pulses, const ookd_symbol_survey *survey, ookd_symbol_roles *roles,
                         ookd_coding *out) {

@@ -15,8 +15,6 @@ namespace ookd {
 
 namespace {
 
-constexpr int kSymPeelRounds = 6;       // distinct kinds a wave looks at before its lanes add for themselves
-constexpr uint32_t kSymPeelMin = 8;     // a kind held by fewer lanes is not worth the ballot: its lanes add for themselves
 constexpr uint32_t kRoleAbsent = 4;     // a symbol at or beyond S (in LDS only)
 
 // a tile's edges in LDS: slot i holds edge 2 base - 2 + i of the capture, i < kSymTileEdges -- two edges in front of
@@ -32,15 +30,10 @@ struct CapRange {
     uint32_t tiles;
 };
 
-// the capture's range: the prefix's words, never beyond what the list can hold (the host refuses a run whose list
-// overflowed; this keeps the loads inside the allocation whatever it was given)
+// the capture's range, inside the list (edge_list_dev.hpp), and what it holds in symbols and tiles
 __device__ __forceinline__ CapRange cap_range(const SymParams &p) {
-    uint64_t total = p.blk_offset[(size_t)p.num_captures * p.blocks_per_cap];
-    if (total > p.edge_capacity) total = p.edge_capacity;
-    uint64_t lo = p.blk_offset[(size_t)p.capture * p.blocks_per_cap];
-    uint64_t hi = p.blk_offset[(size_t)(p.capture + 1u) * p.blocks_per_cap];
-    if (hi > total) hi = total;
-    if (lo > hi) lo = hi;
+    uint64_t lo, hi;
+    edge_list_range(p.list, p.capture, edge_list_total(p.list), lo, hi);
     const uint64_t E = hi - lo;
     CapRange r;
     r.lo = lo;
@@ -73,7 +66,7 @@ __device__ __forceinline__ void stage_edges(SymLds &s, const SymParams &p, const
     for (uint32_t i = threadIdx.x; i < kSymTileEdges; i += kSymThreads) {
         const int64_t el = (int64_t)(2u * base) + (int64_t)i - 2;
         uint64_t v = 0ull;
-        if (el >= 0 && el <= last_edge) v = p.edges[r.lo + (uint64_t)el];
+        if (el >= 0 && el <= last_edge) v = p.list.edges[r.lo + (uint64_t)el];
         s.edge[edge_slot(i)] = v;
     }
 }
@@ -92,30 +85,6 @@ __device__ __forceinline__ uint32_t kind_of(const SymLds &s, const SymParams &p,
     const uint32_t on = class_of(s.lower[1], s.upper[1], p.num_classes[1], e1 - e0);
     const uint32_t off = class_of(s.lower[0], s.upper[0], p.num_classes[0], e2 - e1);
     return on * kSymSide + off;
-}
-
-// Every lane of the wave calls this together.  Two or three kinds hold nearly every symbol of a capture, so most
-// lanes of a wave hold the same key: the wave counts the lanes that share the first pending lane's key and that lane
-// alone adds the count -- one LDS add per distinct key instead of up to 64 on one address.  A key held by few lanes
-// gains nothing from it: its lanes step aside to add for themselves and the rounds go on with the next pending key.
-__device__ __forceinline__ void wave_add_kinds(unsigned long long *hist, bool valid, uint32_t key) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint64_t todo = __ballot(valid), self = 0ull;
-#pragma unroll 1
-    for (int r = 0; r < kSymPeelRounds && todo; ++r) {
-        const int leader = __ffsll((unsigned long long)todo) - 1;
-        const uint32_t lk = (uint32_t)__shfl((int)key, leader);
-        const uint64_t same = __ballot(valid && key == lk) & todo;
-        const uint32_t n = (uint32_t)__popcll(same);
-        todo &= ~same;
-        if (n < kSymPeelMin) {                  // (wave-uniform)
-            self |= same;
-            continue;
-        }
-        if ((int)lane == leader) atomicAdd(&hist[lk], (unsigned long long)n);
-    }
-    self |= todo;
-    if ((self >> lane) & 1ull) atomicAdd(&hist[key], 1ull);
 }
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
@@ -212,7 +181,7 @@ __global__ __launch_bounds__(kSymThreads) void symbol_kinds_kernel(SymParams p) 
             const uint64_t j = base + sl;
             const bool valid = j < r.S;
             const uint32_t key = valid ? kind_of(s, p, (int)sl) : 0u;
-            wave_add_kinds(hist, valid, key);
+            wave_peel_add<false>(hist, valid, key, 0ull);
             if (kRoles) {
                 role[q] = valid ? (uint32_t)s.role_of_key[key] : kRoleAbsent;
                 if (role[q] == kRoleSync) {

@@ -1,6 +1,6 @@
 // symbols.hpp -- symbol survey: what symbols.hip (the kernels) and symbols.cpp (their C ABI and the host-only coding
 // and device rules) share: the result's layout in device memory, the kernels' parameters and their launch.  The
-// contract is in include/ookiedokie_amd.h; what rx.cpp shares with symbols.cpp is in pulse_run.hpp.
+// contract is in include/ookiedokie_amd.h; what rx.cpp shares with symbols.cpp is in edge_pass.hpp.
 #pragma once
 
 #include <cstdint>
@@ -8,7 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
-#include "pulse_run.hpp"
+#include "edge_list_dev.hpp"
 
 namespace ookd {
 
@@ -44,11 +44,7 @@ struct SymCarry {
 };
 
 struct SymParams {
-    const uint64_t *edges;          // the run's one edge list, capture-major
-    uint64_t edge_capacity;         // elements of it that exist: nothing at or beyond is read
-    const uint32_t *blk_offset;     // capture c's edges are [blk_offset[c * blocks_per_cap], blk_offset[(c + 1) * blocks_per_cap])
-    uint32_t blocks_per_cap;
-    uint32_t num_captures;
+    EdgeListView list;
     uint32_t capture;               // the one asked about
     uint32_t num_tiles_cap;         // tiles agg / carry hold: no tile at or beyond is written
     unsigned long long *result;     // [kSymWords], zero at launch

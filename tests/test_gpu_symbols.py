@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import golden_path
-from tests.pulse_contract import RATE, SPB, THR, golden_iq
+from tests.pulse_contract import RATE, SPB, THR, assert_same_hist, golden_iq, hist_of
 from tests.symbol_contract import (NO_FRAMES, OTHER, ONE, SIDE, SYNC, ZERO, assert_same_survey, frames_dict, py_chain,
                                    survey_of)
 from tests.tuned_contract import golden_capture, moved
@@ -293,6 +293,45 @@ def test_one_context_dense_sparse_empty(ok):
     got = rx.symbol_survey(TABLE, ROLES)
     assert_same_survey(got, survey_of([], TABLE, ROLES))
     assert rx.symbol_kernel_ms == 0.0
+    rx.close()
+
+
+def test_both_passes_on_one_context(ok):
+    """the pulse and the symbol pass share a base on the host: a 1-capture run, then a 3-capture run (the pulse result
+    buffer grows) on one context, each asked pulse_hist, symbol_survey, pulse_hist -- a symbol pass must not disturb
+    the pulse cache or its time, nor a refused one; the context is closed with both passes alive"""
+    import torch
+    rng = np.random.default_rng(12)
+    n = 2 * SPB
+    host = np.zeros((3, 2 * n), dtype=np.int16)
+    host[0] = lay([Y] + data(rng, 30) + [X, Y] + data(rng, TILE + 40) + [Y, P], lead=0, ending="high", n=n)
+    host[1, :2 * SPB] = lay(data(rng, 5) + [Y, Z, O, Y, N], lead=700)
+    host[2] = lay([Y if k % 36 == 0 else p for k, p in enumerate(data(rng, 600))], lead=9, n=n)
+    dev_t = torch.from_numpy(host).cuda()
+    rx = ok.Receiver(None, None, max_samples=n, max_captures=3, threshold=THR, edge_capacity=3 * n)
+    for caps, samples in ((1, SPB), (3, n)):
+        rx.rx_device(dev_t[1].data_ptr() if caps == 1 else dev_t.data_ptr(), samples, num_captures=caps)
+        assert rx.pulse_kernel_ms == 0.0 and rx.symbol_kernel_ms == 0.0, caps   # nobody has asked about this run yet
+        n_out = rx.stats()["decimated_samples"]
+        edges = [rx.edges(c) for c in range(caps)]
+        assert all(e.size >= 3 for e in edges)
+        first = [rx.pulse_hist(c) for c in range(caps)]
+        ms = rx.pulse_kernel_ms
+        assert ms > 0.0 and rx.symbol_kernel_ms == 0.0, caps
+        for c in range(caps):
+            assert_same_hist(first[c], hist_of(edges[c], n_out), "run of %d, capture %d" % (caps, c))
+            got = rx.symbol_survey(TABLE, ROLES, c)
+            assert rx.symbol_kernel_ms > 0.0, (caps, c)
+            assert_same_survey(got, survey_of(edges[c], TABLE, ROLES), "run of %d, capture %d" % (caps, c))
+        for c in range(caps):
+            assert_same_hist(rx.pulse_hist(c), first[c], "run of %d, capture %d again" % (caps, c))
+        assert rx.pulse_kernel_ms == ms, caps                   # answered from host memory: nothing was launched
+    with pytest.raises(ok.OokdError) as e:
+        rx.symbol_survey(TABLE, ROLES, 3)
+    assert e.value.code == -1 and "capture 3 of 3" in str(e.value)
+    assert rx.symbol_kernel_ms == 0.0 and rx.pulse_kernel_ms == ms
+    assert_same_survey(rx.symbol_survey(TABLE, None, 2), survey_of(edges[2], TABLE), "the last pass")
+    assert rx.symbol_kernel_ms > 0.0
     rx.close()
 
 
