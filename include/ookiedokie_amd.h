@@ -576,7 +576,15 @@ int ookd_rx_get_fir(const ookd_rx *rx, uint32_t capture, ookd_complexf *out,
  *         capture.  In a batched run the list is capture-major, EXCEPT when the
  *         scan form refused some captures and those were redone by the round
  *         form (stats.fsm_path 3): then the refused captures' errors follow
- *         those of all the others.  *num is always the total. */
+ *         those of all the others.  *num is always the total, and every one of
+ *         them has its position: the first min(*num, capacity) entries of
+ *         `samples` are written, none is ever missing in between.  The lists
+ *         are sized at context creation by what the reference can report --
+ *         one error per buffer of samples_per_buffer, since the rest of that
+ *         buffer is dropped -- for max_samples and max_captures.  Only a
+ *         context whose bound exceeds 2^25 positions (a tiny
+ *         samples_per_buffer with a huge max_samples) holds fewer; a run of it
+ *         with more errors than it holds fails with OOKD_ERR_CAPACITY. */
 int ookd_rx_get_errors(const ookd_rx *rx, uint64_t *samples, uint64_t capacity,
                        uint64_t *num);
 

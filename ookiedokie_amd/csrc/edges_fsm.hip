@@ -982,7 +982,13 @@ __global__ __launch_bounds__(64) void fsm_round_kernel(const FsmParams p, uint32
             nmsg++;
         } else if (r == kResError) {
             const uint64_t apos = seg_start + at;
-            if (nerr < p.err_slots && lane == 0) errs[nerr] = apos;
+            // (err_slots is the most a segment can report -- one per buffer -- unless the context capped it: then the
+            //  run fails with the capacity error rather than hand out a list with holes)
+            if (nerr < p.err_slots) {
+                if (lane == 0) errs[nerr] = apos;
+            } else {
+                flags |= 4u;
+            }
             nerr++;
             // device.c:646: the rest of this buffer is never fed in
             const uint64_t in_idx = (uint64_t)p.total_decim * (apos + 1) - 1;

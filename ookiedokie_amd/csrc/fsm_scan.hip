@@ -3341,6 +3341,9 @@ __global__ __launch_bounds__(256) void fin_msg_kernel(ScanParams sp, PublishPara
             if (h_msgs && m < pp.first_msgs) h_msgs[m] = mm;
         } else {
             const uint32_t cap = (uint32_t)(m - nmsg);
+            // a capture the scan refused (batched run) has no tail leaf: fin_write left its record as it was -- from
+            // an earlier run, or never written -- and its epoch start is no index into this run's pool
+            if (sp.cap_fallback && sp.f.num_captures > 1 && sp.cap_fallback[cap]) continue;
             SegState so = sp.final_state[cap];
             uint64_t e0;
             cap_edges(sp.f, cap, e0);

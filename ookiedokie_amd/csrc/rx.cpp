@@ -37,6 +37,8 @@ namespace {
 constexpr uint32_t kIterBatch = 4;      // FSM fix-point rounds queued per host sync
 
 constexpr uint64_t kHostMsgFirst = 2048;    // messages copied with the header
+constexpr uint64_t kErrListMax = 1ull << 25;    // entries (256 MiB) an error list is allowed: it is sized by the buffers of
+                                                // the largest run, this only stops a tiny samples_per_buffer on a huge context
 
 struct ResultHeader {
     uint32_t changed[kIterBatch];
@@ -591,6 +593,7 @@ struct ookd_rx : RxHandles {
     int dump_scan_debug();
     int fsm_to_fixpoint(const FsmStateDev *first, bool fresh, bool force_first, const FsmParams *view = nullptr);
     int redo_refused_captures();
+    int segment_errors_overflow() const;
     int fetch_results();
     int enqueue_publish();
     PublishParams publish_params() const;
@@ -998,6 +1001,14 @@ int ookd_rx::fsm_to_fixpoint(const FsmStateDev *first, bool fresh, bool force_fi
 // results for all the others stand; each refused capture is redone alone in the round form and
 // its messages / errors are merged in, in capture order.  (Round 1 sent the whole call -- every
 // capture of the batch -- through the rounds.)
+// The round form ran out of error slots in a segment (header flag 4): only where setup_run_buffers had to cap them
+int ookd_rx::segment_errors_overflow() const {
+    set_error("a state machine segment reported more than %u errors (the context's error lists are capped at %llu "
+              "positions: raise ookd_rx_config.samples_per_buffer or lower segment_buffers)", err_slots,
+              (unsigned long long)kErrListMax);
+    return OOKD_ERR_CAPACITY;
+}
+
 int ookd_rx::redo_refused_captures() {
     std::vector<uint32_t> flags(run_caps);
     HIPCHK(hipMemcpy(flags.data(), d_cap_fallback.p, run_caps * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1026,6 +1037,10 @@ int ookd_rx::redo_refused_captures() {
         int rc = fsm_to_fixpoint(nullptr, true, false, &one);
         if (rc != OOKD_OK) return rc;
         rounds += stats.fsm_iterations;
+        // (the gather is queued behind the last round, unwaited for; the copies below run on the null stream, which
+        //  this non-blocking stream does not order itself against: without the wait they could read the totals and the
+        //  list before the gather wrote them, and the capture came back with no messages)
+        HIPCHK(hipStreamSynchronize(stream));
         ResultHeader hdr;
         HIPCHK(hipMemcpy(&hdr, d_hdr.p, sizeof(hdr), hipMemcpyDeviceToHost));
         if (hdr.flags & 1u) {
@@ -1033,6 +1048,7 @@ int ookd_rx::redo_refused_captures() {
                       "(raise ookd_rx_config.message_slots)", msg_slots);
             return OOKD_ERR_CAPACITY;
         }
+        if (hdr.flags & 4u) return segment_errors_overflow();
         const uint64_t m = std::min<uint64_t>(hdr.totals[0], msg_capacity);
         const size_t at = merged.size();
         merged.resize(at + m);
@@ -1386,6 +1402,14 @@ int ookd_rx::collect_results() {
         num_msgs = total;
         stats.num_messages = total;
         stats.num_errors = h_hdr->totals[1];
+        // every reported error has its position, or the run fails: ookd_rx_get_errors never hands out a list with holes
+        if (scan_used && stats.num_errors > d_scan_errs.n) {
+            set_error("error list overflow: %llu errors, the list holds %llu (one per buffer of max_samples, at most %llu: "
+                      "raise ookd_rx_config.samples_per_buffer)", (unsigned long long)stats.num_errors,
+                      (unsigned long long)d_scan_errs.n, (unsigned long long)kErrListMax);
+            return OOKD_ERR_CAPACITY;
+        }
+        if (!scan_used && (h_hdr->flags & 4u)) return segment_errors_overflow();
         if (redo_some) {
             const int rc = redo_refused_captures();
             if (rc != OOKD_OK) return rc;
@@ -1460,11 +1484,21 @@ bool setup_run_buffers(ookd_rx &rx, const ookd_rx_config &cfg) {
     }
     rx.seg_len = std::min<uint64_t>(rx.seg_len, 1ull << 30);   // 32-bit offsets inside a segment
     rx.msg_slots = cfg.message_slots ? cfg.message_slots : 32;
-    rx.err_slots = 32;
     uint32_t blocks = 0, segs = 0;
     rx.geometry(rx.max_samples, true, rx.max_n_in, rx.max_n_out, rx.max_words, blocks, segs);
     rx.max_blocks = blocks;
     rx.max_segs_per_cap = std::max<uint32_t>(segs, 1);
+    {
+        // Error positions of a segment of the round form.  The reference reports at most one error per buffer (the
+        // rest of it is dropped, device.c:646), and fsm_cuts_kernel moves each end of a segment by up to seg_len / 2:
+        // a segment spans at most 2 seg_len decimated samples, or the capture.  Every position fits, unless a tiny
+        // samples_per_buffer on a huge context runs into kErrListMax -- then a run with more errors than slots fails
+        // with OOKD_ERR_CAPACITY (collect_results), it never hands out a list with holes.
+        const uint64_t span_in = std::min<uint64_t>(2 * rx.seg_len * rx.total_decim(), rx.max_n_in);
+        const uint64_t need = (span_in + spb - 1) / spb + 2;
+        const uint64_t room = std::max<uint64_t>(32, kErrListMax / ((uint64_t)rx.max_captures * rx.max_segs_per_cap));
+        rx.err_slots = (uint32_t)std::min<uint64_t>(need, room);
+    }
     const uint64_t total_out = rx.max_n_out * rx.max_captures;
     rx.edge_capacity = cfg.edge_capacity ? cfg.edge_capacity : total_out / 32 + (1u << 20);
     if (rx.edge_capacity > 0xfffffff0ull) rx.edge_capacity = 0xfffffff0ull;
@@ -1522,7 +1556,16 @@ int setup_scan_workspace(ookd_rx &rx) {
     rc |= rx.d_events.alloc(rx.edge_capacity + caps + 8);
     rc |= rx.d_ev_hot.alloc(rx.edge_capacity + caps + 8);
     rc |= rx.d_app_vals.alloc(2 * (rx.edge_capacity + caps) + 512 * caps + 1024);
-    rc |= rx.d_scan_errs.alloc(1u << 16);
+    {
+        // error positions of a run: at most one per buffer and capture (device.c:646), and never more than there are
+        // level changes (an error is a pulse_start / pulse_end trigger that fails its state's duration: it takes a
+        // change of level, fed or inside a dropped rest-of-buffer) -- every position fits; beyond kErrListMax a run
+        // with more errors fails with OOKD_ERR_CAPACITY (collect_results)
+        const uint64_t spb = rx.cfg.samples_per_buffer;
+        const uint64_t per_cap = (rx.max_n_in + spb - 1) / spb + 1;
+        const uint64_t need = std::min<uint64_t>(caps * per_cap, rx.edge_capacity + caps);
+        rc |= rx.d_scan_errs.alloc(std::max<uint64_t>(64, std::min<uint64_t>(need, kErrListMax)));
+    }
     rc |= rx.d_cap_fallback.alloc(caps);
     // (the walk from synchronising spans keeps a plane of entry codes per candidate)
     rx.pre_plane = rx.scan_sync ? (size_t)rx.scan_blocks_cap * leaf_block + 64 : 0;
@@ -1532,6 +1575,8 @@ int setup_scan_workspace(ookd_rx &rx) {
     rc |= rx.d_sync_rec.alloc(((size_t)rx.scan_blocks_cap + 8) * 10);     // records, digests, selections
     rc |= rx.d_blk_in.alloc((size_t)rx.scan_blocks_cap + 16);
     rc |= rx.d_final_state.alloc(caps);
+    // (fin_msg_kernel resolves every capture's record: one that no run has written yet must read as "no bits")
+    if (rc == OOKD_OK && hipMemset(rx.d_final_state.p, 0, caps * sizeof(SegState)) != hipSuccess) rc = OOKD_ERR_HIP;
     rx.scan_fin_cap = (uint32_t)((rx.edge_capacity + caps) / fsm_scan_fin_block() + caps + 8);
     rc |= rx.d_fin_off.alloc(caps + 1);
     rc |= rx.d_fsum.alloc(4 * (size_t)rx.scan_fin_cap);
