@@ -214,6 +214,56 @@ def test_append_pool_limit(ok, oracle):
     d.close()
 
 
+# ------------------------------------------------------------------------- the workspace at its smallest ----
+
+def _tight_batch(captures=3, n=4096):
+    """burst(8) messages back to back (some 20 to 40 us apart) in `captures` captures of n samples, and in each
+    capture three pulses too short for `on`: an error each, the rest of that buffer dropped"""
+    caps = []
+    for c in range(captures):
+        runs = dd.burst_runs(8, 12, seed=950 + c, lead=30 + 7 * c, gap=(20, 40))
+        for at in (41, 101, 161):       # (odd: a pulse) 20 us -> 5 us, the low run behind it takes the rest
+            runs[at], runs[at + 1] = 5, runs[at + 1] + 15
+        caps.append(dd.iq_of(stream_from_runs(runs)[:n]))
+    return caps
+
+
+@pytest.mark.parametrize("leg", ["tables", "walk", "composed"])
+def test_small_batch_in_a_workspace_of_mostly_pads(ok, oracle, leg):
+    """Three captures of four buffers of 1024 samples with an edge_capacity of exactly the batch's edges: the scan's
+    workspace is a handful of blocks and groups plus its per-capture pads (blocks_cap = edges / leaf_block + captures
+    + 8), so cap_first, the sync walk's digests and selections and every per-capture prefix lie as close to the end of
+    their allocations as they ever do.  Messages, payloads, every error position and num_edges against the oracle."""
+    spb = 1024
+    dev = dd.burst(8)
+    d, od = dd.ok_device(ok, dev), dd.fsm_desc(oracle, dev)
+    host, n, stride = _batch(_tight_batch())
+    assert n == 4 * spb
+    wants = [oracle.rx(host[c, :2 * n], None, dd.THR, od, spb, want_bits=True) for c in range(len(host))]
+    edges = [len(edges_of(w.bits)) for w in wants]
+    print("small batch: edges %s messages %s errors %s" % (edges, [len(w.msg_samples) for w in wants],
+                                                         [len(w.err_samples) for w in wants]))
+    assert all(100 <= e <= 400 for e in edges) and all(len(w.msg_samples) >= 2 and len(w.err_samples) >= 2 for w in wants)
+    kw, walk = next((kw, walk) for name, kw, walk, _ in LEGS if name == leg)
+    with _sync_walk_forced(walk):
+        rx = ok.Receiver(None, d, max_samples=n, max_captures=len(host), threshold=dd.THR, samples_per_buffer=spb,
+                         edge_capacity=sum(edges), message_capacity=256, **kw)
+    import torch
+    dev_iq = torch.from_numpy(host).cuda()
+    torch.cuda.synchronize()            # (the context's stream does not wait for the copy's)
+    got = rx.rx_device(dev_iq.data_ptr(), n, num_captures=len(host), stride=stride)
+    assert got.stats["fsm_path"] == 1 and got.stats["num_edges"] == sum(edges), got.stats
+    for c, want in enumerate(wants):
+        gc = got.for_capture(c)
+        assert list(gc.msg_samples) == list(want.msg_samples), (leg, c)
+        assert gc.payloads.shape == want.payloads.shape and (gc.payloads == want.payloads).all(), (leg, c)
+    errs_want = [int(e) for w in wants for e in w.err_samples]         # capture-major
+    errs, nerr = rx.errors(len(errs_want) + 8)
+    assert nerr == len(errs_want) == got.stats["num_errors"] and list(errs) == errs_want, leg
+    rx.close()
+    d.close()
+
+
 # --------------------------------------------------------------------------------------------- long payloads ----
 
 LONG_CASES = [(k, n) for n in dd.LONG_BITS for k in ("rle", "burst")] + [("drip", n) for n in dd.DRIP_BITS]
