@@ -290,7 +290,30 @@ typedef struct ookd_message {
 /* Carried state of the symbol state machine between shards of one capture
  * (what struct state_machine holds across sm_process calls,
  * src/state_machine.c:57-75): current state, increments of elapsed_us since
- * it was last zeroed, previous bit, bits collected so far and the payload. */
+ * it was last zeroed, previous bit, bits collected so far and the payload.
+ *
+ * A state_out is what the sequential machine holds in front of the shard's
+ * next sample, and it is canonical: two shards that leave the machine in the
+ * same condition hand on the same 64 bytes, whichever form of the state
+ * machine ran (callers compare states as bytes to see whether a refinement
+ * changed anything).  All zero is the reset state a capture starts in.
+ *   state, prev_bit : the machine's.  Behind an error the rest of that buffer
+ *       is dropped: state is the reset state and prev_bit the level of the
+ *       ERROR sample, not that of the shard's last sample.
+ *   num_bits, payload : as the machine holds them, first bit = bit 0 of byte 0.
+ *       In the reset state they are still those of the message (or the error)
+ *       before: the machine zeroes them on its next sample and nothing reads
+ *       them before that.  Payload bits at and above num_bits, and every byte
+ *       behind them, are 0.
+ *   k : increments of elapsed_us (one per evaluation without a firing) since
+ *       it was last zeroed, in every state that looks at it -- a state or
+ *       trigger duration, a time-out that a trigger waits for.  In a state in
+ *       which nothing reads it (the reset state, an idle state without a
+ *       time-out) k is 0, however long the machine has been there.  k
+ *       saturates: a state_out never holds more than 0xfffffffe, and a
+ *       state_in above that is read as that (no device window reaches it:
+ *       devices with a finite bound above 2^31 increments are refused).
+ *   reserved : 0. */
 typedef struct ookd_fsm_state {
     uint32_t state;
     uint32_t num_bits;

@@ -268,6 +268,9 @@ def lib() -> C.CDLL:
         L.ook_sm_peek.argtypes = [C.c_void_p, C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]
+        L.ook_sm_poke.restype = None
+        L.ook_sm_poke.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double,
+                                  C.c_int, C.c_char_p, C.c_size_t]
         L.ook_oracle_rx.restype = C.c_uint64
         L.ook_oracle_rx.argtypes = [
             C.c_void_p, C.c_uint64, C.POINTER(_FirDescC), C.c_float,

@@ -279,6 +279,20 @@ void ook_sm_peek(const ook_sm *sm, uint32_t *state, uint32_t *num_bits,
     if (prev_bit) *prev_bit = sm->prev_bit;
 }
 
+/* The inverse of ook_sm_peek / ook_sm_data: a machine put into a state another
+ * one was seen in (tests of the shard hand-over restart it in front of a cut). */
+void ook_sm_poke(ook_sm *sm, uint32_t state, uint32_t num_bits,
+                 double elapsed_us, int prev_bit, const uint8_t *data,
+                 size_t data_bytes)
+{
+    sm->cur = state;
+    sm->num_bits = num_bits;
+    sm->elapsed_us = elapsed_us;
+    sm->prev_bit = prev_bit;
+    memset(sm->data, 0, sizeof(sm->data));
+    memcpy(sm->data, data, data_bytes < sizeof(sm->data) ? data_bytes : sizeof(sm->data));
+}
+
 /*
  * src/state_machine.c:100-133.  A non-zero duration d gives the window
  * [ (float)(d - 0.15*d), (float)(d + 0.15*d) ]: the arithmetic is done in

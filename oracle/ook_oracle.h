@@ -124,6 +124,10 @@ const uint8_t *ook_sm_data(const ook_sm *sm);
 /* Introspection for differential tests against oracle/_ref. */
 void ook_sm_peek(const ook_sm *sm, uint32_t *state, uint32_t *num_bits,
                  double *elapsed_us, int *prev_bit);
+/* ... and its inverse: the machine as if it had got there by itself. */
+void ook_sm_poke(ook_sm *sm, uint32_t state, uint32_t num_bits,
+                 double elapsed_us, int prev_bit, const uint8_t *data,
+                 size_t data_bytes);
 
 /* ---- whole-path driver ------------------------------------------------
  * Restates ookiedokie_rx (src/ookiedokie.c:238-290) fed by the file

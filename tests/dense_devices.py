@@ -103,6 +103,16 @@ def drip(nbits, timeout_us=10):
                                 (PULSE_END, NONE, "run", 0), (TIMEOUT, APPEND_0, "run", 0)])])
 
 
+def gated(nbits):
+    """burst behind a preamble: a 20 us pulse and a gap of 30 us in front of every message.  `gap` has a DURATION, so a
+    rising edge that ends a gap of another length is an error -- on a HIGH sample; burst's only error, a pulse of the
+    wrong length in `on`, falls on a low one.  (tests/shard_cut_inputs.py: the level behind an error at a shard's end)"""
+    sync = ("sync", 20, 60, [(PULSE_END, NONE, "gap", 0), (TIMEOUT, NONE, "reset", 0)])
+    gap = ("gap", 30, 200, [(PULSE_START, NONE, "on", 0), (TIMEOUT, NONE, "reset", 0)])
+    off = ("off", 0, 200, [(PULSE_START, APPEND_1, "on", 50), (PULSE_START, APPEND_0, "on", 20), (TIMEOUT, NONE, "reset", 0)])
+    return _tables("gated%d" % nbits, nbits, [_RESET, ("idle", 0, 0, [(PULSE_START, NONE, "sync", 0)]), sync, gap, _ON, off])
+
+
 _TABLE_KEYS = ("state_duration_us", "state_timeout_us", "trig_begin", "trig_cond", "trig_action", "trig_next",
                "trig_duration_us")
 
