@@ -2,8 +2,8 @@
  * ookd_scan.c -- a C99 host on top of libookiedokie_amd.so that uses the whole chain on one capture whose
  * carriers are NOT at its centre:
  *     spectrum (ookd_spectrum_*, ookd_suggest_carriers)        which carriers are there
- *  -> per carrier a tuned envelope survey (ookd_survey_create_tuned, ookd_suggest_threshold)
- *                                                              which threshold does this carrier want
+ *  -> ONE carriers survey (ookd_survey_create_carriers; ookd_suggest_threshold per carrier)
+ *                                                              which threshold does each carrier want
  *  -> per device ONE carrier context (ookd_rx_create_carriers) that decodes every carrier at its own threshold in
  *     one pass over the capture
  *  -> formatter / rx_print text on stdout.
@@ -13,7 +13,10 @@
  *   gcc -std=c99 -Wall -Werror -Iinclude examples/ookd_scan.c -o ookd_scan \
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
- * ookd_scan <capture.sc16q11|.cs8|.cu8> <samplerate> <filter.json> <device.json> [<device.json> ...] [csv|pretty]
+ * ookd_scan [--survey-stride N] <capture.sc16q11|.cs8|.cu8> <samplerate> <filter.json> <device.json>
+ *           [<device.json> ...] [csv|pretty]
+ * --survey-stride N: the survey counts every N-th filter output (a power of two, 1 .. 64; default 1, every output;
+ * N > 1 needs a one-stage filter without decimation).
  *
  * stderr: one line per carrier -- the peak at DC (the receiver's own) is reported and skipped, every other one
  * with its threshold and the two envelope levels, or "no two envelope levels" --, and one line per carrier and
@@ -39,6 +42,14 @@ static int fail(const char *what)
 int main(int argc, char **argv)
 {
     int fmt = OOKD_RX_FMT_PRETTY;
+    uint32_t survey_stride = 1;
+    for (int i = 1; i + 1 < argc; ++i) {        /* the option may stand anywhere; it is taken out of argv */
+        if (strcmp(argv[i], "--survey-stride")) continue;
+        survey_stride = (uint32_t) strtoul(argv[i + 1], NULL, 0);
+        for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+        argc -= 2;
+        break;
+    }
     if (argc > 1 && (!strcmp(argv[argc - 1], "csv") || !strcmp(argv[argc - 1], "pretty"))) {
         fmt = !strcmp(argv[argc - 1], "csv") ? OOKD_RX_FMT_CSV : OOKD_RX_FMT_PRETTY;
         --argc;
@@ -46,8 +57,8 @@ int main(int argc, char **argv)
     const unsigned rate = argc > 2 ? (unsigned) strtoul(argv[2], NULL, 0) : 0;
     const int ndev = argc - 4;
     if (argc < 5 || ndev > MAX_DEVICES || rate == 0) {
-        fprintf(stderr, "usage: %s <capture.sc16q11|.cs8|.cu8> <samplerate> <filter.json> <device.json> "
-                        "[<device.json> ... up to %d] [csv|pretty]\n", argv[0], MAX_DEVICES);
+        fprintf(stderr, "usage: %s [--survey-stride N] <capture.sc16q11|.cs8|.cu8> <samplerate> <filter.json> "
+                        "<device.json> [<device.json> ... up to %d] [csv|pretty]\n", argv[0], MAX_DEVICES);
         return EXIT_FAILURE;
     }
     int status = EXIT_FAILURE;
@@ -117,34 +128,35 @@ int main(int argc, char **argv)
     double carrier_hz[MAX_CARRIERS];
     uint32_t ncar = 0;
     memset(carrier, 0, sizeof(carrier));
-    for (uint32_t c = 0; c < nfound; ++c) {
-        if (found[c].at_dc) continue;
-        const double hz = found[c].nu * (double) rate;
-        ookd_tune tune;
-        memset(&tune, 0, sizeof(tune));
-        tune.nu = found[c].nu;
-
-        /* 2. which threshold: the envelope this carrier has behind the filter tuned to it */
+    /* 2. which threshold: the envelope every carrier has behind the filter tuned to it -- ONE carriers survey, one
+     * pass over the capture for all of them, counting every survey_stride-th output */
+    ookd_tune tunes[MAX_CARRIERS];
+    uint32_t ntunes = 0;
+    memset(tunes, 0, sizeof(tunes));
+    for (uint32_t c = 0; c < nfound; ++c)
+        if (!found[c].at_dc) tunes[ntunes++].nu = found[c].nu;
+    survey = ookd_survey_create_carriers(0, filter, sample_flags, 1, NULL, tunes, ntunes, survey_stride);
+    if (!survey) { fail("ookd_survey_create_carriers"); goto out; }
+    if (ookd_survey_device(survey, d_iq, 1, n, n) != 0) { fail("ookd_survey_device"); goto out; }
+    for (uint32_t k = 0; k < ntunes; ++k) {
+        const double hz = tunes[k].nu * (double) rate;
         ookd_level_hist hist;
         ookd_threshold_suggestion sug;
-        survey = ookd_survey_create_tuned(0, filter, sample_flags, 1, NULL, &tune);
-        if (!survey) { fail("ookd_survey_create_tuned"); goto out; }
-        if (ookd_survey_device(survey, d_iq, 1, n, n) != 0) { fail("ookd_survey_device"); goto out; }
-        if (ookd_survey_get_hist(survey, 0, &hist) != 0) { fail("ookd_survey_get_hist"); goto out; }
+        if (ookd_survey_get_carrier_hist(survey, 0, k, &hist) != 0) { fail("ookd_survey_get_carrier_hist"); goto out; }
         if (ookd_suggest_threshold(&hist, &sug) != 0) { fail("ookd_suggest_threshold"); goto out; }
-        ookd_survey_destroy(survey);
-        survey = NULL;
         if (!sug.found) {
             fprintf(stderr, "carrier %+.6g Hz: no two envelope levels\n", hz);
             continue;
         }
         fprintf(stderr, "carrier %+.6g Hz: threshold %.6g (off %.6g, on %.6g)\n", hz, sug.threshold, sug.off_level,
                 sug.on_level);
-        carrier[ncar].nu = found[c].nu;
+        carrier[ncar].nu = tunes[k].nu;
         carrier[ncar].threshold = sug.threshold;
         carrier_hz[ncar] = hz;
         ++ncar;
     }
+    ookd_survey_destroy(survey);
+    survey = NULL;
 
     /* 3. decode: per device ONE carrier context, which reads the capture once for all carriers.  Its messages come
      * in carrier order, ookd_message.capture being the carrier index. */

@@ -730,6 +730,56 @@ ookd_survey *ookd_survey_create_tuned(int32_t hip_device, const ookd_filter *fil
 double ookd_survey_tune(const ookd_survey *s);     /* 0 for an untuned one, 0 for NULL */
 uint32_t ookd_survey_form(const ookd_survey *s);   /* the form a run takes / took; 0 for NULL */
 
+/* Carriers survey: the tuned survey of several carriers in ONE pass over the
+ * captures, counting every stride-th output.  The threshold rule does not need
+ * every power: the envelope behind a channel filter moves over hundreds of
+ * samples, so a histogram of every 8th or 64th output shows the same two levels
+ * at an 8th or a 64th of the arithmetic.
+ *
+ * The contract: carrier k's histogram of capture c is the histogram of
+ * ookd_survey_create_tuned(..., {tunes[k].nu}) on that capture, RESTRICTED TO
+ * THE OUTPUTS WITH INDEX i = 0 (mod stride), i < floor(n / D).
+ *   - the tap rule, the four unfused statements per tap, p = ar*ar + ai*ai with
+ *     its three roundings, the bin rule, zero history, nothing padded and no
+ *     input at or beyond n read: all unchanged;
+ *   - ookd_level_hist.samples = ceil(floor(n / D) / stride) = the sum of bins[];
+ *   - at stride 1 it is that survey's histogram, bin for bin;
+ *   - nu = 0 is a legal carrier (im = +0: the untuned survey's counts, as for
+ *     ookd_rx_create_carriers), and the same nu may appear twice.
+ * It stays an exact integer function of the capture: the same contract over a
+ * subset of the outputs.  ookd_suggest_threshold applies OOKD_LEVEL_MIN_SIDE to
+ * COUNTS: see there for what that means at a stride.
+ *
+ * Forms.  OOKD_SURVEY_TUNED_MULTI for 1 stage, decimation 1 and <= 256 taps,
+ * without OOKD_RX_EXACT_FIR: one launch for all carriers and captures; 8-bit
+ * captures are read in place; a capture whose first sample is not on a 16-byte
+ * boundary is read sample by sample by the same kernel and the form stays
+ * OOKD_SURVEY_TUNED_MULTI (the rule of OOKD_SURVEY_TUNED_FIR1).  Any other
+ * shape, or OOKD_RX_EXACT_FIR, at stride 1: the OOKD_SURVEY_TUNED_GENERIC path
+ * once per carrier, and that form is reported -- the cross-check partner at
+ * stride 1.  stride > 1 on those shapes or with the flag fails at create time.
+ *
+ * Fails, before any HIP call, for: num_carriers 0 or > OOKD_SURVEY_MAX_CARRIERS,
+ * tunes == NULL, a NaN nu or |nu| > 0.5, non-zero ookd_tune.reserved, no
+ * filter, a stride that is not a power of two in 1 .. OOKD_SURVEY_MAX_STRIDE,
+ * flag bits other than the sample-format bits and OOKD_RX_EXACT_FIR, both
+ * format bits, max_captures == 0.
+ *
+ * ookd_survey_device / _host / _kernel_ms / _form / _destroy and
+ * ookd_suggest_threshold serve this kind too.  ookd_survey_get_hist returns
+ * carrier 0, ookd_survey_tune carrier 0's nu. */
+#define OOKD_SURVEY_MAX_CARRIERS 16
+#define OOKD_SURVEY_MAX_STRIDE   64
+enum { OOKD_SURVEY_TUNED_MULTI = 4 };   /* several carriers, every stride-th output, one launch */
+ookd_survey *ookd_survey_create_carriers(int32_t hip_device, const ookd_filter *filter,
+                                         uint32_t flags, uint32_t max_captures, void *stream,
+                                         const ookd_tune *tunes, uint32_t num_carriers,
+                                         uint32_t stride);
+uint32_t ookd_survey_num_carriers(const ookd_survey *s);   /* 0 for the other two kinds, 0 for NULL */
+uint32_t ookd_survey_stride(const ookd_survey *s);         /* 1 for the other two kinds, 0 for NULL */
+int ookd_survey_get_carrier_hist(const ookd_survey *s, uint32_t capture, uint32_t carrier,
+                                 ookd_level_hist *out);
+
 /* The bin rule above and its inverse, pure host code (no GPU needed).
  * ookd_level_bin_lower: the power at which bin `bin` starts (0 for bin 0;
  * bins beyond 255 continue the series: 256 gives the upper edge of the
@@ -770,6 +820,9 @@ float ookd_level_bin_lower(uint32_t bin);
  * OOKD_LEVEL_MIN_SIDE, 512 samples: a level held for less is a transient --
  * the start-up ramp of a carrier that is always on (11 outputs through
  * fs32_fs4, at most the tap count) --, while one message holds thousands.
+ * The rule is applied to COUNTS: on a histogram of a carriers survey with
+ * stride S (ookd_survey_create_carriers) a level must be held for 512 * S
+ * outputs in total to count as a level.
  * Limits: two levels only (the strongest of several transmitters sets the on
  * level); a capture of tiny integer noise without a filter has a share of
  * samples exactly zero (bin 0) far from the rest and reads as two levels. */

@@ -78,6 +78,9 @@ RX_MAX_CARRIERS = 16
 SURVEY_GENERIC = 1                      # survey forms (Survey.form): OOKD_SURVEY_*; what an untuned Survey runs
 SURVEY_TUNED_GENERIC = 2                # a tuned Survey (Survey(tune=...)): any shape, the contract's order
 SURVEY_TUNED_FIR1 = 3                   # ... 1 stage, decimation 1, <= 256 taps: register-blocked, same histogram
+SURVEY_TUNED_MULTI = 4                  # a carriers Survey (Survey(carriers=[...])): several carriers, one launch
+SURVEY_MAX_CARRIERS = 16                # OOKD_SURVEY_MAX_CARRIERS
+SURVEY_MAX_STRIDE = 64                  # OOKD_SURVEY_MAX_STRIDE
 LEVEL_BINS = 256                        # OOKD_LEVEL_BINS: envelope survey, four bins per octave of power
 LEVEL_MIN_SEPARATION = 18               # OOKD_LEVEL_MIN_SEPARATION
 LEVEL_MIN_SIDE = 512                    # OOKD_LEVEL_MIN_SIDE
@@ -360,6 +363,11 @@ _PROTOTYPES = {
     "ookd_survey_create": (C.c_void_p, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "ookd_survey_create_tuned": (C.c_void_p, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                               C.POINTER(Tune)]),
+    "ookd_survey_create_carriers": (C.c_void_p, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.POINTER(Tune), C.c_uint32, C.c_uint32]),
+    "ookd_survey_num_carriers": (C.c_uint32, [C.c_void_p]),
+    "ookd_survey_stride": (C.c_uint32, [C.c_void_p]),
+    "ookd_survey_get_carrier_hist": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(LevelHist)]),
     "ookd_survey_tune": (C.c_double, [C.c_void_p]),
     "ookd_survey_form": (C.c_uint32, [C.c_void_p]),
     "ookd_survey_destroy": (None, [C.c_void_p]),
@@ -1249,11 +1257,20 @@ class Survey:
 
     tune / tune_hz with sample_rate: as `Receiver` takes them -- the survey of a carrier beside the capture's
     centre, counted through the taps `Filter.tuned_taps` returns (ookd_survey_create_tuned).  exact=True runs the
-    tuned survey's generic form for every shape (same histogram; for cross-checks)."""
+    tuned survey's generic form for every shape (same histogram; for cross-checks).
+
+    carriers=[nu, ...] with stride=S (a power of two, 1 .. 64; default 1): the tuned survey of every carrier in
+    one pass over the capture, counting the outputs with index 0 (mod S) (ookd_survey_create_carriers).
+    `hist(capture, carrier)` is one carrier's histogram, `survey(iq)` returns all of them as [K, 256]."""
 
     def __init__(self, filt: Optional[Filter], *, hip_device: int = 0, max_captures: int = 1, stream: int = 0,
                  sample_format: str = "sc16q11", tune: Optional[float] = None, tune_hz: Optional[float] = None,
-                 sample_rate: Optional[float] = None, exact: bool = False):
+                 sample_rate: Optional[float] = None, exact: bool = False, carriers=None,
+                 stride: Optional[int] = None):
+        if carriers is not None and (tune is not None or tune_hz is not None or sample_rate is not None):
+            raise ValueError("give either carriers or tune / tune_hz, not both")
+        if stride is not None and carriers is None:
+            raise ValueError("stride needs carriers: only a carriers survey counts every stride-th output")
         if tune is not None and (tune_hz is not None or sample_rate is not None):
             raise ValueError("give either tune (cycles per sample) or tune_hz with sample_rate, not both")
         if (tune_hz is None) != (sample_rate is None):
@@ -1268,7 +1285,19 @@ class Survey:
         fmt_flag, self._sample_dtype = SAMPLE_FORMATS[sample_format]
         self._filter = filt
         self.total_decimation = filt.total_decimation if filt else 1
-        if tune is None and not exact:
+        if carriers is not None:
+            nus = [float(nu) for nu in carriers]
+            tunes = (Tune * max(len(nus), 1))()
+            for t, nu in zip(tunes, nus):
+                t.nu = nu
+            if stride is None:
+                stride = 1
+            if int(stride) != stride or not 0 <= stride < 2 ** 32:
+                raise ValueError("stride must be a power of two in 1 .. %d" % SURVEY_MAX_STRIDE)
+            self._h = lib().ookd_survey_create_carriers(hip_device, filt._h if filt else None,
+                                                        fmt_flag | (RX_EXACT_FIR if exact else 0), max_captures,
+                                                        stream, tunes, len(nus), int(stride))
+        elif tune is None and not exact:
             self._h = lib().ookd_survey_create(hip_device, filt._h if filt else None, fmt_flag, max_captures, stream)
         else:
             t = None                                            # exact alone: tune = NULL, the untuned survey
@@ -1288,8 +1317,19 @@ class Survey:
 
     @property
     def form(self) -> int:
-        """The kernel form a run takes: SURVEY_GENERIC, SURVEY_TUNED_GENERIC or SURVEY_TUNED_FIR1."""
+        """The kernel form a run takes: SURVEY_GENERIC, SURVEY_TUNED_GENERIC, SURVEY_TUNED_FIR1 or
+        SURVEY_TUNED_MULTI."""
         return int(lib().ookd_survey_form(self._h))
+
+    @property
+    def num_carriers(self) -> int:
+        """Carriers of a carriers survey; 0 for the other kinds."""
+        return int(lib().ookd_survey_num_carriers(self._h))
+
+    @property
+    def stride(self) -> int:
+        """Every stride-th output is counted; 1 but for a carriers survey made with another stride."""
+        return int(lib().ookd_survey_stride(self._h))
 
     def survey_device(self, d_iq_ptr: int, samples_per_capture: int, num_captures: int = 1,
                       stride: Optional[int] = None) -> None:
@@ -1298,18 +1338,26 @@ class Survey:
                                         stride if stride is not None else samples_per_capture))
 
     def survey(self, iq: np.ndarray) -> np.ndarray:
-        """One host capture (staged over PCIe first), same arrays as `Receiver.rx` takes; returns its histogram."""
+        """One host capture (staged over PCIe first), same arrays as `Receiver.rx` takes; returns its histogram
+        (a carriers survey: every carrier's, [K, 256])."""
         if self.sample_format != "sc16q11" and np.asarray(iq).dtype != self._sample_dtype:
             raise TypeError("this Survey takes %s samples as %s, not %s"
                             % (self.sample_format, np.dtype(self._sample_dtype).name, np.asarray(iq).dtype.name))
         iq = np.ascontiguousarray(iq, dtype=self._sample_dtype).reshape(-1)
         _check(lib().ookd_survey_host(self._h, iq.ctypes.data, iq.size // 2))
-        return self.hist(0)
+        K = self.num_carriers
+        return np.stack([self.hist(0, k) for k in range(K)]) if K else self.hist(0)
 
-    def hist(self, capture: int = 0) -> np.ndarray:
-        """The 256 counts of one capture of the last run (uint64); they sum to `samples`."""
+    def hist(self, capture: int = 0, carrier: int = 0) -> np.ndarray:
+        """The 256 counts of one capture (and, of a carriers survey, one carrier) of the last run (uint64); they
+        sum to `samples`."""
         lh = LevelHist()
-        _check(lib().ookd_survey_get_hist(self._h, capture, C.byref(lh)))
+        if self.num_carriers:
+            _check(lib().ookd_survey_get_carrier_hist(self._h, capture, carrier, C.byref(lh)))
+        else:
+            if carrier:
+                raise ValueError("only a carriers survey has carriers")
+            _check(lib().ookd_survey_get_hist(self._h, capture, C.byref(lh)))
         self.samples = int(lh.samples)
         return np.frombuffer(bytes(lh.bins), dtype=np.uint64).copy()
 

@@ -573,6 +573,20 @@ bool survey_tuned_fir1_shape(uint32_t R, uint32_t waves);      // a shape the ke
 hipError_t launch_survey_tuned_fir1(const SurveyParams &p, const float *ctaps, uint32_t num_captures, uint32_t R,
                                     uint32_t waves, hipStream_t stream);
 
+// ---- tuned envelope survey of several carriers, every S-th output (survey_carriers.hip) ----------
+// One launch for K carriers and all captures: SurveyParams as for the fir1 form with p.tile = 64 R, R = 8, 16, 32 or 64
+// (survey_multi_R: the measured choice per stride); ctaps holds
+// carrier k's ntaps_pad (re, im) pairs at ctaps + 2 * ntaps_pad * k; p.hist is [captures][K][kLevelBins], zero at
+// launch; stride a power of two, 1 .. kSurveyMaxStride.  Carrier k's counts are the fir1 form's for its taps over
+// the outputs i = 0 (mod stride).
+constexpr int kSurveyMaxCarriers = 16;          // OOKD_SURVEY_MAX_CARRIERS
+constexpr int kSurveyMaxStride = 64;            // OOKD_SURVEY_MAX_STRIDE
+constexpr int kSurveyMultiWaves = 4;            // waves per workgroup, which share the K x 256 counters
+inline uint32_t survey_multi_R(uint32_t stride) { return stride >= 32u ? 32u : stride >= 16u ? 16u : 8u; }
+bool survey_multi_shape(uint32_t R, uint32_t stride);  // a shape the kernel is instantiated for: 8, 16; 32, 64 for S >= R
+hipError_t launch_survey_tuned_multi(const SurveyParams &p, const float *ctaps, uint32_t num_captures, uint32_t K,
+                                     uint32_t stride, hipStream_t stream);
+
 // ---- carrier survey (spectrum.hip) ----------------------------------------------
 // Welch power spectrum of every capture: whole 1024-sample periodic-Hann frames, fp32 inside a frame, double
 // across frames, no padding; the contract is in the header at ookd_spectrum_*.

@@ -24,7 +24,11 @@ struct ookd_survey : ScanCtx {
     unsigned long long *d_hist = nullptr;
     uint32_t num_captures = 0;      // of the last run
     uint64_t samples = 0;           // floor(n / D) of the last run
-    std::vector<uint64_t> hist;     // [num_captures][kLevelBins]
+    std::vector<uint64_t> hist;     // [num_captures][kLevelBins]; a carriers survey: [num_captures][K][kLevelBins]
+    // carriers survey (ookd_survey_create_carriers): K > 0, the stride, every carrier's nu, and -- where the shape
+    // has no OOKD_SURVEY_TUNED_MULTI form -- one tuned survey per carrier on this context's stream
+    uint32_t num_carriers = 0, stride = 1;
+    std::vector<std::unique_ptr<ookd_survey>> singles;
 
     ~ookd_survey() {
         if (dev < 0) return;
@@ -300,11 +304,148 @@ ookd_survey *ookd_survey_create_tuned(int32_t hip_device, const ookd_filter *fil
                          (flags & OOKD_RX_EXACT_FIR) != 0);
 }
 
+ookd_survey *ookd_survey_create_carriers(int32_t hip_device, const ookd_filter *filter, uint32_t flags,
+                                         uint32_t max_captures, void *stream, const ookd_tune *tunes,
+                                         uint32_t num_carriers, uint32_t stride) {
+    static const char who[] = "ookd_survey_create_carriers";
+    static_assert(OOKD_SURVEY_MAX_CARRIERS == kSurveyMaxCarriers && OOKD_SURVEY_MAX_STRIDE == kSurveyMaxStride,
+                  "OOKD_SURVEY_MAX_*");
+    clear_error();
+    const uint32_t both = OOKD_RX_SAMPLES_CS8 | OOKD_RX_SAMPLES_CU8;
+    if ((flags & ~(both | OOKD_RX_EXACT_FIR)) || (flags & both) == both) {
+        set_error("%s: flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8, with or without OOKD_RX_EXACT_FIR",
+                  who);
+        return nullptr;
+    }
+    if (num_carriers == 0 || num_carriers > OOKD_SURVEY_MAX_CARRIERS) {
+        set_error("%s: num_carriers must be 1 .. %d, not %u", who, OOKD_SURVEY_MAX_CARRIERS, num_carriers);
+        return nullptr;
+    }
+    if (!tunes) {
+        set_error("%s: tunes is NULL", who);
+        return nullptr;
+    }
+    for (uint32_t k = 0; k < num_carriers; ++k) {
+        if (!(std::fabs(tunes[k].nu) <= 0.5)) {
+            set_error("%s: carrier %u: nu must be within [-0.5, 0.5] cycles per sample", who, k);
+            return nullptr;
+        }
+        if (tunes[k].reserved[0] | tunes[k].reserved[1] | tunes[k].reserved[2]) {
+            set_error("%s: carrier %u: ookd_tune.reserved must be zero", who, k);
+            return nullptr;
+        }
+    }
+    if (!filter) {
+        set_error("%s: a carriers survey needs a filter: without one the power is |x|^2 for every carrier", who);
+        return nullptr;
+    }
+    if (stride == 0 || stride > OOKD_SURVEY_MAX_STRIDE || (stride & (stride - 1u))) {
+        set_error("%s: stride must be a power of two in 1 .. %d, not %u", who, OOKD_SURVEY_MAX_STRIDE, stride);
+        return nullptr;
+    }
+    if (!scan_ctx_check_create(who, flags & both, max_captures)) return nullptr;
+    if (filter->stages.empty() || filter->stages.size() > (size_t)kMaxStages) {
+        set_error("%s: filters of 1 .. %d stages are supported", who, kMaxStages);
+        return nullptr;
+    }
+    for (size_t i = 0; i < filter->stages.size(); ++i)
+        if (filter->stages[i].taps.empty() || filter->stages[i].decimation == 0) {
+            set_error("%s: stage %zu has no taps or no decimation", who, i);
+            return nullptr;
+        }
+    const bool exact = (flags & OOKD_RX_EXACT_FIR) != 0;
+    const bool multi = !exact && filter->stages.size() == 1 && filter->stages[0].decimation == 1 &&
+                       filter->stages[0].taps.size() <= 256u;
+    if (!multi && stride != 1) {
+        set_error("%s: stride %u needs the OOKD_SURVEY_TUNED_MULTI form: 1 stage, decimation 1, at most 256 taps, no "
+                  "OOKD_RX_EXACT_FIR; every other survey counts every output (stride 1)", who, stride);
+        return nullptr;
+    }
+    std::unique_ptr<ookd_survey> s(new ookd_survey());
+    if (!scan_ctx_open(*s, who, hip_device, flags & both, max_captures, stream)) return nullptr;
+    s->num_carriers = num_carriers;
+    s->stride = stride;
+    s->tune_nu = tunes[0].nu != 0.0 ? tunes[0].nu : 0.0;
+    s->total_decim = filter->total_decimation;
+    if (!multi) {
+        // the tuned contract's generic form, carrier by carrier (nu = 0: the untuned survey, the same counts)
+        s->form = OOKD_SURVEY_TUNED_GENERIC;
+        for (uint32_t k = 0; k < num_carriers; ++k) {
+            ookd_survey *one = survey_create(who, hip_device, filter, flags & both, max_captures, s->stream,
+                                             tunes[k].nu, true);
+            if (!one) return nullptr;
+            s->singles.emplace_back(one);
+        }
+        return s.release();
+    }
+    s->form = OOKD_SURVEY_TUNED_MULTI;
+    const std::vector<float> &h = filter->stages[0].taps;
+    const size_t pad = (h.size() + kTunedChunk - 1) / kTunedChunk * kTunedChunk;
+    SurveyParams &p = s->params;
+    p.sample_fmt = s->fmt;
+    p.num_stages = 1;
+    p.stage[0].decim = 1;
+    p.stage[0].ntaps = (uint32_t)h.size();
+    p.stage[0].ntaps_pad = (uint32_t)pad;
+    p.stage[0].tap_off = 0;
+    // the measured shape per stride; OOKD_SURVEY_MULTI_R=<8|16|32|64> is the experiment hook the rate
+    // tool compares the two with
+    uint32_t R = survey_multi_R(stride);
+    if (const char *e = dev_getenv("OOKD_SURVEY_MULTI_R")) {
+        R = (uint32_t)strtoul(e, nullptr, 10);
+        if (!survey_multi_shape(R, stride)) {
+            set_error("%s: OOKD_SURVEY_MULTI_R must be 8 or 16, or 32 or 64 up to the stride, not '%s'", who, e);
+            return nullptr;
+        }
+    }
+    p.tile = 64u * R;
+    p.num_taps = (uint32_t)h.size();
+    std::vector<float> ctaps((size_t)num_carriers * 2 * pad, 0.0f);     // carrier k's pairs at 2 * pad * k
+    std::vector<float> re(h.size()), im(h.size());
+    for (uint32_t k = 0; k < num_carriers; ++k) {
+        tuned_stage_taps(h, tunes[k].nu, 1, re.data(), im.data());
+        for (size_t t = 0; t < h.size(); ++t) {
+            ctaps[2 * (pad * k + t)] = re[t];
+            ctaps[2 * (pad * k + t) + 1] = im[t];
+        }
+    }
+    if (hipMalloc(reinterpret_cast<void **>(&s->d_hist),
+                  (size_t)max_captures * num_carriers * kLevelBins * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&s->d_ctaps), ctaps.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(s->d_ctaps, ctaps.data(), ctaps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: device allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return nullptr;
+    }
+    p.hist = s->d_hist;
+    return s.release();
+}
+
 double ookd_survey_tune(const ookd_survey *s) { return s ? s->tune_nu : 0.0; }
 
 uint32_t ookd_survey_form(const ookd_survey *s) { return s ? s->form : 0u; }
 
 void ookd_survey_destroy(ookd_survey *s) { delete s; }
+
+// A carriers survey without the multi form: the tuned survey of every carrier in turn, on the one stream.
+static int survey_singles_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, uint64_t samples_per_capture,
+                                 uint64_t capture_stride_samples) {
+    const uint32_t K = s->num_carriers;
+    s->hist.assign((size_t)num_captures * K * kLevelBins, 0);
+    s->num_captures = 0;
+    s->kernel_ms = 0.0f;
+    for (uint32_t k = 0; k < K; ++k) {
+        ookd_survey *one = s->singles[k].get();
+        const int rc = ookd_survey_device(one, d_iq, num_captures, samples_per_capture, capture_stride_samples);
+        if (rc != OOKD_OK) return rc;
+        for (uint32_t c = 0; c < num_captures; ++c)
+            memcpy(s->hist.data() + ((size_t)c * K + k) * kLevelBins, one->hist.data() + (size_t)c * kLevelBins,
+                   kLevelBins * sizeof(uint64_t));
+        s->kernel_ms += one->kernel_ms;
+        s->samples = one->samples;
+    }
+    s->num_captures = num_captures;
+    return OOKD_OK;
+}
 
 int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, uint64_t samples_per_capture,
                        uint64_t capture_stride_samples) {
@@ -312,19 +453,24 @@ int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, 
     const int rc = scan_ctx_check_run(s, "ookd_survey_device", d_iq, num_captures, samples_per_capture,
                                       capture_stride_samples, false);
     if (rc != OOKD_OK) return rc;
+    if (!s->singles.empty())
+        return survey_singles_device(s, d_iq, num_captures, samples_per_capture, capture_stride_samples);
     (void)hipSetDevice(s->dev);
     SurveyParams p = s->params;
     p.iq = d_iq;
     p.cap_stride = capture_stride_samples;
     p.n_out = samples_per_capture / s->total_decim;
     p.num_tiles = (p.n_out + p.tile - 1) / p.tile;
-    const size_t hist_bytes = (size_t)num_captures * kLevelBins * sizeof(unsigned long long);
-    s->hist.assign((size_t)num_captures * kLevelBins, 0);
+    const size_t per_capture = (size_t)(s->num_carriers ? s->num_carriers : 1u) * kLevelBins;
+    const size_t hist_bytes = (size_t)num_captures * per_capture * sizeof(unsigned long long);
+    s->hist.assign((size_t)num_captures * per_capture, 0);
     s->num_captures = 0;
     s->kernel_ms = 0.0f;
     bool ok = hipMemsetAsync(s->d_hist, 0, hist_bytes, s->stream) == hipSuccess;
     ok = ok && hipEventRecord(s->t0, s->stream) == hipSuccess;
-    if (s->form == OOKD_SURVEY_TUNED_FIR1)
+    if (s->form == OOKD_SURVEY_TUNED_MULTI)
+        ok = ok && launch_survey_tuned_multi(p, s->d_ctaps, num_captures, s->num_carriers, s->stride, s->stream) == hipSuccess;
+    else if (s->form == OOKD_SURVEY_TUNED_FIR1)
         ok = ok && launch_survey_tuned_fir1(p, s->d_ctaps, num_captures, s->fir1_R, s->fir1_waves, s->stream) == hipSuccess;
     else        // (d_ctaps is null unless the form is OOKD_SURVEY_TUNED_GENERIC)
         ok = ok && launch_survey(p, s->d_ctaps, num_captures, s->lds_bytes, s->stream) == hipSuccess;
@@ -338,7 +484,7 @@ int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, 
     }
     if (p.num_tiles) (void)hipEventElapsedTime(&s->kernel_ms, s->t0, s->t1);
     s->num_captures = num_captures;
-    s->samples = p.n_out;
+    s->samples = (p.n_out + s->stride - 1) / s->stride;     // (stride is 1 but for a carriers survey)
     return OOKD_OK;
 }
 
@@ -359,9 +505,27 @@ int ookd_survey_get_hist(const ookd_survey *s, uint32_t capture, ookd_level_hist
         return OOKD_ERR_ARG;
     }
     out->samples = s->samples;
-    memcpy(out->bins, s->hist.data() + (size_t)capture * kLevelBins, sizeof out->bins);
+    // (a carriers survey: carrier 0)
+    memcpy(out->bins, s->hist.data() + (size_t)capture * (s->num_carriers ? s->num_carriers : 1u) * kLevelBins,
+           sizeof out->bins);
     return OOKD_OK;
 }
+
+int ookd_survey_get_carrier_hist(const ookd_survey *s, uint32_t capture, uint32_t carrier, ookd_level_hist *out) {
+    clear_error();
+    if (!s || !out || !s->num_carriers || capture >= s->num_captures || carrier >= s->num_carriers) {
+        set_error("ookd_survey_get_carrier_hist: bad argument (capture %u of %u, carrier %u of %u)", capture,
+                  s ? s->num_captures : 0, carrier, s ? s->num_carriers : 0);
+        return OOKD_ERR_ARG;
+    }
+    out->samples = s->samples;
+    memcpy(out->bins, s->hist.data() + ((size_t)capture * s->num_carriers + carrier) * kLevelBins, sizeof out->bins);
+    return OOKD_OK;
+}
+
+uint32_t ookd_survey_num_carriers(const ookd_survey *s) { return s ? s->num_carriers : 0u; }
+
+uint32_t ookd_survey_stride(const ookd_survey *s) { return s ? s->stride : 0u; }
 
 float ookd_survey_kernel_ms(const ookd_survey *s) { return s ? s->kernel_ms : 0.0f; }
 

@@ -57,6 +57,42 @@ __device__ __forceinline__ void wave_count(uint32_t *wave_hist, bool valid, uint
     }
     if ((todo >> lane) & 1ull) atomicAdd(&wave_hist[bin], 1u);
 }
+
+// tuned_chunk<true, R> (front_dev.hpp) for a lane that accumulates only every STEP-th of its R output positions:
+// acc[j] is position j * STEP.  Window position W (newest first) feeds it with tap kk = j * STEP - W when
+// 0 <= kk < 16, so every counted output still receives its taps in ascending order, each as the exact packed
+// multiply and add; a window position no counted output reads is not loaded.  STEP = 1 is tuned_chunk<true, R>.
+template <int R, int STEP, int W, int... Js>
+__device__ __forceinline__ void tuned_wstep_strided(v2f *acc, const v2f *tpair, const v2f *base,
+                                                    std::integer_sequence<int, Js...>) {
+    constexpr int cp = W + kTunedChunk;                 // 1 .. R + 15
+    constexpr bool used = ((Js * STEP - W >= 0 && Js * STEP - W < kTunedChunk) || ...);
+    if constexpr (used) {
+        const v2f x = base[cp + cp / R];
+        ((void)((Js * STEP - W >= 0 && Js * STEP - W < kTunedChunk)
+                    ? (cmac_tuned<true>(acc[Js], tpair[(Js * STEP - W) & 15], x), 0)
+                    : 0),
+         ...);
+    }
+}
+
+// The same for a lane with ONE counted output, position 0 of its R >= 32: tap kk of chunk-from-the-end m reads
+// window index R * lane + u, u = 16 (m + 1) - kk, at slot (R + 1) * lane + u + u / R -- 16 m is no multiple of R here,
+// so the pad slots in front of u are counted at run time (u is wave-uniform).  lanebase = window + (R + 1) * lane.
+template <int R>
+__device__ __forceinline__ void tuned_chunk_single(v2f &acc, const v2f *tpair, const v2f *lanebase, uint32_t m) {
+#pragma unroll
+    for (int kk = 0; kk < kTunedChunk; ++kk) {
+        const uint32_t u = (uint32_t)kTunedChunk * (m + 1u) - (uint32_t)kk;
+        cmac_tuned<true>(acc, tpair[kk], lanebase[u + u / (uint32_t)R]);
+    }
+}
+
+template <int R, int STEP, int... Ws>
+__device__ __forceinline__ void tuned_chunk_strided(v2f *acc, const v2f *tpair, const v2f *base,
+                                                    std::integer_sequence<int, Ws...>) {
+    (tuned_wstep_strided<R, STEP, R - 1 - Ws>(acc, tpair, base, std::make_integer_sequence<int, R / STEP>{}), ...);
+}
 #endif
 
 }  // namespace ookd
