@@ -16,7 +16,8 @@
  * ookd_scan [--survey-stride N] <capture.sc16q11|.cs8|.cu8> <samplerate> <filter.json> <device.json>
  *           [<device.json> ...] [csv|pretty]
  * --survey-stride N: the survey counts every N-th filter output (a power of two, 1 .. 64; default 1, every output;
- * N > 1 needs a one-stage filter without decimation).
+ * N > 1 needs a one-stage filter without decimation, or two decimate-by-2 stages of <= 16 and <= 32 taps such as
+ * the backend default fs128_fs16_dec4).
  *
  * stderr: one line per carrier -- the peak at DC (the receiver's own) is reported and skipped, every other one
  * with its threshold and the two envelope levels, or "no two envelope levels" --, and one line per carrier and
@@ -135,7 +136,9 @@ int main(int argc, char **argv)
     memset(tunes, 0, sizeof(tunes));
     for (uint32_t c = 0; c < nfound; ++c)
         if (!found[c].at_dc) tunes[ntunes++].nu = found[c].nu;
-    survey = ookd_survey_create_carriers(0, filter, sample_flags, 1, NULL, tunes, ntunes, survey_stride);
+    /* (OOKD_RX_TUNED_FIR2: a 2 x decimate-by-2 filter, the backend default, is surveyed by the fused kernel too) */
+    survey = ookd_survey_create_carriers(0, filter, sample_flags | OOKD_RX_TUNED_FIR2, 1, NULL, tunes, ntunes,
+                                         survey_stride);
     if (!survey) { fail("ookd_survey_create_carriers"); goto out; }
     if (ookd_survey_device(survey, d_iq, 1, n, n) != 0) { fail("ookd_survey_device"); goto out; }
     for (uint32_t k = 0; k < ntunes; ++k) {

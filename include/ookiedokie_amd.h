@@ -759,11 +759,37 @@ uint32_t ookd_survey_form(const ookd_survey *s);   /* the form a run takes / too
  * once per carrier, and that form is reported -- the cross-check partner at
  * stride 1.  stride > 1 on those shapes or with the flag fails at create time.
  *
+ * OOKD_SURVEY_TUNED_MULTI_FIR2, on request: with OOKD_RX_TUNED_FIR2 in `flags`
+ * (the flag of the rx contexts) a filter of two decimate-by-2 stages of <= 16
+ * and <= 32 taps -- the backend default fs128_fs16_dec4 -- without
+ * OOKD_RX_EXACT_FIR is surveyed in one launch for all carriers and captures,
+ * at every stride.  Nothing new is defined: it is the contract above with
+ * D = 4, written out for this shape:
+ *   - the taps are ookd_filter_tuned_taps(f, nu_k, s, ...) for s = 0, 1; each
+ *     tap is the four unfused float32 statements, tap 0 on the newest sample,
+ *     the accumulators from +0;
+ *   - stage 0 output j sits on input 2 j + 1, stage 1 output i on stage-0
+ *     output 2 i + 1; the history is zero: inputs and stage-0 outputs with a
+ *     negative index are +0;
+ *   - only outputs i = 0 (mod stride), i < floor(n / 4), are counted, and
+ *     samples = ceil(floor(n / 4) / stride);
+ *   - no fused multiply-add, no guard band, no matrix core, no shortcut for
+ *     im == 0: a stage-0 output of inf times a stage-1 tap of +-0 is NaN here
+ *     as in the contract.
+ * All three sample formats are read in place; a capture whose first sample is
+ * not on a 16-byte boundary is read sample by sample by the same kernel and the
+ * form stays OOKD_SURVEY_TUNED_MULTI_FIR2.  The stride saves less here than on
+ * a single stage: counted outputs are 2 S stage-0 outputs apart and stage 1
+ * spans up to 32 of them, so up to stride 16 every stage-0 output is still
+ * needed and only stage 1 thins; from 32 on stage 0 thins too.  On every other shape and together with OOKD_RX_EXACT_FIR the
+ * flag is accepted and has no effect: the forms and refusals of the paragraph
+ * above.  Without the flag nothing changes.
+ *
  * Fails, before any HIP call, for: num_carriers 0 or > OOKD_SURVEY_MAX_CARRIERS,
  * tunes == NULL, a NaN nu or |nu| > 0.5, non-zero ookd_tune.reserved, no
  * filter, a stride that is not a power of two in 1 .. OOKD_SURVEY_MAX_STRIDE,
- * flag bits other than the sample-format bits and OOKD_RX_EXACT_FIR, both
- * format bits, max_captures == 0.
+ * flag bits other than the sample-format bits, OOKD_RX_EXACT_FIR and
+ * OOKD_RX_TUNED_FIR2, both format bits, max_captures == 0.
  *
  * ookd_survey_device / _host / _kernel_ms / _form / _destroy and
  * ookd_suggest_threshold serve this kind too.  ookd_survey_get_hist returns
@@ -771,6 +797,7 @@ uint32_t ookd_survey_form(const ookd_survey *s);   /* the form a run takes / too
 #define OOKD_SURVEY_MAX_CARRIERS 16
 #define OOKD_SURVEY_MAX_STRIDE   64
 enum { OOKD_SURVEY_TUNED_MULTI = 4 };   /* several carriers, every stride-th output, one launch */
+enum { OOKD_SURVEY_TUNED_MULTI_FIR2 = 5 };  /* ... through 2 x decimate-by-2, with OOKD_RX_TUNED_FIR2 */
 ookd_survey *ookd_survey_create_carriers(int32_t hip_device, const ookd_filter *filter,
                                          uint32_t flags, uint32_t max_captures, void *stream,
                                          const ookd_tune *tunes, uint32_t num_carriers,

@@ -79,6 +79,7 @@ SURVEY_GENERIC = 1                      # survey forms (Survey.form): OOKD_SURVE
 SURVEY_TUNED_GENERIC = 2                # a tuned Survey (Survey(tune=...)): any shape, the contract's order
 SURVEY_TUNED_FIR1 = 3                   # ... 1 stage, decimation 1, <= 256 taps: register-blocked, same histogram
 SURVEY_TUNED_MULTI = 4                  # a carriers Survey (Survey(carriers=[...])): several carriers, one launch
+SURVEY_TUNED_MULTI_FIR2 = 5             # ... with tuned_fir2=True on 2 x decimate-by-2 (<= 16, <= 32 taps): any stride
 SURVEY_MAX_CARRIERS = 16                # OOKD_SURVEY_MAX_CARRIERS
 SURVEY_MAX_STRIDE = 64                  # OOKD_SURVEY_MAX_STRIDE
 LEVEL_BINS = 256                        # OOKD_LEVEL_BINS: envelope survey, four bins per octave of power
@@ -1261,16 +1262,22 @@ class Survey:
 
     carriers=[nu, ...] with stride=S (a power of two, 1 .. 64; default 1): the tuned survey of every carrier in
     one pass over the capture, counting the outputs with index 0 (mod S) (ookd_survey_create_carriers).
-    `hist(capture, carrier)` is one carrier's histogram, `survey(iq)` returns all of them as [K, 256]."""
+    `hist(capture, carrier)` is one carrier's histogram, `survey(iq)` returns all of them as [K, 256].
+
+    tuned_fir2=True (with carriers; OOKD_RX_TUNED_FIR2, as `Receiver` takes it): a filter of two decimate-by-2 stages
+    (<= 16 and <= 32 taps, the backend default fs128_fs16_dec4) is surveyed in one pass for all carriers, at every
+    stride (SURVEY_TUNED_MULTI_FIR2; the same histograms).  No effect on other shapes or with exact=True."""
 
     def __init__(self, filt: Optional[Filter], *, hip_device: int = 0, max_captures: int = 1, stream: int = 0,
                  sample_format: str = "sc16q11", tune: Optional[float] = None, tune_hz: Optional[float] = None,
                  sample_rate: Optional[float] = None, exact: bool = False, carriers=None,
-                 stride: Optional[int] = None):
+                 stride: Optional[int] = None, tuned_fir2: bool = False):
         if carriers is not None and (tune is not None or tune_hz is not None or sample_rate is not None):
             raise ValueError("give either carriers or tune / tune_hz, not both")
         if stride is not None and carriers is None:
             raise ValueError("stride needs carriers: only a carriers survey counts every stride-th output")
+        if tuned_fir2 and carriers is None:
+            raise ValueError("tuned_fir2 needs carriers: only a carriers survey has the fused two-stage form")
         if tune is not None and (tune_hz is not None or sample_rate is not None):
             raise ValueError("give either tune (cycles per sample) or tune_hz with sample_rate, not both")
         if (tune_hz is None) != (sample_rate is None):
@@ -1295,7 +1302,8 @@ class Survey:
             if int(stride) != stride or not 0 <= stride < 2 ** 32:
                 raise ValueError("stride must be a power of two in 1 .. %d" % SURVEY_MAX_STRIDE)
             self._h = lib().ookd_survey_create_carriers(hip_device, filt._h if filt else None,
-                                                        fmt_flag | (RX_EXACT_FIR if exact else 0), max_captures,
+                                                        fmt_flag | (RX_EXACT_FIR if exact else 0)
+                                                        | (RX_TUNED_FIR2 if tuned_fir2 else 0), max_captures,
                                                         stream, tunes, len(nus), int(stride))
         elif tune is None and not exact:
             self._h = lib().ookd_survey_create(hip_device, filt._h if filt else None, fmt_flag, max_captures, stream)
@@ -1317,8 +1325,8 @@ class Survey:
 
     @property
     def form(self) -> int:
-        """The kernel form a run takes: SURVEY_GENERIC, SURVEY_TUNED_GENERIC, SURVEY_TUNED_FIR1 or
-        SURVEY_TUNED_MULTI."""
+        """The kernel form a run takes: SURVEY_GENERIC, SURVEY_TUNED_GENERIC, SURVEY_TUNED_FIR1,
+        SURVEY_TUNED_MULTI or SURVEY_TUNED_MULTI_FIR2."""
         return int(lib().ookd_survey_form(self._h))
 
     @property

@@ -640,9 +640,9 @@ hipError_t launch_front_tuned_fir1(const FrontParams &p, uint32_t num_captures, 
 bool front_uses_tuned_fir2(const FrontParams &p) {
     // use_fir2's shape (kernels.hip: every level's phase is D - 1 when the origin is a multiple of the total
     // decimation), tuned, asked for, and not forced to the contract's order (tune == 2)
-    return p.tune == 1 && p.tuned_fir2 && p.ctaps && p.num_stages == 2 && !p.iq_f32 && !p.halo_f32 &&
-           p.stage[0].decim == 2 && p.stage[1].decim == 2 && p.stage[0].ntaps <= (uint32_t)Fir2Dec4::T1 &&
-           p.stage[1].ntaps <= (uint32_t)Fir2Dec4::T2 && p.origin % 4 == 0;
+    static_assert(Fir2Dec4::T1 == 16 && Fir2Dec4::T2 == 32, "tuned_fir2_shape's tap counts");
+    return p.tune == 1 && p.tuned_fir2 && p.ctaps && !p.iq_f32 && !p.halo_f32 &&
+           tuned_fir2_shape(p.stage, p.num_stages) && p.origin % 4 == 0;
 }
 
 hipError_t launch_front_tuned_fir2(const FrontParams &p, uint32_t num_captures, hipStream_t stream, hipEvent_t t0,

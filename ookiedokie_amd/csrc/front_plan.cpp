@@ -296,8 +296,7 @@ bool plan_carrier(FrontPlan &pl, const ookd_filter &filter, uint32_t flags, Carr
     band_from_error(c.err_valu, c.p_star, c.p_lo, c.p_hi);
     // (the shapes front_uses_tuned_fir1 and, where asked for, front_uses_tuned_fir2 take: the tuned kernels with a
     //  quiet test)
-    if (fp.tuned_fir2 && fp.num_stages == 2 && fp.stage[0].decim == 2 && fp.stage[1].decim == 2 &&
-        fp.stage[0].ntaps <= 16u && fp.stage[1].ntaps <= 32u) {
+    if (fp.tuned_fir2 && tuned_fir2_shape(fp.stage, fp.num_stages)) {
         return tuned_quiet_weights2(re, im, c.threshold, flags, c.quiet_a, c.quiet_b);
     }
     return fp.num_stages == 1 && fp.stage[0].decim == 1 && fp.stage[0].ntaps_pad <= 256u &&

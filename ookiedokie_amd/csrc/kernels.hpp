@@ -197,6 +197,11 @@ hipError_t launch_front_tuned_generic(const FrontParams &p, uint32_t num_capture
 // 2 x decimate-by-2 (<= 16, <= 32 taps), origin a multiple of 4, asked for (FrontParams::tuned_fir2) and not forced
 // to the contract's order: fir2_tuned_kernel (OOKD_FRONT_TUNED_FIR2), tiles of kTunedFir2Tile final outputs
 constexpr uint32_t kTunedFir2Tile = 256;
+// the filter shape of the fused two-stage tuned kernels, front end and survey alike (Fir2Dec4, front_dev.hpp)
+inline bool tuned_fir2_shape(const FirStageDev *stage, uint32_t num_stages) {
+    return num_stages == 2 && stage[0].decim == 2 && stage[1].decim == 2 && stage[0].ntaps <= 16u &&
+           stage[1].ntaps <= 32u;
+}
 bool front_uses_tuned_fir2(const FrontParams &p);
 hipError_t launch_front_tuned_fir2(const FrontParams &p, uint32_t num_captures, hipStream_t stream, hipEvent_t t0,
                                    hipEvent_t t1, uint64_t tile_begin, uint64_t tile_count);
@@ -586,6 +591,18 @@ inline uint32_t survey_multi_R(uint32_t stride) { return stride >= 32u ? 32u : s
 bool survey_multi_shape(uint32_t R, uint32_t stride);  // a shape the kernel is instantiated for: 8, 16; 32, 64 for S >= R
 hipError_t launch_survey_tuned_multi(const SurveyParams &p, const float *ctaps, uint32_t num_captures, uint32_t K,
                                      uint32_t stride, hipStream_t stream);
+
+// ---- the same through two decimate-by-2 stages, <= 16 and <= 32 taps (survey_carriers_fir2.hip) ----------
+// The shape is tuned_fir2_shape's.  SurveyParams carries both stages (decim, true ntaps), p.tile = kSurveyFir2Tile,
+// p.n_out = floor(n / 4), p.num_tiles = ceil(n_out / tile); n = samples per capture (no input at or beyond it is
+// read).  ctaps holds carrier k's pairs at ctaps + kSurveyFir2TapFloats * k: stage 0 zero padded to 16 pairs, then
+// stage 1 zero padded to 32 pairs.  p.hist and stride as for launch_survey_tuned_multi.  Carrier k's counts are the
+// tuned contract's, chained over both stages, over the outputs i = 0 (mod stride).  thin: at strides 32 and 64 stage 0
+// computes only the row entries a counted output reads (the measured choice; the same counts).
+constexpr uint32_t kSurveyFir2Tile = 256;       // final outputs per wave tile
+constexpr int kSurveyFir2TapFloats = 2 * (16 + 32);
+hipError_t launch_survey_tuned_multi_fir2(const SurveyParams &p, const float *ctaps, uint32_t num_captures, uint32_t K,
+                                          uint32_t stride, uint64_t n, bool thin, hipStream_t stream);
 
 // ---- carrier survey (spectrum.hip) ----------------------------------------------
 // Welch power spectrum of every capture: whole 1024-sample periodic-Hann frames, fp32 inside a frame, double

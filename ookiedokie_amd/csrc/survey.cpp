@@ -21,6 +21,7 @@ struct ookd_survey : ScanCtx {
     double tune_nu = 0.0;
     float *d_ctaps = nullptr;
     uint32_t fir1_R = kSurveyFir1R, fir1_waves = kSurveyFir1Waves;
+    bool fir2_thin = true;          // OOKD_SURVEY_TUNED_MULTI_FIR2 at strides 32, 64: stage 0 thinned
     unsigned long long *d_hist = nullptr;
     uint32_t num_captures = 0;      // of the last run
     uint64_t samples = 0;           // floor(n / D) of the last run
@@ -304,6 +305,52 @@ ookd_survey *ookd_survey_create_tuned(int32_t hip_device, const ookd_filter *fil
                          (flags & OOKD_RX_EXACT_FIR) != 0);
 }
 
+// The rest of ookd_survey_create_carriers for OOKD_SURVEY_TUNED_MULTI_FIR2 (survey_carriers_fir2.hip): both stages'
+// complex taps per carrier, zero padded to 16 and 32 pairs.
+static bool survey_carriers_fir2(const char *who, std::unique_ptr<ookd_survey> &s, const ookd_filter *filter,
+                                 const ookd_tune *tunes) {
+    s->form = OOKD_SURVEY_TUNED_MULTI_FIR2;
+    SurveyParams &p = s->params;
+    p.sample_fmt = s->fmt;
+    p.num_stages = 2;
+    const uint32_t pad[2] = {16u, 32u};
+    for (uint32_t i = 0; i < 2; ++i) {
+        p.stage[i].decim = 2;
+        p.stage[i].ntaps = (uint32_t)filter->stages[i].taps.size();
+        p.stage[i].ntaps_pad = pad[i];
+        p.stage[i].tap_off = i ? pad[0] : 0u;
+        p.num_taps += p.stage[i].ntaps;
+    }
+    p.tile = kSurveyFir2Tile;
+    // the measured choice; OOKD_SURVEY_FIR2_THIN=0 is the experiment hook the rate tool compares with
+    if (const char *e = dev_getenv("OOKD_SURVEY_FIR2_THIN")) s->fir2_thin = atoi(e) != 0;
+    const uint32_t K = s->num_carriers;
+    std::vector<float> ctaps((size_t)K * kSurveyFir2TapFloats, 0.0f);
+    for (uint32_t k = 0; k < K; ++k) {
+        uint64_t before = 1;
+        for (uint32_t i = 0; i < 2; ++i) {
+            const std::vector<float> &h = filter->stages[i].taps;
+            std::vector<float> re(h.size()), im(h.size());
+            tuned_stage_taps(h, tunes[k].nu, before, re.data(), im.data());
+            float *dst = ctaps.data() + (size_t)kSurveyFir2TapFloats * k + 2 * p.stage[i].tap_off;
+            for (size_t t = 0; t < h.size(); ++t) {
+                dst[2 * t] = re[t];
+                dst[2 * t + 1] = im[t];
+            }
+            before *= filter->stages[i].decimation;
+        }
+    }
+    if (hipMalloc(reinterpret_cast<void **>(&s->d_hist),
+                  (size_t)s->max_captures * K * kLevelBins * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&s->d_ctaps), ctaps.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(s->d_ctaps, ctaps.data(), ctaps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: device allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return false;
+    }
+    p.hist = s->d_hist;
+    return true;
+}
+
 ookd_survey *ookd_survey_create_carriers(int32_t hip_device, const ookd_filter *filter, uint32_t flags,
                                          uint32_t max_captures, void *stream, const ookd_tune *tunes,
                                          uint32_t num_carriers, uint32_t stride) {
@@ -312,9 +359,9 @@ ookd_survey *ookd_survey_create_carriers(int32_t hip_device, const ookd_filter *
                   "OOKD_SURVEY_MAX_*");
     clear_error();
     const uint32_t both = OOKD_RX_SAMPLES_CS8 | OOKD_RX_SAMPLES_CU8;
-    if ((flags & ~(both | OOKD_RX_EXACT_FIR)) || (flags & both) == both) {
-        set_error("%s: flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8, with or without OOKD_RX_EXACT_FIR",
-                  who);
+    if ((flags & ~(both | OOKD_RX_EXACT_FIR | OOKD_RX_TUNED_FIR2)) || (flags & both) == both) {
+        set_error("%s: flags must be 0, OOKD_RX_SAMPLES_CS8 or OOKD_RX_SAMPLES_CU8, with or without OOKD_RX_EXACT_FIR "
+                  "and OOKD_RX_TUNED_FIR2", who);
         return nullptr;
     }
     if (num_carriers == 0 || num_carriers > OOKD_SURVEY_MAX_CARRIERS) {
@@ -356,7 +403,18 @@ ookd_survey *ookd_survey_create_carriers(int32_t hip_device, const ookd_filter *
     const bool exact = (flags & OOKD_RX_EXACT_FIR) != 0;
     const bool multi = !exact && filter->stages.size() == 1 && filter->stages[0].decimation == 1 &&
                        filter->stages[0].taps.size() <= 256u;
-    if (!multi && stride != 1) {
+    // OOKD_RX_TUNED_FIR2 asks for the fused two-stage form where the shape has one (the front end's shape test); on
+    // every other shape and beside OOKD_RX_EXACT_FIR it has no effect, as on an rx context
+    bool fir2 = false;
+    if ((flags & OOKD_RX_TUNED_FIR2) && !exact && filter->stages.size() == 2) {
+        FirStageDev st[2] = {};
+        for (int i = 0; i < 2; ++i) {
+            st[i].decim = filter->stages[i].decimation;
+            st[i].ntaps = filter->stages[i].taps.size() > 0xffffu ? 0xffffu : (uint32_t)filter->stages[i].taps.size();
+        }
+        fir2 = tuned_fir2_shape(st, 2);
+    }
+    if (!multi && !fir2 && stride != 1) {
         set_error("%s: stride %u needs the OOKD_SURVEY_TUNED_MULTI form: 1 stage, decimation 1, at most 256 taps, no "
                   "OOKD_RX_EXACT_FIR; every other survey counts every output (stride 1)", who, stride);
         return nullptr;
@@ -367,6 +425,7 @@ ookd_survey *ookd_survey_create_carriers(int32_t hip_device, const ookd_filter *
     s->stride = stride;
     s->tune_nu = tunes[0].nu != 0.0 ? tunes[0].nu : 0.0;
     s->total_decim = filter->total_decimation;
+    if (fir2) return survey_carriers_fir2(who, s, filter, tunes) ? s.release() : nullptr;
     if (!multi) {
         // the tuned contract's generic form, carrier by carrier (nu = 0: the untuned survey, the same counts)
         s->form = OOKD_SURVEY_TUNED_GENERIC;
@@ -468,7 +527,10 @@ int ookd_survey_device(ookd_survey *s, const void *d_iq, uint32_t num_captures, 
     s->kernel_ms = 0.0f;
     bool ok = hipMemsetAsync(s->d_hist, 0, hist_bytes, s->stream) == hipSuccess;
     ok = ok && hipEventRecord(s->t0, s->stream) == hipSuccess;
-    if (s->form == OOKD_SURVEY_TUNED_MULTI)
+    if (s->form == OOKD_SURVEY_TUNED_MULTI_FIR2)
+        ok = ok && launch_survey_tuned_multi_fir2(p, s->d_ctaps, num_captures, s->num_carriers, s->stride,
+                                                  samples_per_capture, s->fir2_thin, s->stream) == hipSuccess;
+    else if (s->form == OOKD_SURVEY_TUNED_MULTI)
         ok = ok && launch_survey_tuned_multi(p, s->d_ctaps, num_captures, s->num_carriers, s->stride, s->stream) == hipSuccess;
     else if (s->form == OOKD_SURVEY_TUNED_FIR1)
         ok = ok && launch_survey_tuned_fir1(p, s->d_ctaps, num_captures, s->fir1_R, s->fir1_waves, s->stream) == hipSuccess;
