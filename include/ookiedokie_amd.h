@@ -267,7 +267,13 @@ typedef struct ookd_rx_config {
     uint32_t segment_buffers;       /* buffers per FSM segment, 0 = default   */
     uint32_t message_slots;         /* per segment, 0 = default               */
     uint64_t message_capacity;      /* messages per run, 0 = default (65536)  */
-    void *stream;                   /* hipStream_t to launch on, NULL = own   */
+    void *stream;                   /* hipStream_t to launch on, NULL = own.  A run reads its capture in
+                                       the stream's order: work queued on the caller's stream before
+                                       ookd_rx_submit_device (the copy or kernel that produces the
+                                       capture) is finished when the run reads it, and the buffer may be
+                                       overwritten once ookd_rx_wait has returned.  A context's own stream
+                                       is non-blocking and waits for nobody: synchronise the producer
+                                       before submitting to it.                                        */
     uint64_t pipeline_chunk_samples;/* non-zero: single-capture runs at least twice this long are
                                        pipelined in chunks of about this many input samples: the front
                                        end of chunk c+1 is queued beside the edges / state machine of
@@ -531,7 +537,15 @@ int ookd_rx_process_device(ookd_rx *rx, const void *d_iq,
  * results are in host memory.  One run in flight per context -- use two
  * contexts (each has its own stream) to let the memory-bound front end of
  * one capture overlap the latency-bound state machine of the previous one.
- * ookd_rx_process_device == submit + wait. */
+ * ookd_rx_process_device == submit + wait.
+ *
+ * After a wait that fails (OOKD_ERR_CAPACITY: an edge, message or error list
+ * too small for the run) the context is usable: nothing is in flight any more
+ * -- a second wait fails with "nothing was submitted" --, the failed run has
+ * no results, and the next submit is accepted and decodes as on a context
+ * that never failed.  Contexts that share the failed one's gate are not
+ * affected.  One context belongs to one host thread at a time; contexts that
+ * share a gate may be driven from different host threads. */
 int ookd_rx_submit_device(ookd_rx *rx, const void *d_iq,
                           uint32_t num_captures,
                           uint64_t samples_per_capture,

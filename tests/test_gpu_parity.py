@@ -814,34 +814,9 @@ def test_batch_with_one_refused_capture_redoes_only_that_one(ok, oracle, walk):
     batch the other captures keep the scan's results; the refused one is redone alone in the round form
     and merged in, in capture order -- messages, payloads and error counts per capture as the oracle's."""
     import torch
-    us = RATE // 1000000
-    sh = dict(bits=36, start=500, first=8700, pulse=500, gap0=2000, gap1=4000)
-
-    def message(bits, deep_at=None):
-        runs = [sh["start"] * us, sh["first"] * us]
-        for i, bit in enumerate(bits):
-            gap = (sh["gap1"] if bit else sh["gap0"]) * us
-            runs.append(sh["pulse"] * us)
-            if i == deep_at:
-                pre = []
-                for _ in range(6):
-                    pre += [150, 90]                    # low 150, glitch 90: ends long before any bit window opens
-                runs += pre + [gap - sum(pre)]
-            else:
-                runs.append(gap)
-        return runs + [sh["pulse"] * us, 20000]
-
-    rng = np.random.default_rng(9)
-    def capture(deep):
-        runs = [5000]
-        for m in range(6):
-            bits = rng.integers(0, 2, size=sh["bits"])
-            ones = [i for i, b in enumerate(bits) if b]
-            runs += message(bits, deep_at=(ones[len(ones) // 2] if (deep and m == 2 and ones) else None))
-        return _iq_from_stream(stream_from_runs(runs))
-
-    caps = [capture(False), capture(True), _iq_from_stream(stream_from_runs(_glitchy_message_runs("p3l-nexa2012", 5, seed=5))),
-            capture(False)]
+    from tests.in_flight_inputs import p3l_message_captures
+    plain0, deep, plain1 = p3l_message_captures((False, True, False))      # (the builder lives beside the in-flight captures)
+    caps = [plain0, deep, _iq_from_stream(stream_from_runs(_glitchy_message_runs("p3l-nexa2012", 5, seed=5))), plain1]
     n = max(c.size // 2 for c in caps)
     stride = n + 8
     host = np.zeros((len(caps), 2 * stride), dtype=np.int16)
