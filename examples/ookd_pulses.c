@@ -10,16 +10,19 @@
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
  * ookd_pulses <capture.sc16q11|.cs8|.cu8> <filter.json|none> [--threshold <amplitude>] [--tune <hz>] [--rate <hz>]
- *             [--suggest-device <file.json>]
+ *             [--min-on-us <us>] [--min-off-us <us>] [--suggest-device <file.json>]
  *
  *   --threshold  slicer level, default 0.1 (ookd_scan's stderr names one per carrier)
  *   --tune       carrier offset in Hz (needs a filter), default 0
  *   --rate       sample rate of the capture, default 3000000; the table's microseconds and --tune depend on it
+ *   --min-on-us, --min-off-us  drop glitches first: "on" / "off" runs shorter than this many microseconds are deleted
+ *                from the edge list on the GPU (ookd_rx_clean_edges; --rate and the filter's decimation turn them into
+ *                decimated samples), and the table and --suggest-device read the cleaned list.  Default 0: nothing
  *   --suggest-device  the fourth question, which device: count the capture's pulse/gap symbols and the distances
  *                between its sync symbols (ookd_rx_symbol_survey, on the GPU), print the device ookd_suggest_coding and
  *                ookd_suggest_device make of them and write it as a device JSON -- or say why there is none
  *
- * stdout: one line with the edge count and the two open runs, then per level ("on", "off") one line per class:
+ * stdout: with a minimum, one line on what the cleaning deleted; then one line with the edge count and the two open runs, then per level ("on", "off") one line per class:
  * runs, mean length in decimated samples and in microseconds, and the range of lengths its bins cover.  With
  * --suggest-device one more line: the suggested device, or the reason for none.
  */
@@ -49,8 +52,10 @@ static const char *reason_text(uint32_t reason)
 }
 
 /* symbols -> coding -> frames -> device; prints it and writes the JSON.  0 when the file was written. */
-static int suggest_device(ookd_rx *rx, const ookd_pulse_suggestion *sug, double out_rate, const char *path)
+static int suggest_device(ookd_rx *rx, int clean, const ookd_pulse_suggestion *sug, double out_rate, const char *path)
 {
+    int (*const symbol_survey)(ookd_rx *, uint32_t, const ookd_symbol_table *, const ookd_symbol_roles *,
+                               ookd_symbol_survey *) = clean ? ookd_rx_symbol_survey_clean : ookd_rx_symbol_survey;
     static ookd_symbol_table table;
     static ookd_symbol_roles roles;
     static ookd_symbol_survey survey;
@@ -58,9 +63,9 @@ static int suggest_device(ookd_rx *rx, const ookd_pulse_suggestion *sug, double 
     ookd_coding coding;
     ookd_device_suggestion dev;
     if (ookd_symbol_table_from_pulses(sug, &table) != 0) return fail("ookd_symbol_table_from_pulses");
-    if (ookd_rx_symbol_survey(rx, 0, &table, NULL, &survey) != 0) return fail("ookd_rx_symbol_survey");
+    if (symbol_survey(rx, 0, &table, NULL, &survey) != 0) return fail("ookd_rx_symbol_survey");
     if (ookd_suggest_coding(sug, &survey, &roles, &coding) != 0) return fail("ookd_suggest_coding");
-    if (coding.found && ookd_rx_symbol_survey(rx, 0, &table, &roles, &survey) != 0) return fail("ookd_rx_symbol_survey");
+    if (coding.found && symbol_survey(rx, 0, &table, &roles, &survey) != 0) return fail("ookd_rx_symbol_survey");
     if (ookd_suggest_device(sug, &survey, &coding, out_rate, &dev) != 0) return fail("ookd_suggest_device");
     if (!dev.found) {
         printf("no device suggested: %s\n", reason_text(dev.reason));
@@ -86,7 +91,7 @@ static int suggest_device(ookd_rx *rx, const ookd_pulse_suggestion *sug, double 
 
 int main(int argc, char **argv)
 {
-    double threshold = 0.1, tune_hz = 0.0, rate = 3000000.0;
+    double threshold = 0.1, tune_hz = 0.0, rate = 3000000.0, min_on_us = 0.0, min_off_us = 0.0;
     const char *suggest_path = NULL;
     int bad = argc < 3;
     for (int i = 3; i < argc && !bad; i += 2) {
@@ -94,12 +99,15 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--threshold")) threshold = strtod(argv[i + 1], NULL);
         else if (!strcmp(argv[i], "--tune")) tune_hz = strtod(argv[i + 1], NULL);
         else if (!strcmp(argv[i], "--rate")) rate = strtod(argv[i + 1], NULL);
+        else if (!strcmp(argv[i], "--min-on-us")) min_on_us = strtod(argv[i + 1], NULL);
+        else if (!strcmp(argv[i], "--min-off-us")) min_off_us = strtod(argv[i + 1], NULL);
         else if (!strcmp(argv[i], "--suggest-device")) suggest_path = argv[i + 1];
         else bad = 1;
     }
-    if (bad || !(rate > 0.0) || !(threshold > 0.0)) {
+    if (bad || !(rate > 0.0) || !(threshold > 0.0) || !(min_on_us >= 0.0) || !(min_off_us >= 0.0)) {
         fprintf(stderr, "usage: %s <capture.sc16q11|.cs8|.cu8> <filter.json|none> [--threshold <amplitude>] "
-                        "[--tune <hz>] [--rate <hz>] [--suggest-device <file.json>]\n", argv[0]);
+                        "[--tune <hz>] [--rate <hz>] [--min-on-us <us>] [--min-off-us <us>] [--suggest-device <file.json>]\n",
+                argv[0]);
         return EXIT_FAILURE;
     }
     int status = EXIT_FAILURE;
@@ -144,8 +152,18 @@ int main(int argc, char **argv)
     rx = ookd_rx_create_tuned(&rc, filter, NULL /* no device: edges only */, &tune);
     if (!rx) { fail("ookd_rx_create_tuned"); goto out; }
     if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }
-    if (ookd_rx_pulse_hist(rx, 0, &hist) != 0) { fail("ookd_rx_pulse_hist"); goto out; }
     const double out_rate = rate / (double) decimation;     /* the rate the state machine sees (main.c:683) */
+    const uint64_t min_on = (uint64_t) (min_on_us * 1e-6 * out_rate), min_off = (uint64_t) (min_off_us * 1e-6 * out_rate);
+    const int clean = min_on > 1 || min_off > 1;
+    if (clean) {
+        ookd_clean_info info;
+        if (ookd_rx_clean_edges(rx, min_on, min_off) != 0) { fail("ookd_rx_clean_edges"); goto out; }
+        if (ookd_rx_get_clean_info(rx, 0, &info) != 0) { fail("ookd_rx_get_clean_info"); goto out; }
+        printf("cleaned: on-runs under %llu and off-runs under %llu samples deleted, %llu and %llu of them; %llu of %llu "
+               "edges stay\n", (unsigned long long) min_on, (unsigned long long) min_off, (unsigned long long) info.deleted[1],
+               (unsigned long long) info.deleted[0], (unsigned long long) info.edges_out, (unsigned long long) info.edges_in);
+    }
+    if ((clean ? ookd_rx_pulse_hist_clean : ookd_rx_pulse_hist)(rx, 0, &hist) != 0) { fail("ookd_rx_pulse_hist"); goto out; }
     if (ookd_suggest_pulses(&hist, out_rate, &sug) != 0) { fail("ookd_suggest_pulses"); goto out; }
 
     printf("%llu edges in %llu samples at %.6g Hz; before the first edge %llu samples, after the last %llu (%s)\n",
@@ -163,7 +181,7 @@ int main(int argc, char **argv)
         if (sug.dropped_runs[level])
             printf("  %llu runs in further classes not listed\n", (unsigned long long) sug.dropped_runs[level]);
     }
-    status = suggest_path ? suggest_device(rx, &sug, out_rate, suggest_path) : EXIT_SUCCESS;
+    status = suggest_path ? suggest_device(rx, clean, &sug, out_rate, suggest_path) : EXIT_SUCCESS;
 
 out:
     ookd_rx_destroy(rx);

@@ -1284,6 +1284,87 @@ ookd_device *ookd_device_from_suggestion(const ookd_device_suggestion *s, uint32
 size_t ookd_device_suggestion_json(const ookd_device_suggestion *s, const char *name, char *buf, size_t size);
 
 /* ------------------------------------------------------------------------
+ * Edge cleaning: drop glitch runs before the surveys.  Both surveys above take
+ * the edge list as it is: a one-sample glitch is a class of its own, splits the
+ * run it sits in and puts a symbol of its own between two frames.  One more
+ * by-product pass over the finished run's edge list deletes the runs shorter
+ * than a caller-given length and leaves a second, cleaned list in HBM; the
+ * survey kernels read that list unchanged (ookd_rx_pulse_hist_clean,
+ * ookd_rx_symbol_survey_clean).  A run nobody asks about stays what it was:
+ * the run's own list, ookd_rx_get_edges, ookd_rx_pulse_hist,
+ * ookd_rx_symbol_survey, the decoder and every result of the run are untouched.
+ *
+ * The rule, a contract.  Take capture (or carrier) c of the last run.  Take its
+ * edge list e[0..E) and the closed runs of the pulse survey's contract.  Run i,
+ * 0 <= i < E - 1, has length L_i = e[i+1] - e[i].  It is "on" when i is even.
+ *
+ * Two lengths are given in decimated samples: min_on and min_off (uint64).  0
+ * and 1 mean "keep every run of that level".
+ *
+ *   - short(i) = L_i < min[level(i)].  The comparison is strict.
+ *   - d(-1) = 0, and d(i) = short(i) && !d(i-1).  A deleted run takes its two
+ *     edges with it.  Its neighbours and the run itself merge into one run.  The
+ *     run after it no longer exists on its own and cannot be deleted again.
+ *   - Edge i is dropped iff d(i) (for i < E - 1) or d(i-1) (for i >= 1).
+ *   - The cleaned list is the kept edges in order.
+ *   - The two open runs (before e[0], after e[E-1]) are never short.  n_out is
+ *     unchanged.
+ *
+ * An equivalent parallel form: inside a maximal chain of consecutive short runs
+ * starting at run a, d(i) = ((i - a) even).  A chatter burst of m short runs
+ * vanishes entirely when m is odd.  It leaves exactly its last edge when m is
+ * even.
+ *
+ * Consequences: the number of dropped edges is even, so E & 1 (the tail level)
+ * and "the first edge rises" survive; no closed run of the cleaned list is
+ * shorter than the minimum of its level; cleaning a cleaned list with the same
+ * minimums changes nothing; min_on, min_off <= 1 returns the list itself.
+ *
+ * ookd_clean_edges is the rule in pure host code (no GPU needed), for hosts that
+ * already hold an edge list.  It follows the ookd_rx_get_edges convention:
+ * *num_out receives the cleaned list's length whatever the capacity, and at most
+ * `capacity` edges are stored when out != NULL.  OOKD_ERR_ARG for edges == NULL
+ * with E != 0.
+ *
+ * ookd_rx_clean_edges cleans ALL captures (carriers) of the last run in one
+ * timed pass of three dependent kernel launches on the context's stream.  A
+ * repeated call with the same minimums on the same run launches nothing; other
+ * minimums recompute, and what the two clean readers kept is forgotten.  The
+ * cleaned list, its prefix and the pass's work space are allocated by the first
+ * call in the life of the context, sized by the run's num_edges, grown and never
+ * shrunk, and freed with the context.  It refuses what ookd_rx_pulse_hist
+ * refuses, with the same codes and messages: no finished run, a shard run, a
+ * pipelined run, an overflowed list.  A run of no samples is valid and launches
+ * nothing.
+ *
+ * ookd_rx_get_clean_info, ookd_rx_get_clean_edges (the ookd_rx_get_edges
+ * convention), ookd_rx_pulse_hist_clean and ookd_rx_symbol_survey_clean answer
+ * from the cleaned list of the LAST run: OOKD_ERR_ARG "no cleaned list of the
+ * last run" when ookd_rx_clean_edges has not answered it.  The two clean readers
+ * take the arguments of the originals, run the originals' kernels over the
+ * cleaned list and keep the originals' contracts, with "its edge list" read as
+ * "its cleaned edge list"; their times are not reported separately.
+ * ---------------------------------------------------------------------- */
+typedef struct ookd_clean_info {
+    uint64_t edges_in, edges_out;   /* E before and after                        */
+    uint64_t deleted[2];            /* [level]: runs deleted, 1 = "on"           */
+    uint64_t min_on, min_off;       /* as given                                  */
+} ookd_clean_info;
+int ookd_clean_edges(const uint64_t *edges, uint64_t E, uint64_t min_on, uint64_t min_off,
+                     uint64_t *out, uint64_t capacity, uint64_t *num_out);
+int ookd_rx_clean_edges(ookd_rx *rx, uint64_t min_on, uint64_t min_off);
+int ookd_rx_get_clean_info(const ookd_rx *rx, uint32_t capture, ookd_clean_info *out);
+int ookd_rx_get_clean_edges(const ookd_rx *rx, uint32_t capture, uint64_t *edges, uint64_t capacity,
+                            uint64_t *num_edges);
+int ookd_rx_pulse_hist_clean(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out);
+int ookd_rx_symbol_survey_clean(ookd_rx *rx, uint32_t capture, const ookd_symbol_table *table,
+                                const ookd_symbol_roles *roles /* may be NULL */, ookd_symbol_survey *out);
+/* HIP-event time of the pass that cleaned the last run's lists: the zeroing of
+ * the counts and the three kernels.  0 while ookd_rx_clean_edges has not answered
+ * the last run (also when the call was refused, or the run had no samples). */
+float ookd_rx_clean_kernel_ms(const ookd_rx *rx);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

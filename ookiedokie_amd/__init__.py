@@ -22,6 +22,8 @@ here                              reference (OOKiedokie ``src/``)
 ``suggest_pulses``                a device file's states name (devices/README.md)
 ``Receiver.suggest_device`` /     nothing: writes that device file's state
 ``Device.from_suggestion``        machine for a sync + distance-coded remote
+``Receiver.clean_edges`` /        nothing: drops glitch runs from the edge list
+``clean_edges``                   before the two surveys read it
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -234,6 +236,11 @@ class PulseSuggestion(C.Structure):
                 ("dropped_runs", C.c_uint64 * 2), ("classes", (PulseClass * PULSE_MAX_CLASSES) * 2)]
 
 
+class CleanInfo(C.Structure):
+    _fields_ = [("edges_in", C.c_uint64), ("edges_out", C.c_uint64), ("deleted", C.c_uint64 * 2),
+                ("min_on", C.c_uint64), ("min_off", C.c_uint64)]
+
+
 class SymbolTable(C.Structure):
     _fields_ = [("num_classes", C.c_uint32 * 2), ("lower", (C.c_uint64 * SYMBOL_MAX_CLASSES) * 2),
                 ("upper", (C.c_uint64 * SYMBOL_MAX_CLASSES) * 2)]
@@ -402,6 +409,15 @@ _PROTOTYPES = {
                                       C.POINTER(Coding)]),
     "ookd_suggest_device": (C.c_int, [C.POINTER(PulseSuggestion), C.POINTER(SymbolSurvey), C.POINTER(Coding), C.c_double,
                                       C.POINTER(DeviceSuggestion)]),
+    "ookd_clean_edges": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.POINTER(C.c_uint64)]),
+    "ookd_rx_clean_edges": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "ookd_rx_get_clean_info": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CleanInfo)]),
+    "ookd_rx_get_clean_edges": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_pulse_hist_clean": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(PulseHist)]),
+    "ookd_rx_symbol_survey_clean": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SymbolTable), C.POINTER(SymbolRoles),
+                                              C.POINTER(SymbolSurvey)]),
+    "ookd_rx_clean_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_device_from_suggestion": (C.c_void_p, [C.POINTER(DeviceSuggestion), C.c_uint32]),
     "ookd_device_suggestion_json": (C.c_size_t, [C.POINTER(DeviceSuggestion), C.c_char_p, C.c_char_p, C.c_size_t]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
@@ -965,11 +981,13 @@ class Receiver:
         n = self.stats()["decimated_samples"]
         return np.unpackbits(words[:nw].view(np.uint8), bitorder="little")[:n]
 
-    def edges(self, capture: int = 0) -> np.ndarray:
+    def edges(self, capture: int = 0, clean: bool = False) -> np.ndarray:
+        """The capture's edge list; clean=True: its cleaned list (`clean_edges` first)."""
+        get = lib().ookd_rx_get_clean_edges if clean else lib().ookd_rx_get_edges
         n = C.c_uint64(0)
-        _check(lib().ookd_rx_get_edges(self._h, capture, None, 0, C.byref(n)))
+        _check(get(self._h, capture, None, 0, C.byref(n)))
         out = np.zeros(max(n.value, 1), dtype=np.uint64)
-        _check(lib().ookd_rx_get_edges(self._h, capture, out.ctypes.data, n.value, C.byref(n)))
+        _check(get(self._h, capture, out.ctypes.data, n.value, C.byref(n)))
         return out[:n.value]
 
     def fir_output(self, capture: int = 0) -> np.ndarray:
@@ -1007,14 +1025,36 @@ class Receiver:
         _check(lib().ookd_rx_get_errors(self._h, out.ctypes.data, cap, C.byref(n)))
         return out[:min(cap, n.value)], int(n.value)
 
+    # -- edge cleaning ---------------------------------------------------------------
+    def clean_edges(self, min_on: int = 0, min_off: int = 0) -> List[dict]:
+        """Deletes the runs shorter than min_on ("on" runs) / min_off ("off" runs) decimated samples from every
+        capture's (carrier's) edge list of the last run, on the GPU, into a second list (ookd_rx_clean_edges; the rule
+        is `clean_edges` at module level).  0 and 1 keep every run of that level.  The run's own list and results stay
+        what they were; `edges`, `pulse_hist` and `symbol_survey` read the cleaned list with clean=True.  Returns per
+        capture edges_in, edges_out, deleted ([off runs, on runs]), min_on, min_off."""
+        _check(lib().ookd_rx_clean_edges(self._h, int(min_on), int(min_off)))
+        out = []
+        info = CleanInfo()
+        # (the call above answered the last run: the first refusal is the capture behind the run's last)
+        while lib().ookd_rx_get_clean_info(self._h, len(out), C.byref(info)) == 0:
+            out.append(dict(edges_in=int(info.edges_in), edges_out=int(info.edges_out),
+                            deleted=[int(info.deleted[0]), int(info.deleted[1])], min_on=int(info.min_on),
+                            min_off=int(info.min_off)))
+        return out
+
+    @property
+    def clean_kernel_ms(self) -> float:
+        """HIP-event time of the pass behind `clean_edges` for the last run; 0 while nobody has asked for it."""
+        return float(lib().ookd_rx_clean_kernel_ms(self._h))
+
     # -- pulse survey ----------------------------------------------------------------
-    def pulse_hist(self, capture: int = 0) -> dict:
+    def pulse_hist(self, capture: int = 0, clean: bool = False) -> dict:
         """Run-length histograms of one capture (or carrier) of the last run (ookd_rx_pulse_hist): `count` and `sum`
         as uint64 arrays [2, 512] indexed [level, bin] (level 1 = "on" runs), `runs` [2], and the scalars num_edges,
         samples, open_head, open_tail, tail_level.  Computed on the GPU for all captures at the first call after a
-        run.  Feed it to `suggest_pulses`."""
+        run.  Feed it to `suggest_pulses`.  clean=True: of the cleaned list (`clean_edges` first)."""
         h = PulseHist()
-        _check(lib().ookd_rx_pulse_hist(self._h, capture, C.byref(h)))
+        _check((lib().ookd_rx_pulse_hist_clean if clean else lib().ookd_rx_pulse_hist)(self._h, capture, C.byref(h)))
         return _pulse_hist_dict(h)
 
     @property
@@ -1023,12 +1063,13 @@ class Receiver:
         return float(lib().ookd_rx_pulse_kernel_ms(self._h))
 
     # -- symbol survey ---------------------------------------------------------------
-    def symbol_survey(self, table, roles=None, capture: int = 0) -> dict:
+    def symbol_survey(self, table, roles=None, capture: int = 0, clean: bool = False) -> dict:
         """Pulse/gap symbols of one capture (or carrier) of the last run, counted on the GPU at every call
         (ookd_rx_symbol_survey).  `table` is a class table (`symbol_table_from_pulses`, or a dict with `lower` and
         `upper`: per level -- 0 = off, 1 = on -- a list of inclusive bounds); `roles` a uint8 array [17, 17] indexed
         [on class, off class] (`suggest_coding` makes one), or None for the kind counts alone.  Returns num_symbols,
-        kinds (uint64 [17, 17]), num_syncs, head_symbols, tail_symbols and frames (uint64 [2, 512], [clean, distance])."""
+        kinds (uint64 [17, 17]), num_syncs, head_symbols, tail_symbols and frames (uint64 [2, 512], [clean, distance]).
+        clean=True: of the cleaned list (`clean_edges` first)."""
         t = _symbol_table_struct(table)
         r = None
         if roles is not None:
@@ -1038,8 +1079,8 @@ class Receiver:
             r = SymbolRoles()
             C.memmove(r.role, a.ctypes.data, a.nbytes)
         out = SymbolSurvey()
-        _check(lib().ookd_rx_symbol_survey(self._h, capture, C.byref(t), C.byref(r) if r is not None else None,
-                                           C.byref(out)))
+        survey = lib().ookd_rx_symbol_survey_clean if clean else lib().ookd_rx_symbol_survey
+        _check(survey(self._h, capture, C.byref(t), C.byref(r) if r is not None else None, C.byref(out)))
         return _symbol_survey_dict(out)
 
     @property
@@ -1047,14 +1088,18 @@ class Receiver:
         """HIP-event time of the last `symbol_survey` call's pass; 0 when it was refused or had nothing to launch."""
         return float(lib().ookd_rx_symbol_kernel_ms(self._h))
 
-    def suggest_device(self, sample_rate: float, capture: int = 0) -> dict:
+    def suggest_device(self, sample_rate: float, capture: int = 0, min_on: int = 0, min_off: int = 0) -> dict:
         """The whole chain for one capture of the last run: pulse_hist -> suggest_pulses -> class table -> kind
         counts -> suggest_coding -> frames -> `suggest_device`'s dict (found = 0 with a reason when the capture does
-        not look like a sync + distance-coded device).  sample_rate is that of the decimated samples."""
-        pulses = suggest_pulses(self.pulse_hist(capture), sample_rate)
+        not look like a sync + distance-coded device).  sample_rate is that of the decimated samples.  With min_on or
+        min_off above 1 the list is cleaned first (`clean_edges`) and the chain runs on the cleaned list."""
+        clean = min_on > 1 or min_off > 1
+        if clean:
+            self.clean_edges(min_on, min_off)
+        pulses = suggest_pulses(self.pulse_hist(capture, clean), sample_rate)
         table = symbol_table_from_pulses(pulses)
-        coding = suggest_coding(pulses, self.symbol_survey(table, None, capture))
-        survey = self.symbol_survey(table, coding["roles"], capture) if coding["found"] else \
+        coding = suggest_coding(pulses, self.symbol_survey(table, None, capture, clean))
+        survey = self.symbol_survey(table, coding["roles"], capture, clean) if coding["found"] else \
             dict(num_syncs=0, frames=np.zeros((2, FRAME_BINS), dtype=np.uint64))
         return suggest_device(pulses, survey, coding, sample_rate)
 
@@ -1068,6 +1113,20 @@ class Receiver:
             self.close()
         except Exception:
             pass
+
+
+# --------------------------------------------------------------------------
+# edge cleaning
+
+def clean_edges(edges, min_on: int, min_off: int) -> np.ndarray:
+    """ookd_clean_edges: an edge list without its runs shorter than min_on ("on" runs: the first, third, ...) /
+    min_off ("off" runs) -- d(i) = short(i) and not d(i - 1); a deleted run takes its two edges with it.  Pure host code."""
+    e = np.ascontiguousarray(edges, dtype=np.uint64)
+    out = np.zeros(max(e.size, 1), dtype=np.uint64)
+    n = C.c_uint64(0)
+    _check(lib().ookd_clean_edges(e.ctypes.data if e.size else None, e.size, int(min_on), int(min_off), out.ctypes.data,
+                                  e.size, C.byref(n)))
+    return out[:n.value]
 
 
 # --------------------------------------------------------------------------

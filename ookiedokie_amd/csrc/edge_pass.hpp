@@ -50,7 +50,15 @@ struct EdgePass {
             const std::function<hipError_t(unsigned long long *)> &queue);
 };
 
-enum EdgePassId { kEdgePassPulse = 0, kEdgePassSymbol = 1, kEdgePasses = 2 };
+// kEdgePassClean writes the cleaned list (clean.cpp); the two after it are the surveys' passes over that list
+enum EdgePassId {
+    kEdgePassPulse = 0,
+    kEdgePassSymbol = 1,
+    kEdgePassClean = 2,
+    kEdgePassCleanPulse = 3,
+    kEdgePassCleanSymbol = 4,
+    kEdgePasses = 5
+};
 
 // The refusals every reader shares, after its own argument checks: fills `run`, then OOKD_OK, or OOKD_ERR_ARG (no
 // finished run, a shard run, a pipelined run, capture out of range) or OOKD_ERR_CAPACITY (the list overflowed) + error.

@@ -5,6 +5,7 @@
 #include <new>
 #include <vector>
 
+#include "clean.hpp"
 #include "pulses.hpp"
 
 using namespace ookd;
@@ -30,32 +31,25 @@ struct ClassAcc {
 
 double to_us(double x, double rate) { return rate > 0.0 ? x / rate * 1e6 : 0.0; }
 
-}  // namespace
-
-extern "C" {
-
-uint32_t ookd_pulse_bin(uint64_t length) { return pulse_bin_of(length); }
-
-uint64_t ookd_pulse_bin_lower(uint32_t bin) {
-    if (bin < 32u) return bin;
-    const uint64_t m = 16u + (bin - 32u) % 16u;         // five significant bits
-    const uint32_t sh = 1u + (bin - 32u) / 16u;
-    return sh > 59u ? UINT64_MAX : m << sh;
-}
-
-int ookd_rx_pulse_hist(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
+// ookd_rx_pulse_hist (clean = false: the run's own edge list, pass kEdgePassPulse) and ookd_rx_pulse_hist_clean (the
+// cleaned list, pass kEdgePassCleanPulse): the same kernel and the same contract over an EdgeListView of either
+int pulse_hist(const char *who, bool clean, ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
     clear_error();
     if (!rx || !out) {
-        set_error("ookd_rx_pulse_hist: NULL argument");
+        set_error("%s: NULL argument", who);
         return OOKD_ERR_ARG;
     }
     EdgeRun run;
-    if (const int rc = edge_run_check("ookd_rx_pulse_hist", rx, capture, run); rc != OOKD_OK) return rc;
-    std::unique_ptr<EdgePass> &slot = ookd_rx_edge_pass(rx, kEdgePassPulse);
+    if (const int rc = edge_run_check(who, rx, capture, run); rc != OOKD_OK) return rc;
+    if (clean && !clean_run_view(rx, run)) {
+        set_error("%s: no cleaned list of the last run (ookd_rx_clean_edges first)", who);
+        return OOKD_ERR_ARG;
+    }
+    std::unique_ptr<EdgePass> &slot = ookd_rx_edge_pass(rx, clean ? kEdgePassCleanPulse : kEdgePassPulse);
     if (!slot) slot.reset(new (std::nothrow) PulseCtx());
     PulseCtx *ctx = static_cast<PulseCtx *>(slot.get());
     if (!ctx) {
-        set_error("ookd_rx_pulse_hist: out of memory");
+        set_error("%s: out of memory", who);
         return OOKD_ERR_NOMEM;
     }
     if (ctx->serial != run.serial) {    // one launch for all captures of the run; ctx->host keeps them until the next run
@@ -64,7 +58,7 @@ int ookd_rx_pulse_hist(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
             ctx->serial = run.serial;
             ctx->kernel_ms = 0.0f;
         } else {
-            const int rc = ctx->run("ookd_rx_pulse_hist", run, ctx->host.size(), ctx->host.data(), [&](unsigned long long *d) {
+            const int rc = ctx->run(who, run, ctx->host.size(), ctx->host.data(), [&](unsigned long long *d) {
                 return launch_pulse_hist(PulseParams{edge_list_view(run), d}, run.num_edges, run.stream);
             });
             if (rc != OOKD_OK) return rc;
@@ -86,6 +80,27 @@ int ookd_rx_pulse_hist(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
     out->open_tail = E ? run.n_out - r[kPulseMetaWord + 2] : 0;
     out->tail_level = (uint32_t)(E & 1u);
     return OOKD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t ookd_pulse_bin(uint64_t length) { return pulse_bin_of(length); }
+
+uint64_t ookd_pulse_bin_lower(uint32_t bin) {
+    if (bin < 32u) return bin;
+    const uint64_t m = 16u + (bin - 32u) % 16u;         // five significant bits
+    const uint32_t sh = 1u + (bin - 32u) / 16u;
+    return sh > 59u ? UINT64_MAX : m << sh;
+}
+
+int ookd_rx_pulse_hist(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
+    return pulse_hist("ookd_rx_pulse_hist", false, rx, capture, out);
+}
+
+int ookd_rx_pulse_hist_clean(ookd_rx *rx, uint32_t capture, ookd_pulse_hist *out) {
+    return pulse_hist("ookd_rx_pulse_hist_clean", true, rx, capture, out);
 }
 
 float ookd_rx_pulse_kernel_ms(const ookd_rx *rx) { return edge_pass_kernel_ms(rx, kEdgePassPulse); }

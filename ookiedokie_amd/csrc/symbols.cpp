@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "clean.hpp"
 #include "symbols.hpp"
 
 using namespace ookd;
@@ -45,19 +46,20 @@ bool table_ok(const ookd_symbol_table &t) {
     return true;
 }
 
-// the capture's pass: d_agg / d_carry on the first call, then the kernels' parameters and the timed sequence
-int compute(SymbolCtx &c, const EdgeRun &run, uint32_t capture, const ookd_symbol_table &table,
-            const ookd_symbol_roles *roles, std::vector<uint64_t> &host) {
+// the capture's pass: d_agg / d_carry on the first call, then the kernels' parameters and the timed sequence.
+// list_capacity: the edges the context's own list holds -- a cleaned list is never longer
+int compute(const char *who, SymbolCtx &c, const EdgeRun &run, uint64_t list_capacity, uint32_t capture,
+            const ookd_symbol_table &table, const ookd_symbol_roles *roles, std::vector<uint64_t> &host) {
     if (!c.d_agg) {
         if (hipSetDevice(run.dev) != hipSuccess) {
-            set_error("ookd_rx_symbol_survey: hipSetDevice failed");
+            set_error("%s: hipSetDevice failed", who);
             return OOKD_ERR_HIP;
         }
-        const uint32_t tiles = std::max<uint32_t>(sym_tiles_of(run.edge_capacity), 1u);
+        const uint32_t tiles = std::max<uint32_t>(sym_tiles_of(list_capacity), 1u);
         bool ok = hipMalloc(reinterpret_cast<void **>(&c.d_agg), (size_t)tiles * sizeof(SymAgg)) == hipSuccess;
         ok = ok && hipMalloc(reinterpret_cast<void **>(&c.d_carry), (size_t)tiles * sizeof(SymCarry)) == hipSuccess;
         if (!ok) {
-            set_error("ookd_rx_symbol_survey: device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+            set_error("%s: device allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
             if (c.d_agg) (void)hipFree(c.d_agg);
             c.d_agg = nullptr;
             c.d_carry = nullptr;
@@ -79,10 +81,74 @@ int compute(SymbolCtx &c, const EdgeRun &run, uint32_t capture, const ookd_symbo
         }
     }
     if (roles) memcpy(p.role, roles->role, kSymKinds);
-    return c.run("ookd_rx_symbol_survey", run, host.size(), host.data(), [&](unsigned long long *d_result) {
+    return c.run(who, run, host.size(), host.data(), [&](unsigned long long *d_result) {
         p.result = d_result;
         return launch_symbol_survey(p, roles != nullptr, run.num_edges, run.stream);
     });
+}
+
+// ookd_rx_symbol_survey (clean = false: the run's own edge list, pass kEdgePassSymbol) and ookd_rx_symbol_survey_clean
+// (the cleaned list, pass kEdgePassCleanSymbol): the same kernels and the same contract over an EdgeListView of either
+int symbol_survey(const char *who, bool clean, ookd_rx *rx, uint32_t capture, const ookd_symbol_table *table,
+                  const ookd_symbol_roles *roles, ookd_symbol_survey *out) {
+    const EdgePassId id = clean ? kEdgePassCleanSymbol : kEdgePassSymbol;
+    clear_error();
+    if (!table || !out) {
+        set_error("%s: NULL argument", who);
+        return OOKD_ERR_ARG;
+    }
+    if (rx) {                   // whatever happens below, the last call's time is no finished pass's
+        if (EdgePass *c = ookd_rx_edge_pass(rx, id).get()) {
+            c->serial = 0;
+            c->kernel_ms = 0.0f;
+        }
+    }
+    // the table and the roles first: they are judged without a context (and without a GPU)
+    if (!table_ok(*table)) {
+        set_error("%s: the class table needs at most %u ranges per level, lower <= upper, ascending and disjoint", who,
+                  kSymClasses);
+        return OOKD_ERR_ARG;
+    }
+    if (roles) {
+        for (uint32_t i = 0; i < kSymKinds; ++i) {
+            if ((&roles->role[0][0])[i] > OOKD_ROLE_ONE) {
+                set_error("%s: role %u of kind (%u, %u)", who, (&roles->role[0][0])[i], i / kSymSide, i % kSymSide);
+                return OOKD_ERR_ARG;
+            }
+        }
+    }
+    if (!rx) {
+        set_error("%s: NULL argument", who);
+        return OOKD_ERR_ARG;
+    }
+    EdgeRun run;
+    if (const int rc = edge_run_check(who, rx, capture, run); rc != OOKD_OK) return rc;
+    const uint64_t list_capacity = run.edge_capacity;
+    if (clean && !clean_run_view(rx, run)) {
+        set_error("%s: no cleaned list of the last run (ookd_rx_clean_edges first)", who);
+        return OOKD_ERR_ARG;
+    }
+    memset(out, 0, sizeof *out);
+    if (run.n_out == 0) return OOKD_OK;         // no buffer was processed: nothing was written for the kernels to read
+    std::unique_ptr<EdgePass> &slot = ookd_rx_edge_pass(rx, id);
+    if (!slot) slot.reset(new (std::nothrow) SymbolCtx());
+    SymbolCtx *ctx = static_cast<SymbolCtx *>(slot.get());
+    if (!ctx) {
+        set_error("%s: out of memory", who);
+        return OOKD_ERR_NOMEM;
+    }
+    std::vector<uint64_t> host(kSymWords, 0);
+    const int rc = compute(who, *ctx, run, list_capacity, capture, *table, roles, host);
+    if (rc != OOKD_OK) return rc;
+    out->num_symbols = host[kSymWordS];
+    memcpy(out->kinds, host.data() + kSymWordKinds, sizeof out->kinds);
+    if (roles) {
+        out->num_syncs = host[kSymWordSyncs];
+        out->head_symbols = host[kSymWordSyncs + 1];
+        out->tail_symbols = host[kSymWordSyncs + 2];
+        memcpy(out->frames, host.data() + kSymWordFrames, sizeof out->frames);
+    }
+    return OOKD_OK;
 }
 
 struct Kind {
@@ -168,58 +234,12 @@ int ookd_symbol_table_from_pulses(const ookd_pulse_suggestion *pulses, ookd_symb
 
 int ookd_rx_symbol_survey(ookd_rx *rx, uint32_t capture, const ookd_symbol_table *table, const ookd_symbol_roles *roles,
                           ookd_symbol_survey *out) {
-    clear_error();
-    if (!table || !out) {
-        set_error("ookd_rx_symbol_survey: NULL argument");
-        return OOKD_ERR_ARG;
-    }
-    if (rx) {                   // whatever happens below, the last call's time is no finished pass's
-        if (EdgePass *c = ookd_rx_edge_pass(rx, kEdgePassSymbol).get()) {
-            c->serial = 0;
-            c->kernel_ms = 0.0f;
-        }
-    }
-    // the table and the roles first: they are judged without a context (and without a GPU)
-    if (!table_ok(*table)) {
-        set_error("ookd_rx_symbol_survey: the class table needs at most %u ranges per level, lower <= upper, ascending "
-                  "and disjoint", kSymClasses);
-        return OOKD_ERR_ARG;
-    }
-    if (roles) {
-        for (uint32_t i = 0; i < kSymKinds; ++i) {
-            if ((&roles->role[0][0])[i] > OOKD_ROLE_ONE) {
-                set_error("ookd_rx_symbol_survey: role %u of kind (%u, %u)", (&roles->role[0][0])[i], i / kSymSide, i % kSymSide);
-                return OOKD_ERR_ARG;
-            }
-        }
-    }
-    if (!rx) {
-        set_error("ookd_rx_symbol_survey: NULL argument");
-        return OOKD_ERR_ARG;
-    }
-    EdgeRun run;
-    if (const int rc = edge_run_check("ookd_rx_symbol_survey", rx, capture, run); rc != OOKD_OK) return rc;
-    memset(out, 0, sizeof *out);
-    if (run.n_out == 0) return OOKD_OK;         // no buffer was processed: nothing was written for the kernels to read
-    std::unique_ptr<EdgePass> &slot = ookd_rx_edge_pass(rx, kEdgePassSymbol);
-    if (!slot) slot.reset(new (std::nothrow) SymbolCtx());
-    SymbolCtx *ctx = static_cast<SymbolCtx *>(slot.get());
-    if (!ctx) {
-        set_error("ookd_rx_symbol_survey: out of memory");
-        return OOKD_ERR_NOMEM;
-    }
-    std::vector<uint64_t> host(kSymWords, 0);
-    const int rc = compute(*ctx, run, capture, *table, roles, host);
-    if (rc != OOKD_OK) return rc;
-    out->num_symbols = host[kSymWordS];
-    memcpy(out->kinds, host.data() + kSymWordKinds, sizeof out->kinds);
-    if (roles) {
-        out->num_syncs = host[kSymWordSyncs];
-        out->head_symbols = host[kSymWordSyncs + 1];
-        out->tail_symbols = host[kSymWordSyncs + 2];
-        memcpy(out->frames, host.data() + kSymWordFrames, sizeof out->frames);
-    }
-    return OOKD_OK;
+    return symbol_survey("ookd_rx_symbol_survey", false, rx, capture, table, roles, out);
+}
+
+int ookd_rx_symbol_survey_clean(ookd_rx *rx, uint32_t capture, const ookd_symbol_table *table, const ookd_symbol_roles *roles,
+                                ookd_symbol_survey *out) {
+    return symbol_survey("ookd_rx_symbol_survey_clean", true, rx, capture, table, roles, out);
 }
 
 float ookd_rx_symbol_kernel_ms(const ookd_rx *rx) { return edge_pass_kernel_ms(rx, kEdgePassSymbol); }
