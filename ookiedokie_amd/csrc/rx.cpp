@@ -1294,7 +1294,10 @@ int ookd_rx::collect_results() {
             if (rc != OOKD_OK) return rc;
             rc = run_state_machine(pending_first_valid ? &pending_first : nullptr, true);
             if (rc != OOKD_OK) return rc;
-            return fetch_results();
+            rc = fetch_results();
+            // (the second pass zeroed it: say why this run composed, as a pipelined run that was redone whole does)
+            if (rc == OOKD_OK && stats.fsm_fallback_reason == 0) stats.fsm_fallback_reason = kScanFbSync;
+            return rc;
         } else if (h_hdr->edge_overflow) {
             // refused because the edge list overflowed: there is nothing to run the rounds on (blk_offset counts
             // edges that were never written); reported below
