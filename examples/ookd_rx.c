@@ -10,8 +10,8 @@
  *   gcc -std=c99 -Wall -Iinclude examples/ookd_rx.c -o ookd_rx \
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
- * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none>
- *         <samplerate> [csv|pretty] [dig.csv]
+ * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>]
+ *         <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]
  *
  * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
  * it is; `auto` surveys the capture's envelope levels first (ookd_survey_*, ookd_suggest_threshold), reports
@@ -26,6 +26,11 @@
  * --tune auto: one spectrum pass over the capture finds the carriers (ookd_spectrum_*, ookd_suggest_carriers);
  * every one is reported on stderr and the context is tuned to the strongest that is not the peak at DC.  Without
  * such a carrier a line says so and the decode is untuned.
+ *
+ * --min-on-us, --min-off-us: debounce.  "on" / "off" runs shorter than this many microseconds are deleted from the
+ * edge list on the GPU as part of the run and the state machine decodes the cleaned list (ookd_rx_set_debounce; the
+ * sample rate and the filter's decimation turn them into decimated samples, as in ookd_pulses): a glitch in front of
+ * a message no longer costs the message.  The dig file stays the raw stream's.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,7 +49,7 @@ int main(int argc, char **argv)
     /* --threshold <value>|auto is taken out of argv; what is left is positional, as before */
     float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
     int threshold_auto = 0, tune_auto = 0, bad_option = 0;
-    double tune_hz = 0.0;
+    double tune_hz = 0.0, min_on_us = 0.0, min_off_us = 0.0;
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--threshold")) {
@@ -61,14 +66,21 @@ int main(int argc, char **argv)
             tune_auto = 0;
             tune_hz = strtod(argv[i], &end);
             if (end == argv[i] || *end != '\0') { bad_option = 1; break; }
+        } else if (!strcmp(argv[i], "--min-on-us") || !strcmp(argv[i], "--min-off-us")) {
+            char *end = NULL;
+            double *us = !strcmp(argv[i], "--min-on-us") ? &min_on_us : &min_off_us;
+            if (++i >= argc) { bad_option = 1; break; }
+            *us = strtod(argv[i], &end);
+            if (end == argv[i] || *end != '\0' || !(*us >= 0.0)) { bad_option = 1; break; }
         } else {
             argv[kept++] = argv[i];
         }
     }
     argc = kept;
     if (argc < 5 || bad_option) {
-        fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] <capture.sc16q11|.cs8|.cu8> <device.json> "
-                        "<filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n", argv[0]);
+        fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] "
+                        "<capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
+                argv[0]);
         return EXIT_FAILURE;
     }
     if (threshold_auto && (tune_auto || tune_hz != 0.0)) {
@@ -179,6 +191,14 @@ int main(int argc, char **argv)
     tune.nu = rate ? tune_hz / (double) rate : 0.0;     /* cycles per input sample; 0 = ookd_rx_create */
     rx = ookd_rx_create_tuned(&rc, filter, device, &tune);
     if (!rx) { fail("ookd_rx_create_tuned"); goto out; }
+    {
+        const double out_rate = (double) rate / (double) decimation;    /* the rate the state machine sees */
+        const uint64_t min_on = (uint64_t) (min_on_us * 1e-6 * out_rate), min_off = (uint64_t) (min_off_us * 1e-6 * out_rate);
+        if ((min_on > 1 || min_off > 1) && ookd_rx_set_debounce(rx, min_on, min_off) != 0) {
+            fail("ookd_rx_set_debounce");
+            goto out;
+        }
+    }
 
     if (ookd_rx_process_device(rx, d_iq, 1, n, n) != 0) { fail("ookd_rx_process_device"); goto out; }
 
@@ -198,9 +218,15 @@ int main(int argc, char **argv)
 
     ookd_rx_stats st;
     if (ookd_rx_get_stats(rx, &st) == 0) {
+        ookd_clean_info ci;
         fprintf(stderr, "%llu samples, %llu edges, %llu messages, front end %.3f ms\n",
                 (unsigned long long) st.input_samples, (unsigned long long) st.num_edges,
                 (unsigned long long) st.num_messages, st.fir_kernel_ms);
+        if (ookd_rx_get_clean_info(rx, 0, &ci) == 0) {      /* a debounced run: its cleaned list exists */
+            fprintf(stderr, "debounce %llu / %llu samples: %llu pulses and %llu gaps deleted, %llu edges decoded\n",
+                    (unsigned long long) ci.min_on, (unsigned long long) ci.min_off, (unsigned long long) ci.deleted[1],
+                    (unsigned long long) ci.deleted[0], (unsigned long long) ci.edges_out);
+        }
     }
     status = EXIT_SUCCESS;
 

@@ -1365,6 +1365,76 @@ int ookd_rx_symbol_survey_clean(ookd_rx *rx, uint32_t capture, const ookd_symbol
 float ookd_rx_clean_kernel_ms(const ookd_rx *rx);
 
 /* ------------------------------------------------------------------------
+ * Debounced decode: the state machine on the cleaned edge list.  Opt-in, per
+ * context.  With a minimum above 1 set, EVERY run of the context cleans its edge
+ * list on the GPU as part of the run's chain -- the three kernels of the pass
+ * above and a fourth that makes the cleaned list's prefix over blocks of 4096
+ * outputs -- and the state machine decodes the cleaned list: the scan in all its
+ * forms, the round form, and the redo of the captures the scan refused.
+ *
+ * min_on, min_off are in decimated samples and follow the clean rule: a run is
+ * short when its length is < the minimum of its level (strict), 0 and 1 keep
+ * every run of that level.  Both <= 1 turns the debounce off: the context then
+ * queues exactly the launches it queued before this call existed, and gives the
+ * same results.
+ *
+ * What the decoder sees, a contract.  Take capture (or carrier) c of the run, its
+ * edge list e, and the bit stream painted over n_out decimated samples from
+ * ookd_clean_edges(e, min_on, min_off): level 0 before the first edge, toggling
+ * at every edge.  Messages, payloads, every error position and num_errors of c
+ * are those of the reference state machine fed that stream buffer by buffer
+ * (samples_per_buffer / total decimation samples each).  ookd_message.sample
+ * keeps its meaning.
+ *
+ * What stays the run's own: ookd_rx_get_bits, the dig recorders, ookd_rx_get_fir,
+ * ookd_rx_get_edges, ookd_rx_pulse_hist, ookd_rx_symbol_survey and
+ * ookd_rx_stats.num_edges are the raw stream's.  edge_capacity bounds the raw
+ * list, and an edge overflow fails the run as before.
+ *
+ * The list made in the chain IS the context's cleaned list of that run:
+ * ookd_rx_get_clean_edges, ookd_rx_get_clean_info, ookd_rx_pulse_hist_clean and
+ * ookd_rx_symbol_survey_clean answer from it without any ookd_rx_clean_edges
+ * call, ookd_rx_clean_edges with the same minimums launches nothing, and with
+ * other minimums it recomputes the list for the readers only (the run's results
+ * are final).  ookd_rx_clean_kernel_ms stays 0: the pass is part of the chain and
+ * inside ookd_rx_stats.total_device_ms.  The per-capture counts are fetched by
+ * the first call that asks for them, not by the run.
+ *
+ * Nothing between the front end and the state machine waits for the host: the
+ * pass is queued on the context's stream with its grids sized by edge_capacity,
+ * so ookd_rx_submit_device / ookd_rx_wait and several contexts in flight work as
+ * they did.  Batched runs and carrier contexts work (carriers are captures).  A
+ * context without a device makes the cleaned list and runs no state machine.
+ *
+ * Refused or changed: a debounced context never pipelines a capture in chunks
+ * (it behaves as with OOKD_RX_NO_PIPELINE; stats.pipeline_chunks is 0), and
+ * ookd_rx_shard_begin / ookd_rx_shard_refine return OOKD_ERR_ARG naming the
+ * debounce: chunk-local lists and the level carried into a shard are outside the
+ * clean rule, as they are for ookd_rx_clean_edges.
+ *
+ * ookd_rx_set_debounce may be called between runs (it takes effect with the
+ * next); OOKD_ERR_ARG while a run is in flight (submitted, not waited for) and
+ * for rx == NULL.  The first call with a minimum above 1 allocates what the
+ * chain needs -- the cleaned list, the per-block prefix and the pass's work
+ * space -- sized by the context's edge_capacity and max_captures.  When that
+ * fails the call returns OOKD_ERR_NOMEM and leaves the debounce OFF (0, 0),
+ * whatever it was.  Where the call has to replace the buffers of an earlier
+ * ookd_rx_clean_edges (a context that was cleaned by hand first), the last
+ * run's cleaned list goes with them: the clean readers answer "no cleaned list
+ * of the last run" until the next run or the next ookd_rx_clean_edges.
+ * ookd_rx_get_debounce returns the minimums as set (either pointer may be NULL).
+ *
+ * The per-capture counts of a debounced run are fetched by the first of
+ * ookd_rx_get_clean_info, ookd_rx_get_clean_edges, ookd_rx_pulse_hist_clean and
+ * ookd_rx_symbol_survey_clean after it: that call does one blocking copy from
+ * the device and, although two of them take a const context, updates the
+ * context.  Like every call on a context they must not run concurrently with
+ * one another on the same context.
+ * ---------------------------------------------------------------------- */
+int ookd_rx_set_debounce(ookd_rx *rx, uint64_t min_on, uint64_t min_off);
+int ookd_rx_get_debounce(const ookd_rx *rx, uint64_t *min_on, uint64_t *min_off);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

@@ -24,6 +24,8 @@ here                              reference (OOKiedokie ``src/``)
 ``Device.from_suggestion``        machine for a sync + distance-coded remote
 ``Receiver.clean_edges`` /        nothing: drops glitch runs from the edge list
 ``clean_edges``                   before the two surveys read it
+``Receiver(min_on=, min_off=)`` / nothing: the decoder itself on the cleaned
+``Receiver.set_debounce``         list, so a glitch no longer costs a message
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -418,6 +420,8 @@ _PROTOTYPES = {
     "ookd_rx_symbol_survey_clean": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SymbolTable), C.POINTER(SymbolRoles),
                                               C.POINTER(SymbolSurvey)]),
     "ookd_rx_clean_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_rx_set_debounce": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "ookd_rx_get_debounce": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ookd_device_from_suggestion": (C.c_void_p, [C.POINTER(DeviceSuggestion), C.c_uint32]),
     "ookd_device_suggestion_json": (C.c_size_t, [C.POINTER(DeviceSuggestion), C.c_char_p, C.c_char_p, C.c_size_t]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
@@ -770,7 +774,8 @@ class Receiver:
                  scan_tables: bool = False, sample_format: str = "sc16q11",
                  tune: Optional[float] = None, tune_hz: Optional[float] = None,
                  sample_rate: Optional[float] = None,
-                 carriers: Optional[Sequence] = None, tuned_fir2: bool = False):
+                 carriers: Optional[Sequence] = None, tuned_fir2: bool = False,
+                 min_on: int = 0, min_off: int = 0):
         """tune: carrier offset in cycles per input sample (|tune| <= 0.5), or tune_hz with sample_rate -- one
         of the two forms.  The context then filters with the taps `Filter.tuned_taps` returns (ookd_rx_create_tuned);
         0 is an untuned context.
@@ -782,7 +787,9 @@ class Receiver:
 
         tuned_fir2: a tuned or carrier context on a filter of two decimate-by-2 stages (<= 16 and <= 32 taps, the
         backend default fs128_fs16_dec4) runs the fused kernel FRONT_TUNED_FIR2 instead of FRONT_TUNED_GENERIC
-        (OOKD_RX_TUNED_FIR2): same bits, floats within err_valu.  Changes nothing for any other context."""
+        (OOKD_RX_TUNED_FIR2): same bits, floats within err_valu.  Changes nothing for any other context.
+
+        min_on, min_off: debounce, in decimated samples (`set_debounce`); 0 and 1 leave the context as it always was."""
         if carriers is not None and (tune is not None or tune_hz is not None):
             raise ValueError("carriers and tune / tune_hz are mutually exclusive: a carrier list names every nu")
         if tune is not None and (tune_hz is not None or sample_rate is not None):
@@ -840,6 +847,28 @@ class Receiver:
                                                  device._h if device else None, C.byref(t))
         if not self._h:
             raise OokdError(-4, last_error())
+        if int(min_on) > 1 or int(min_off) > 1:
+            try:
+                self.set_debounce(min_on, min_off)
+            except OokdError:
+                self.close()
+                raise
+
+    def set_debounce(self, min_on: int = 0, min_off: int = 0) -> None:
+        """From the next run on, every run cleans its edge list on the GPU in its chain (the `clean_edges` rule: "on" /
+        "off" runs shorter than min_on / min_off decimated samples go, 0 and 1 keep every run of that level) and the
+        state machine decodes the cleaned list (ookd_rx_set_debounce).  bits, edges(), the surveys and
+        stats()["num_edges"] stay the raw stream's; edges(c, clean=True) and the other clean readers answer from the
+        run's cleaned list without a `clean_edges` call.  Such a context never pipelines in chunks and refuses
+        shards.  Both <= 1: off.  Refused while a run is in flight."""
+        _check(lib().ookd_rx_set_debounce(self._h, int(min_on), int(min_off)))
+
+    @property
+    def debounce(self) -> Tuple[int, int]:
+        """(min_on, min_off) as set; (0, 0) for a context never given any."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ookd_rx_get_debounce(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     @property
     def tune(self) -> float:

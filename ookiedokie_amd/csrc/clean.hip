@@ -11,7 +11,12 @@
 // The recurrence as a scan: a short run maps the d in front of it to its negation, any other run maps it to 0.  Maps
 // of one bit compose associatively and there are four of them (const 0, const 1, id, not), two bits each
 // (clean.hpp: map_then), so lanes, waves, tiles and captures all scan the same way.
+//
+// A debounced context queues the same three launches in every run's chain and a fourth behind them,
+// clean_block_prefix_kernel: the cleaned list's prefix over the run's own blocks, which the state machine reads in the
+// place of the run's blk_offset.
 #include "clean.hpp"
+#include "kernels.hpp"     // kBlockShift: the edge stage's block
 
 namespace ookd {
 
@@ -354,6 +359,51 @@ __global__ __launch_bounds__(kCleanThreads) void clean_compact_kernel(CleanParam
     }
 }
 
+// ---- 4. (the debounced decode only) the cleaned list's prefix over the run's own blocks ------------------------
+//
+// One lane per block: a lower bound for b * 4096 inside the capture's cleaned range.  The cleaned edges in front of a
+// block are among the run's own in front of it, so the run's own prefix brackets the search from above.  Whatever the
+// lists hold, every load stays below out_capacity and every store below blk_prefix_capacity.
+__global__ __launch_bounds__(kCleanThreads) void clean_block_prefix_kernel(CleanParams p) {
+    const EdgeListView &list = p.list;
+    const uint64_t bpc = list.blocks_per_cap;
+    if (list.num_captures == 0u || bpc == 0u) return;
+    const uint64_t entries = (uint64_t)list.num_captures * bpc;     // and one more word: the total
+    const uint64_t raw_total = edge_list_total(list);
+    for (uint64_t i = (uint64_t)blockIdx.x * kCleanThreads + threadIdx.x; i <= entries; i += (uint64_t)gridDim.x * kCleanThreads) {
+        if (i >= p.blk_prefix_capacity) break;
+        const uint32_t c = (uint32_t)(i / bpc);
+        const uint64_t b = i - (uint64_t)c * bpc;
+        uint64_t lo = p.out_prefix[c];
+        if (lo > p.out_capacity) lo = p.out_capacity;
+        if (i == entries) {
+            p.blk_prefix[i] = (uint32_t)lo;
+            break;
+        }
+        uint64_t hi = p.out_prefix[c + 1u];
+        if (hi > p.out_capacity) hi = p.out_capacity;
+        if (hi < lo) hi = lo;
+        uint64_t raw_lo, raw_hi;
+        edge_list_range(list, c, raw_total, raw_lo, raw_hi);
+        uint64_t raw_b = list.blk_offset[i];
+        if (raw_b > raw_hi) raw_b = raw_hi;
+        if (raw_b < raw_lo) raw_b = raw_lo;
+        // first cleaned edge of the capture at or beyond the block's first output, among its first `n`
+        uint64_t j0 = 0u, n = hi - lo < raw_b - raw_lo ? hi - lo : raw_b - raw_lo;
+        const uint64_t at = b << kBlockShift;
+        while (n != 0u) {
+            const uint64_t half = n >> 1;
+            if (p.out[lo + j0 + half] < at) {
+                j0 += half + 1u;
+                n -= half + 1u;
+            } else {
+                n = half;
+            }
+        }
+        p.blk_prefix[i] = (uint32_t)(lo + j0);
+    }
+}
+
 hipError_t launch_clean_edges(const CleanParams &p, uint64_t expect_edges, hipStream_t stream) {
     uint64_t groups = clean_tiles_of(expect_edges, p.list.num_captures);
     if (groups > p.num_tiles_cap) groups = p.num_tiles_cap;
@@ -366,6 +416,14 @@ hipError_t launch_clean_edges(const CleanParams &p, uint64_t expect_edges, hipSt
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(clean_compact_kernel, dim3((uint32_t)groups), dim3(kCleanThreads), 0, stream, p);
+    e = hipGetLastError();
+    if (e != hipSuccess || !p.blk_prefix) return e;
+    uint64_t lanes = (uint64_t)p.list.num_captures * p.list.blocks_per_cap + 1u;
+    if (lanes > p.blk_prefix_capacity) lanes = p.blk_prefix_capacity;
+    groups = (lanes + kCleanThreads - 1u) / kCleanThreads;
+    if (groups < 1u) groups = 1u;
+    if (groups > kCleanMaxGroups) groups = kCleanMaxGroups;
+    hipLaunchKernelGGL(clean_block_prefix_kernel, dim3((uint32_t)groups), dim3(kCleanThreads), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -13,21 +13,7 @@ int EdgePass::run(const char *who, const EdgeRun &run, size_t words, uint64_t *h
                   const std::function<hipError_t(unsigned long long *)> &queue) {
     serial = 0;
     kernel_ms = 0.0f;
-    if (hipSetDevice(run.dev) != hipSuccess) {
-        set_error("%s: hipSetDevice failed", who);
-        return OOKD_ERR_HIP;
-    }
-    if (capacity < words) {
-        if (d_result) (void)hipFree(d_result);
-        d_result = nullptr;
-        capacity = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&d_result), words * 8) != hipSuccess) {
-            d_result = nullptr;
-            set_error("%s: device allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
-            return OOKD_ERR_NOMEM;
-        }
-        capacity = words;
-    }
+    if (const int rc = reserve_result(who, run.dev, words); rc != OOKD_OK) return rc;
     if (!t0 && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess)) {
         set_error("%s: hipEventCreate failed", who);
         return OOKD_ERR_HIP;
@@ -48,6 +34,25 @@ int EdgePass::run(const char *who, const EdgeRun &run, size_t words, uint64_t *h
         return OOKD_ERR_HIP;
     }
     serial = run.serial;
+    return OOKD_OK;
+}
+
+int EdgePass::reserve_result(const char *who, int dev, size_t words) {
+    if (hipSetDevice(dev) != hipSuccess) {
+        set_error("%s: hipSetDevice failed", who);
+        return OOKD_ERR_HIP;
+    }
+    if (capacity < words) {
+        if (d_result) (void)hipFree(d_result);
+        d_result = nullptr;
+        capacity = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&d_result), words * 8) != hipSuccess) {
+            d_result = nullptr;
+            set_error("%s: device allocation failed: %s", who, hipGetErrorString(hipGetLastError()));
+            return OOKD_ERR_NOMEM;
+        }
+        capacity = words;
+    }
     return OOKD_OK;
 }
 

@@ -48,6 +48,8 @@ struct EdgePass {
     // code + error with both zero.
     int run(const char *who, const EdgeRun &run, size_t words, uint64_t *host,
             const std::function<hipError_t(unsigned long long *)> &queue);
+    // d_result holds `words` words from here on (what run() does first; a pass queued in a run's chain reserves ahead)
+    int reserve_result(const char *who, int dev, size_t words);
 };
 
 // kEdgePassClean writes the cleaned list (clean.cpp); the two after it are the surveys' passes over that list

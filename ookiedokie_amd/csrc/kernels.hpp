@@ -31,6 +31,8 @@ constexpr int kGenTile = 1024;          // final outputs per workgroup, generic 
 constexpr int kGenTileMin = 64;         // ... and the smallest (one bit word): generic_tile() picks between them
 constexpr size_t kGenLdsBytes = 160 * 1024;     // LDS the generic kernels' level buffers may take
 constexpr int kBlockWords = 64;         // one edge block = 64 words = 4096 bits
+constexpr uint32_t kBlockShift = 12;    // log2 of its outputs: the block of a sample, of blk_offset and of a cleaned list's prefix
+static_assert((1u << kBlockShift) == (uint32_t)kBlockWords * 64u, "one edge block is 2^kBlockShift outputs");
 constexpr int kPayloadWords = 5;        // 4 x u64 payload + 1 spare (bit index == max_bits)
 // ---- front end -------------------------------------------------------------
 
@@ -346,6 +348,10 @@ struct FsmParams {
     uint32_t stamp_bits;
     const uint32_t *big;        // tables of a device with more than 64 states / triggers (see kMaxStatesBig), or null
     uint32_t big_words;
+    // set (a debounced context): `edges` / `blk_offset` are the cleaned list and its per-block prefix,
+    // and the level of a sample is the parity of the capture's cleaned edges at or below it -- the bit words and tile
+    // infos are the raw stream's, where a deleted glitch is still 1 and a deleted gap still 0 (fsm_level_at)
+    uint32_t level_from_list;
     // the edge stage's overflow flag (device): set = the list's tail was never written and blk_offset counts
     // edges that are not there -- the round-form kernels return at once (the host reports OOKD_ERR_CAPACITY)
     const uint32_t *edge_overflow;
@@ -353,6 +359,21 @@ struct FsmParams {
 
 // level of decimated sample `pos` of capture `cap` (pos may be -1 for a chunk: the sample in front of it)
 __device__ __forceinline__ uint32_t fsm_level_at(const FsmParams &p, uint32_t cap, int64_t pos) {
+    if (p.level_from_list) {
+        // the edges in front of pos's block by the prefix, and those of the block at or below pos by a search in it
+        if (pos < 0) return 0u;
+        const uint64_t blk0 = (uint64_t)cap * p.blocks_per_cap;
+        uint64_t b = (uint64_t)pos >> kBlockShift;
+        if (b >= p.blocks_per_cap) b = p.blocks_per_cap - 1u;
+        const uint32_t first = p.blk_offset[blk0];
+        uint32_t lo = p.blk_offset[blk0 + b], hi = p.blk_offset[blk0 + b + 1u];
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (p.edges[mid] <= (uint64_t)pos) lo = mid + 1u;
+            else hi = mid;
+        }
+        return (lo - first) & 1u;
+    }
     if (p.tile_info) {
         const int64_t tile = pos >> p.tile_shift;
         if (!tile_live(p.tile_info[(int64_t)cap * p.tiles_per_cap + tile], p.stamp_bits)) return 0u;

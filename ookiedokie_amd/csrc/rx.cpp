@@ -19,6 +19,7 @@
 #include "ingest.hpp"
 #include "kernels.hpp"
 #include "edge_pass.hpp"
+#include "clean.hpp"
 
 using namespace ookd;
 
@@ -456,6 +457,12 @@ struct ookd_rx : RxHandles {
     bool run_shard = false, run_overflow = false;
     bool run_edges_valid = false;   // collect_results has read this run's edge count: the prefix and the list are its own
     std::unique_ptr<EdgePass> edge_pass[kEdgePasses];   // each made by its reader's first call
+    // debounce (ookd_rx_set_debounce): with a minimum above 1 every run cleans its edge list in the
+    // chain (clean.hip) and the state machine reads the cleaned list and its per-block prefix in the place of the
+    // run's own -- fsm_params hands them out, and with them the scan, the round form and the redo of refused captures
+    uint64_t debounce_on = 0, debounce_off = 0;
+    CleanChainView debounce_view;       // the clean pass's buffers, allocated by the setter for the context's capacity
+    bool debounce() const { return debounce_on > 1 || debounce_off > 1; }
     uint32_t iter_next = 0;         // next FSM iteration number (parity continues)
     uint32_t final_parity = 0;
     ookd_rx_stats stats{};
@@ -558,6 +565,11 @@ struct ookd_rx : RxHandles {
             f.tiles_per_cap = (uint32_t)(run_words * 64 / tile_bits());
             f.tile_shift = (uint32_t)__builtin_ctz(tile_bits());
             f.stamp_bits = tile_stamp << kTileStampShift;
+        }
+        if (debounce()) {
+            f.edges = debounce_view.edges;
+            f.blk_offset = debounce_view.blk_prefix;
+            f.level_from_list = 1u;
         }
         return f;
     }
@@ -694,6 +706,7 @@ int ookd_rx::densify_bits() const {
 bool ookd_rx::plan_chunks() {
     chunks.clear();
     if (!pipe_ok || no_pipeline_once || run_caps != 1 || run_n_out == 0) return false;
+    if (debounce()) return false;       // (chunk-local lists and carried levels are not cleaned: as with pipeline = false)
     const uint64_t spb = cfg.samples_per_buffer;
     // boundary (decimated index) o: o % 4096 == 0 and o * D % spb == 0
     const uint64_t per_buf = spb / gcd64(spb, total_decim());
@@ -914,6 +927,12 @@ int ookd_rx::front_and_edges(const void *d_iq, uint64_t stride, const int16_t *d
         HIPCHK(launch_all());
     }
     if (run_n_out > 0) HIPCHK(launch_edges(edge_params(), stream));
+    if (debounce()) {
+        // the clean pass behind the edge stage, on the same stream: nothing here waits for the device
+        EdgeRun run;
+        ookd_rx_edge_run(this, &run);
+        HIPCHK(clean_chain_queue(this, run, debounce_on, debounce_off));
+    }
     return OOKD_OK;
 }
 
@@ -1977,6 +1996,11 @@ int ookd_rx_shard_begin(ookd_rx *rx, const void *d_iq, uint64_t num_samples, con
         set_error("ookd_rx_shard_begin: a carrier context runs whole captures, not shards");
         return OOKD_ERR_ARG;
     }
+    if (rx->debounce()) {
+        set_error("ookd_rx_shard_begin: the context has a debounce set (ookd_rx_set_debounce): the level in front of a "
+                  "shard is not known to the clean pass");
+        return OOKD_ERR_ARG;
+    }
     const uint64_t spb = rx->cfg.samples_per_buffer;
     const uint64_t align = spb / gcd64(spb, rx->total_decim()) * rx->total_decim();
     if (!last_shard && (num_samples % align) != 0) {
@@ -2037,6 +2061,10 @@ int ookd_rx_shard_refine(ookd_rx *rx, const ookd_fsm_state *state_in, ookd_fsm_s
         set_error("ookd_rx_shard_refine: a carrier context runs whole captures, not shards");
         return OOKD_ERR_ARG;
     }
+    if (rx->debounce()) {
+        set_error("ookd_rx_shard_refine: the context has a debounce set (ookd_rx_set_debounce): it runs no shards");
+        return OOKD_ERR_ARG;
+    }
     HIPCHK(hipSetDevice(rx->dev));
     if (!rx->have_fsm || rx->run_n_out == 0) {
         if (state_out) *state_out = *state_in;
@@ -2060,6 +2088,42 @@ int ookd_rx_shard_refine(ookd_rx *rx, const ookd_fsm_state *state_in, ookd_fsm_s
                                             : &rx->d_state_out.p[(size_t)rx->final_parity * nseg + (nseg - 1)];
         HIPCHK(hipMemcpy(state_out, &src->st, sizeof(FsmStateDev), hipMemcpyDeviceToHost));
     }
+    return OOKD_OK;
+}
+
+int ookd_rx_set_debounce(ookd_rx *rx, uint64_t min_on, uint64_t min_off) {
+    clear_error();
+    if (!rx) {
+        set_error("ookd_rx_set_debounce: NULL argument");
+        return OOKD_ERR_ARG;
+    }
+    if (rx->submitted) {
+        set_error("ookd_rx_set_debounce: a run is in flight (ookd_rx_wait first)");
+        return OOKD_ERR_ARG;
+    }
+    if (min_on > 1 || min_off > 1) {
+        // by what the context can hold, not by any run's edge count: nothing is allocated on a run's path
+        // (+ 64: as d_edges is allocated)
+        const int rc = clean_chain_reserve(rx, rx->dev, rx->edge_capacity + 64, rx->max_captures, rx->max_blocks, rx->debounce_view);
+        if (rc != OOKD_OK) {
+            // (a buffer of the chain may be gone: the context runs on without a debounce rather than on half of them)
+            rx->debounce_on = rx->debounce_off = 0;
+            return rc;
+        }
+    }
+    rx->debounce_on = min_on;
+    rx->debounce_off = min_off;
+    return OOKD_OK;
+}
+
+int ookd_rx_get_debounce(const ookd_rx *rx, uint64_t *min_on, uint64_t *min_off) {
+    clear_error();
+    if (!rx) {
+        set_error("ookd_rx_get_debounce: NULL argument");
+        return OOKD_ERR_ARG;
+    }
+    if (min_on) *min_on = rx->debounce_on;
+    if (min_off) *min_off = rx->debounce_off;
     return OOKD_OK;
 }
 
