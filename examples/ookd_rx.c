@@ -10,7 +10,7 @@
  *   gcc -std=c99 -Wall -Iinclude examples/ookd_rx.c -o ookd_rx \
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
- * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>]
+ * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] [--levels]
  *         <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]
  *
  * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
@@ -31,6 +31,11 @@
  * edge list on the GPU as part of the run and the state machine decodes the cleaned list (ookd_rx_set_debounce; the
  * sample rate and the filter's decimation turn them into decimated samples, as in ookd_pulses): a glitch in front of
  * a message no longer costs the message.  The dig file stays the raw stream's.
+ *
+ * --levels: after the messages, one line per message on stderr, `level <capture> <sample> <dBFS>`: the lower median of
+ * the peak powers of the message's last num_bits + 2 pulses (ookd_rx_get_run_peaks, ookd_message_levels) as
+ * 10 log10(power), 0 dBFS being a full-scale carrier.  Of the list the state machine decoded: the cleaned one when a
+ * debounce is on.  stdout is what it is without the option.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,11 +49,25 @@ static int fail(const char *what)
     return EXIT_FAILURE;
 }
 
+/* 10 log10(p) for p > 0 without libm (the build line above links none): p = m 2^e with m in [1, 2), and
+ * ln m = 2 atanh((m - 1) / (m + 1)) by its series: |y| <= 1/3, so 20 terms leave less than 3^-41 */
+static double decibel(double p)
+{
+    int e = 0;
+    while (p >= 2.0) { p *= 0.5; ++e; }
+    while (p < 1.0) { p *= 2.0; --e; }
+    const double y = (p - 1.0) / (p + 1.0), y2 = y * y;
+    double term = y, sum = 0.0;
+    for (int k = 1; k < 40; k += 2) { sum += term / k; term *= y2; }
+    const double ln2 = 0.69314718055994530942, ln10 = 2.30258509299404568402;
+    return 10.0 * (2.0 * sum + e * ln2) / ln10;
+}
+
 int main(int argc, char **argv)
 {
     /* --threshold <value>|auto is taken out of argv; what is left is positional, as before */
     float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
-    int threshold_auto = 0, tune_auto = 0, bad_option = 0;
+    int threshold_auto = 0, tune_auto = 0, bad_option = 0, levels = 0;
     double tune_hz = 0.0, min_on_us = 0.0, min_off_us = 0.0;
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
@@ -72,6 +91,8 @@ int main(int argc, char **argv)
             if (++i >= argc) { bad_option = 1; break; }
             *us = strtod(argv[i], &end);
             if (end == argv[i] || *end != '\0' || !(*us >= 0.0)) { bad_option = 1; break; }
+        } else if (!strcmp(argv[i], "--levels")) {
+            levels = 1;
         } else {
             argv[kept++] = argv[i];
         }
@@ -79,7 +100,7 @@ int main(int argc, char **argv)
     argc = kept;
     if (argc < 5 || bad_option) {
         fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] "
-                        "<capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
+                        "[--levels] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
                 argv[0]);
         return EXIT_FAILURE;
     }
@@ -112,6 +133,8 @@ int main(int argc, char **argv)
     ookd_survey *survey = NULL;
     ookd_spectrum *spectrum = NULL;
     char *text = NULL;
+    uint64_t *edges = NULL, *at = NULL;
+    float *peaks = NULL, *level = NULL;
 
     void *sdr = sdr_hip_file_init((const struct ookiedokie_cfg *)&cfg);   /* same layout: see ookd_host_cfg */
     if (!sdr) return fail("sdr_hip_file_init");
@@ -228,9 +251,47 @@ int main(int argc, char **argv)
                     (unsigned long long) ci.deleted[0], (unsigned long long) ci.edges_out);
         }
     }
+    if (levels && nmsg) {                   /* one more pass over the capture, which is still in HBM */
+        ookd_clean_info ci;
+        const int clean = ookd_rx_get_clean_info(rx, 0, &ci) == 0;
+        uint64_t ne = 0, nr = 0;
+        if ((clean ? ookd_rx_get_clean_edges(rx, 0, NULL, 0, &ne) : ookd_rx_get_edges(rx, 0, NULL, 0, &ne)) != 0) {
+            fail("ookd_rx_get_edges");
+            goto out;
+        }
+        if ((clean ? ookd_rx_get_run_peaks_clean(rx, 0, NULL, 0, &nr) : ookd_rx_get_run_peaks(rx, 0, NULL, 0, &nr)) != 0) {
+            fail("ookd_rx_get_run_peaks");
+            goto out;
+        }
+        edges = malloc((ne + 1) * sizeof *edges);
+        peaks = malloc((nr + 1) * sizeof *peaks);
+        at = malloc(nmsg * sizeof *at);
+        level = malloc(nmsg * sizeof *level);
+        if (!edges || !peaks || !at || !level) goto out;
+        if ((clean ? ookd_rx_get_clean_edges(rx, 0, edges, ne, &ne) : ookd_rx_get_edges(rx, 0, edges, ne, &ne)) != 0 ||
+            (clean ? ookd_rx_get_run_peaks_clean(rx, 0, peaks, nr, &nr) : ookd_rx_get_run_peaks(rx, 0, peaks, nr, &nr)) != 0) {
+            fail("ookd_rx_get_run_peaks");
+            goto out;
+        }
+        for (uint64_t m = 0; m < nmsg; ++m) at[m] = msgs[m].sample;
+        if (ookd_message_levels(edges, ne, peaks, nr, at, nmsg, ookd_device_num_bits(device) + 2, level) != 0) {
+            fail("ookd_message_levels");
+            goto out;
+        }
+        for (uint64_t m = 0; m < nmsg; ++m) {
+            if (level[m] > 0.0f)
+                fprintf(stderr, "level %u %llu %.2f\n", msgs[m].capture, (unsigned long long) at[m], decibel((double) level[m]));
+            else
+                fprintf(stderr, "level %u %llu -inf\n", msgs[m].capture, (unsigned long long) at[m]);
+        }
+    }
     status = EXIT_SUCCESS;
 
 out:
+    free(level);
+    free(at);
+    free(peaks);
+    free(edges);
     free(text);
     ookd_rx_destroy(rx);
     ookd_survey_destroy(survey);

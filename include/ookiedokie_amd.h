@@ -1435,6 +1435,98 @@ int ookd_rx_set_debounce(ookd_rx *rx, uint64_t min_on, uint64_t min_off);
 int ookd_rx_get_debounce(const ookd_rx *rx, uint64_t *min_on, uint64_t *min_off);
 
 /* ------------------------------------------------------------------------
+ * Pulse levels: the peak power of every on-run of the last run, and a level per
+ * message.  A decoded message says where and what, not how strong; two
+ * transmitters at different distances on one frequency differ in exactly that.
+ *
+ * The contract.  Take capture (or carrier) c of the context's last run, its edge
+ * list e[0..E) as ookd_rx_get_edges returns it and n_out =
+ * ookd_rx_stats.decimated_samples.
+ *   - On-run r, 0 <= r < R = ceil(E / 2), covers outputs [e[2r], f_r), f_r =
+ *     e[2r + 1], or n_out for an open last run.
+ *   - p_j is the power the slicer compares, restated by the context's kind:
+ *       untuned context   the survey contract at ookd_survey_create: unpack, FIR
+ *                         stages in the reference's order with a separately
+ *                         rounded multiply and add per tap, then re*re + im*im
+ *                         with three roundings;
+ *       tuned or carrier  the tuned survey contract at ookd_survey_create_tuned
+ *                         with that carrier's nu (nu = 0 included: the same
+ *                         powers as the untuned contract);
+ *       no filter         |x_j|^2.
+ *     The history in front of the capture is zero.  Inputs at or beyond the
+ *     run's n samples are zero and are never read from memory: the capture's
+ *     allocation may end at n.  p_j is therefore defined for every j < n_out,
+ *     the padding to whole buffers included -- where a capture that ends high
+ *     falls.  (An 8-bit capture is the SC16Q11 capture of 16 times its values.)
+ *   - peak[r] = max over the run's j of p_j, as a float.  Powers are not
+ *     negative, so the maximum of the bit patterns as uint32 is the maximum of
+ *     the values: the result is exact and independent of any order.
+ *   - hist is an ookd_level_hist of the R peaks under ookd_level_bin, samples = R.
+ *   - tile_outputs is the pass's tile; tiles_total = ceil(n_out / tile_outputs);
+ *     tiles_filtered counts the tiles [t tile, (t + 1) tile) that hold at least
+ *     one output of an on-run -- a function of the edge list, and the number of
+ *     tiles the kernel ran the filter on (it counts them itself).
+ *
+ * Like ookd_rx_pulse_hist the pass is a by-product of a finished run: a run
+ * nobody asks about launches and allocates nothing.  The first of these calls
+ * after a run makes one timed pass on the context's stream for all captures or
+ * carriers of the run (ookd_rx_levels_kernel_ms: its HIP-event time, 0 while
+ * nobody has asked or there was nothing to launch); later calls about the same
+ * run answer from what it left.  The calls refuse what ookd_rx_pulse_hist
+ * refuses, with the same codes: no finished run, a run in flight, a shard run, a
+ * pipelined run (OOKD_ERR_ARG), an overflowed edge list (OOKD_ERR_CAPACITY), a
+ * capture out of range.  A run of no samples is valid and launches nothing.  A
+ * filter whose history the pass's LDS window cannot hold (the one
+ * ookd_survey_create refuses) is refused at the first call with that message.
+ *
+ * The capture is read again, through the pointer and stride the context recorded
+ * at submit: the caller of ookd_rx_process_device / ookd_rx_submit_device keeps
+ * the capture resident and unchanged until the first of these calls about the
+ * run has returned.  After ookd_rx_process_host it is the context's own copy.
+ *
+ * The _clean forms read the cleaned list of the last run (ookd_rx_clean_edges,
+ * or a debounced context's own) in the place of the run's list: an on-run that
+ * swallowed a short off-run reports the maximum over its whole extent.  Each
+ * form keeps its own pass and time; ookd_rx_levels_kernel_ms is the raw list's.
+ * When ookd_rx_clean_edges makes another list for the same run (other
+ * minimums), the next _clean call makes a new pass over that list, as
+ * ookd_rx_pulse_hist_clean does.
+ *
+ * ookd_rx_get_run_peaks follows the ookd_rx_get_edges convention: *num_runs
+ * receives R, at most `capacity` peaks are stored, peaks may be NULL.
+ *
+ * Limits: the peak only, no mean; the levels of off-runs are the survey's
+ * business (ookd_survey_*); shard and pipelined runs are refused.
+ * ---------------------------------------------------------------------- */
+typedef struct ookd_run_levels {
+    uint64_t num_runs;              /* R                                      */
+    uint64_t tiles_total;
+    uint64_t tiles_filtered;
+    uint32_t tile_outputs;
+    uint32_t reserved;
+    ookd_level_hist hist;           /* of the R peaks                         */
+} ookd_run_levels;
+
+int ookd_rx_run_levels(ookd_rx *rx, uint32_t capture, ookd_run_levels *out);
+int ookd_rx_run_levels_clean(ookd_rx *rx, uint32_t capture, ookd_run_levels *out);
+int ookd_rx_get_run_peaks(ookd_rx *rx, uint32_t capture, float *peaks, uint64_t capacity,
+                          uint64_t *num_runs);
+int ookd_rx_get_run_peaks_clean(ookd_rx *rx, uint32_t capture, float *peaks, uint64_t capacity,
+                                uint64_t *num_runs);
+float ookd_rx_levels_kernel_ms(const ookd_rx *rx);
+
+/* A level per message, pure host code (no GPU).  edges[0..E) and peaks[0..R),
+ * R = ceil(E / 2), are one capture's; msg_samples[0..M) that capture's
+ * ookd_message.sample values, ascending.  Message m takes the on-runs whose
+ * rising edge is <= msg_samples[m] and > msg_samples[m - 1] (every run up to
+ * msg_samples[0] for the first message), of these the last `pulses`, and
+ * levels[m] is their lower median: element (count - 1) / 2 of the sorted peaks;
+ * 0 when there are none.  OOKD_ERR_ARG for a NULL array that is not empty,
+ * R != ceil(E / 2), msg_samples that descend, or pulses = 0. */
+int ookd_message_levels(const uint64_t *edges, uint64_t E, const float *peaks, uint64_t R,
+                        const uint64_t *msg_samples, uint64_t M, uint32_t pulses, float *levels);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

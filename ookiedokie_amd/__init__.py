@@ -26,6 +26,8 @@ here                              reference (OOKiedokie ``src/``)
 ``clean_edges``                   before the two surveys read it
 ``Receiver(min_on=, min_off=)`` / nothing: the decoder itself on the cleaned
 ``Receiver.set_debounce``         list, so a glitch no longer costs a message
+``Receiver.run_levels`` /         nothing: the peak power of every pulse and a
+``Receiver.message_levels``       signal level per decoded message
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -218,6 +220,11 @@ class SpectrumResult(C.Structure):
 class CarrierStruct(C.Structure):
     _fields_ = [("nu", C.c_double), ("bin", C.c_int32), ("at_dc", C.c_uint32), ("power", C.c_double),
                 ("ratio", C.c_double)]
+
+
+class RunLevels(C.Structure):
+    _fields_ = [("num_runs", C.c_uint64), ("tiles_total", C.c_uint64), ("tiles_filtered", C.c_uint64),
+                ("tile_outputs", C.c_uint32), ("reserved", C.c_uint32), ("hist", LevelHist)]
 
 
 class PulseHist(C.Structure):
@@ -422,6 +429,13 @@ _PROTOTYPES = {
     "ookd_rx_clean_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_rx_set_debounce": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "ookd_rx_get_debounce": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ookd_rx_run_levels": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RunLevels)]),
+    "ookd_rx_run_levels_clean": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RunLevels)]),
+    "ookd_rx_get_run_peaks": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_get_run_peaks_clean": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_levels_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_message_levels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                      C.c_void_p]),
     "ookd_device_from_suggestion": (C.c_void_p, [C.POINTER(DeviceSuggestion), C.c_uint32]),
     "ookd_device_suggestion_json": (C.c_size_t, [C.POINTER(DeviceSuggestion), C.c_char_p, C.c_char_p, C.c_size_t]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
@@ -1132,6 +1146,45 @@ class Receiver:
             dict(num_syncs=0, frames=np.zeros((2, FRAME_BINS), dtype=np.uint64))
         return suggest_device(pulses, survey, coding, sample_rate)
 
+    # -- pulse levels ----------------------------------------------------------------
+    def run_levels(self, capture: int = 0, clean: bool = False) -> dict:
+        """The peak power of every on-run of one capture (or carrier) of the last run (ookd_rx_run_levels): `peaks`
+        float32 [num_runs] -- run r begins at edge 2 r of `edges(capture, clean)` --, `hist` (uint64 [256], the peaks
+        under `level_bin`), num_runs, tile_outputs, tiles_total and tiles_filtered (the tiles that held an on sample:
+        the only ones the pass filtered).  Computed on the GPU for all captures at the first call after a run, from
+        the capture itself: a capture handed over as a device pointer stays resident and unchanged until then.
+        clean=True: over the cleaned list (`clean_edges` first, or a debounced context)."""
+        out = RunLevels()
+        _check((lib().ookd_rx_run_levels_clean if clean else lib().ookd_rx_run_levels)(self._h, capture, C.byref(out)))
+        peaks = np.zeros(max(int(out.num_runs), 1), dtype=np.float32)
+        n = C.c_uint64(0)
+        get = lib().ookd_rx_get_run_peaks_clean if clean else lib().ookd_rx_get_run_peaks
+        _check(get(self._h, capture, peaks.ctypes.data, int(out.num_runs), C.byref(n)))
+        return dict(num_runs=int(out.num_runs), tiles_total=int(out.tiles_total), tiles_filtered=int(out.tiles_filtered),
+                    tile_outputs=int(out.tile_outputs), hist=np.array(out.hist.bins, dtype=np.uint64),
+                    peaks=peaks[:int(n.value)])
+
+    def message_levels(self, result: RxResult, pulses: Optional[int] = None, clean: bool = False) -> np.ndarray:
+        """A power per message of `result` (this context's last run), float32 aligned with it: the lower median of the
+        peaks of the message's last `pulses` on-runs (`message_levels` at module level; pulses defaults to the
+        device's num_bits + 2).  10 log10 of it is the level in dBFS.  In a carrier context each message uses its
+        carrier's list."""
+        if pulses is None:
+            if self._device is None:
+                raise ValueError("pulses is needed on a context without a device")
+            pulses = self._device.num_bits + 2
+        out = np.zeros(len(result.msg_samples), dtype=np.float32)
+        for c in np.unique(result.captures):
+            m = np.nonzero(result.captures == c)[0]
+            lv = self.run_levels(int(c), clean)
+            out[m] = message_levels(self.edges(int(c), clean), lv["peaks"], result.msg_samples[m], pulses)
+        return out
+
+    @property
+    def levels_kernel_ms(self) -> float:
+        """HIP-event time of the pass behind `run_levels` for the last run; 0 while nobody has asked about it."""
+        return float(lib().ookd_rx_levels_kernel_ms(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_rx_destroy(self._h)
@@ -1156,6 +1209,22 @@ def clean_edges(edges, min_on: int, min_off: int) -> np.ndarray:
     _check(lib().ookd_clean_edges(e.ctypes.data if e.size else None, e.size, int(min_on), int(min_off), out.ctypes.data,
                                   e.size, C.byref(n)))
     return out[:n.value]
+
+
+# --------------------------------------------------------------------------
+# pulse levels
+
+def message_levels(edges, peaks, msg_samples, pulses: int) -> np.ndarray:
+    """ookd_message_levels: message m takes the on-runs whose rising edge is <= msg_samples[m] and beyond the message
+    before, of these the last `pulses`, and its level is the lower median of their peaks (0 without any).  One
+    capture's edges, peaks (`Receiver.run_levels`) and ascending message samples.  Pure host code."""
+    e = np.ascontiguousarray(edges, dtype=np.uint64)
+    p = np.ascontiguousarray(peaks, dtype=np.float32)
+    m = np.ascontiguousarray(msg_samples, dtype=np.uint64)
+    out = np.zeros(max(m.size, 1), dtype=np.float32)
+    _check(lib().ookd_message_levels(e.ctypes.data if e.size else None, e.size, p.ctypes.data if p.size else None, p.size,
+                                     m.ctypes.data if m.size else None, m.size, int(pulses), out.ctypes.data))
+    return out[:m.size]
 
 
 # --------------------------------------------------------------------------

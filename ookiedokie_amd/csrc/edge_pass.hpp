@@ -1,4 +1,4 @@
-// edge_pass.hpp -- what the surveys that read a finished run's edge list (pulses.cpp, symbols.cpp) have in common on the
+// edge_pass.hpp -- what the readers of a finished run's edge list (pulses.cpp, symbols.cpp, run_levels.cpp) have in common on the
 // host, and what they share with rx.cpp, the context whose edge list it is: the last run as a reader sees it, the
 // refusals, and the timed pass with its result buffer.  `who` names the entry point in the messages.  No device code:
 // the kernels' side is edge_list_dev.hpp.
@@ -59,7 +59,9 @@ enum EdgePassId {
     kEdgePassClean = 2,
     kEdgePassCleanPulse = 3,
     kEdgePassCleanSymbol = 4,
-    kEdgePasses = 5
+    kEdgePassLevels = 5,            // the pulse levels (run_levels.cpp) over the run's list, and over the cleaned one
+    kEdgePassCleanLevels = 6,
+    kEdgePasses = 7
 };
 
 // The refusals every reader shares, after its own argument checks: fills `run`, then OOKD_OK, or OOKD_ERR_ARG (no

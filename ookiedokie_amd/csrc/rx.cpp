@@ -19,6 +19,7 @@
 #include "ingest.hpp"
 #include "kernels.hpp"
 #include "edge_pass.hpp"
+#include "run_levels.hpp"
 #include "clean.hpp"
 
 using namespace ookd;
@@ -2182,6 +2183,14 @@ void ookd_rx_edge_run(const ookd_rx *rx, EdgeRun *out) {
 }
 
 std::unique_ptr<EdgePass> &ookd_rx_edge_pass(ookd_rx *rx, EdgePassId id) { return rx->edge_pass[id]; }
+
+// run_levels.hpp: what the pulse-level pass reads again of the last run
+void ookd_rx_level_source(const ookd_rx *rx, RunLevelSource *out) {
+    out->plan = &rx->front.plan;
+    out->iq = rx->last_iq;
+    out->stride = rx->last_stride;
+    out->n_valid = rx->run_n_valid;
+}
 
 extern "C" {
 
