@@ -1,8 +1,9 @@
 """The pulse levels' contract (include/ookiedokie_amd.h, "Pulse levels") restated in numpy, independent of the
 library: power + edge list -> the peak of every on-run, the tiles that hold an on output, and the level of a message.
 The power comes from tests.test_survey_host.oracle_power (untuned) or tests.tuned_survey_contract.contract_power
-(tuned), both over the capture zero padded to whole buffers.  Shared by tests/test_run_levels_host.py and
-tests/test_gpu_run_levels.py."""
+(tuned), both over the capture zero padded to whole buffers.  Shared by tests/test_run_levels_host.py,
+tests/test_gpu_run_levels.py and the two seam files (tests/test_run_level_seams_host.py,
+tests/test_gpu_run_level_seams.py), whose captures behind a filter are built here, on the reference's edges."""
 import numpy as np
 
 RATE = 3000000
@@ -22,6 +23,16 @@ def padded(iq, spb=SPB):
     out = np.zeros(2 * (-(-n // spb) * spb), dtype=iq.dtype)
     out[:iq.size] = iq
     return out
+
+
+def ref_edges(oracle, fir, iq, spb=SPB, thr=THR):
+    """the reference's edge list of a capture: its filter (None: the samples) and its threshold over the capture
+    zero padded to whole buffers"""
+    from tests.helpers import edges_of
+    y = oracle.unpack(padded(iq, spb))
+    if fir is not None:
+        y = oracle.fir_run(fir, y)
+    return edges_of(oracle.threshold(y, thr)).astype(np.uint64)
 
 
 def runs_of(edges, n_out):
@@ -80,3 +91,70 @@ def two_level_capture(vectors):
     g, a = scaled_golden(vectors, "G1", 1.0, noise_seed=1)
     _, b = scaled_golden(vectors, "G1", 0.25, noise_seed=2)
     return g, np.concatenate([a, b]), a.size // 2
+
+
+# ---- the seam captures behind a filter (tests/run_level_seams_inputs.py), built on the reference --------------------
+
+SEAM_NU = 600e3 / RATE              # the tuned seam cases' carrier
+
+
+def oracle_fir(oracle, shape):
+    """the reference's filter of a seam shape: a golden filter's name, "three", "narrow32", "narrow4" """
+    from tests import run_level_seams_inputs as S
+    from tests.helpers import golden_path
+    if shape == "three":
+        return oracle.make_fir(S.three_stages())
+    if shape.startswith("narrow"):
+        return oracle.make_fir(S.narrow_stages(int(shape[6:])))
+    return oracle.load_filter_json(golden_path("filters", shape))
+
+
+_built = {}
+
+
+def seam_filtered(oracle, shape, which):
+    """-> (capture, samples, samples per buffer, targets) of FILTERED_TARGETS[which] behind `shape`"""
+    from tests import run_level_seams_inputs as S
+    if (shape, which) not in _built:
+        D = S.SHAPE_D[shape]
+        n, spb = S.FILTERED_OUT * D, 500 * D
+        fir = oracle_fir(oracle, shape)
+        iq = S.filtered_capture(lambda x: ref_edges(oracle, fir, x, spb), n, D, S.FILTERED_PULSE, S.FILTERED_TARGETS[which])
+        _built[shape, which] = (iq, n, spb, S.FILTERED_TARGETS[which])
+    return _built[shape, which]
+
+
+def seam_narrow(oracle, tile):
+    """-> (capture, samples, samples per buffer, targets): NARROW_TARGETS behind the single stage whose tile is `tile`"""
+    from tests import run_level_seams_inputs as S
+    if ("narrow", tile) not in _built:
+        fir = oracle_fir(oracle, "narrow%d" % tile)
+        iq = S.filtered_capture(lambda x: ref_edges(oracle, fir, x), S.NARROW_N, 1, S.NARROW_PULSE, S.NARROW_TARGETS)
+        _built["narrow", tile] = (iq, S.NARROW_N, SPB, S.NARROW_TARGETS)
+    return _built["narrow", tile]
+
+
+def seam_tuned(flt, which):
+    """the fs32_fs4 seam capture with its pulses moved to SEAM_NU, laid on the contract of a context tuned there
+    (flt: the library's filter, whose tuned taps the contract reads) -> (capture, samples, samples per buffer,
+    targets, the contract's stages)"""
+    from tests import run_level_seams_inputs as S
+    from tests.helpers import edges_of
+    from tests.tuned_contract import contract_rx, lib_stages, moved
+    stages = lib_stages(flt, SEAM_NU)
+    if ("tuned", which) not in _built:
+        n, spb = S.FILTERED_OUT, 500
+        iq = S.filtered_capture(lambda x: edges_of(contract_rx(x, stages, THR, spb)[0]), n, 1, S.FILTERED_PULSE,
+                                S.FILTERED_TARGETS[which], move=lambda x: moved(x, SEAM_NU))
+        _built["tuned", which] = (iq, n, spb, S.FILTERED_TARGETS[which])
+    return _built["tuned", which] + (stages,)
+
+
+def assert_targets(edges, n_out, targets, what=""):
+    """every target is an edge of its kind ("open": the list ends on)"""
+    e = [int(x) for x in edges]
+    for kind, j in targets:
+        if kind == "open":
+            assert len(e) % 2 == 1 and j == n_out, (what, kind, j, len(e))
+        else:
+            assert j in e[0 if kind == "rise" else 1::2], (what, kind, j, e)
