@@ -11,6 +11,7 @@
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
  * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] [--levels]
+ *         [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>]]
  *         <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]
  *
  * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
@@ -36,6 +37,14 @@
  * the peak powers of the message's last num_bits + 2 pulses (ookd_rx_get_run_peaks, ookd_message_levels) as
  * 10 log10(power), 0 dBFS being a full-scale carrier.  Of the list the state machine decoded: the cleaned one when a
  * debounce is on.  stdout is what it is without the option.
+ *
+ * --bursts <file>: after the messages, the keyed stretches of the capture alone are cut out on the GPU
+ * (ookd_rx_bursts, ookd_rx_copy_bursts_host) and written to <file> in the capture's own sample format: give it the
+ * capture's extension and it reads back like the input (the hip_file backend picks the format from the extension).
+ * <file>.idx gets one text line per burst, `first_sample num_samples offset`, in input samples.  On-runs whose gaps
+ * are at most --burst-gap-us (default 20000) form one burst, which begins --burst-pre-us (default 500) in front of
+ * its first rise and ends --burst-post-us (default 19500) behind its last fall; the gap is raised to pre + post when
+ * it is given smaller.  Of the list the state machine decoded, as with --levels.  stdout is what it is without the option.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -69,6 +78,8 @@ int main(int argc, char **argv)
     float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
     int threshold_auto = 0, tune_auto = 0, bad_option = 0, levels = 0;
     double tune_hz = 0.0, min_on_us = 0.0, min_off_us = 0.0;
+    double burst_pre_us = 500.0, burst_post_us = 19500.0, burst_gap_us = 20000.0;
+    const char *bursts_path = NULL;
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--threshold")) {
@@ -91,6 +102,15 @@ int main(int argc, char **argv)
             if (++i >= argc) { bad_option = 1; break; }
             *us = strtod(argv[i], &end);
             if (end == argv[i] || *end != '\0' || !(*us >= 0.0)) { bad_option = 1; break; }
+        } else if (!strcmp(argv[i], "--burst-pre-us") || !strcmp(argv[i], "--burst-post-us") || !strcmp(argv[i], "--burst-gap-us")) {
+            char *end = NULL;
+            double *us = !strcmp(argv[i], "--burst-pre-us") ? &burst_pre_us : !strcmp(argv[i], "--burst-post-us") ? &burst_post_us : &burst_gap_us;
+            if (++i >= argc) { bad_option = 1; break; }
+            *us = strtod(argv[i], &end);
+            if (end == argv[i] || *end != '\0' || !(*us >= 0.0)) { bad_option = 1; break; }
+        } else if (!strcmp(argv[i], "--bursts")) {
+            if (++i >= argc) { bad_option = 1; break; }
+            bursts_path = argv[i];
         } else if (!strcmp(argv[i], "--levels")) {
             levels = 1;
         } else {
@@ -100,7 +120,8 @@ int main(int argc, char **argv)
     argc = kept;
     if (argc < 5 || bad_option) {
         fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] "
-                        "[--levels] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
+                        "[--levels] [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>]] "
+                        "<capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
                 argv[0]);
         return EXIT_FAILURE;
     }
@@ -135,6 +156,9 @@ int main(int argc, char **argv)
     char *text = NULL;
     uint64_t *edges = NULL, *at = NULL;
     float *peaks = NULL, *level = NULL;
+    ookd_burst *bursts = NULL;
+    void *cut = NULL;
+    char *idx_path = NULL;
 
     void *sdr = sdr_hip_file_init((const struct ookiedokie_cfg *)&cfg);   /* same layout: see ookd_host_cfg */
     if (!sdr) return fail("sdr_hip_file_init");
@@ -285,9 +309,49 @@ int main(int argc, char **argv)
                 fprintf(stderr, "level %u %llu -inf\n", msgs[m].capture, (unsigned long long) at[m]);
         }
     }
+    if (bursts_path) {                      /* the table from the edge list, then the cut from the capture in HBM */
+        ookd_clean_info ci;
+        ookd_burst_info bi;
+        const double out_rate = (double) rate / (double) decimation;
+        const uint64_t pre = (uint64_t) (burst_pre_us * 1e-6 * out_rate), post = (uint64_t) (burst_post_us * 1e-6 * out_rate);
+        uint64_t max_gap = (uint64_t) (burst_gap_us * 1e-6 * out_rate), nb = 0;
+        FILE *f;
+        if (max_gap < pre + post) max_gap = pre + post;
+        if (ookd_rx_bursts(rx, pre, post, max_gap, ookd_rx_get_clean_info(rx, 0, &ci) == 0 ? OOKD_BURSTS_CLEAN : 0) != 0 ||
+            ookd_rx_get_burst_info(rx, 0, &bi) != 0) {
+            fail("ookd_rx_bursts");
+            goto out;
+        }
+        bursts = malloc((bi.num_bursts + 1) * sizeof *bursts);
+        cut = malloc((size_t) (bi.total_samples + 1) * bi.sample_bytes);
+        idx_path = malloc(strlen(bursts_path) + 5);
+        if (!bursts || !cut || !idx_path) goto out;
+        if (ookd_rx_get_bursts(rx, 0, bursts, bi.num_bursts, &nb) != 0) { fail("ookd_rx_get_bursts"); goto out; }
+        if (ookd_rx_copy_bursts_host(rx, 0, cut, bi.total_samples) != 0) { fail("ookd_rx_copy_bursts_host"); goto out; }
+        f = fopen(bursts_path, "wb");
+        if (!f || fwrite(cut, bi.sample_bytes, (size_t) bi.total_samples, f) != (size_t) bi.total_samples || fclose(f) != 0) {
+            fprintf(stderr, "%s: cannot write\n", bursts_path);
+            goto out;
+        }
+        strcpy(idx_path, bursts_path);
+        strcat(idx_path, ".idx");
+        f = fopen(idx_path, "w");
+        if (!f) { fprintf(stderr, "%s: cannot write\n", idx_path); goto out; }
+        for (uint64_t b = 0; b < nb; ++b)
+            fprintf(f, "%llu %llu %llu\n", (unsigned long long) bursts[b].first_sample,
+                    (unsigned long long) bursts[b].num_samples, (unsigned long long) bursts[b].offset);
+        if (fclose(f) != 0) { fprintf(stderr, "%s: cannot write\n", idx_path); goto out; }
+        fprintf(stderr, "bursts: %llu of %llu samples in %llu bursts (pre %llu, post %llu, gap %llu outputs; table %.3f ms, "
+                        "copy %.3f ms)\n", (unsigned long long) bi.total_samples, (unsigned long long) n,
+                (unsigned long long) nb, (unsigned long long) pre, (unsigned long long) post, (unsigned long long) max_gap,
+                ookd_rx_bursts_kernel_ms(rx), ookd_rx_burst_copy_kernel_ms(rx));
+    }
     status = EXIT_SUCCESS;
 
 out:
+    free(idx_path);
+    free(cut);
+    free(bursts);
     free(level);
     free(at);
     free(peaks);

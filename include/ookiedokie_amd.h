@@ -1527,6 +1527,113 @@ int ookd_message_levels(const uint64_t *edges, uint64_t E, const float *peaks, u
                         const uint64_t *msg_samples, uint64_t M, uint32_t pulses, float *levels);
 
 /* ------------------------------------------------------------------------
+ * Burst extraction: the on-stretches of the last run's captures, cut out of
+ * the capture on the GPU.  A run says where the transmissions are and what
+ * they hold; this hands back the signal itself -- only the part that matters,
+ * in the capture's own sample format -- without the whole capture crossing
+ * PCIe.  The counterpart of a recorder that writes only what was keyed.
+ *
+ * The contract.  Take capture (or carrier) c of the context's last run: its edge
+ * list e[0..E) as ookd_rx_get_edges returns it (the cleaned list with
+ * OOKD_BURSTS_CLEAN), n_out = ookd_rx_stats.decimated_samples, D the filter's
+ * total decimation (1 without a filter) and n the samples per capture that
+ * exist in memory (the run's n_valid).
+ *   - On-run r, 0 <= r < R = ceil(E / 2), covers outputs [a_r, f_r): a_r = e[2r],
+ *     f_r = e[2r + 1], or n_out for an open last run (as at ookd_rx_run_levels).
+ *     g_r = a_{r+1} - f_r is the off-run behind run r.
+ *   - pre, post and max_gap are in decimated samples.  max_gap < pre + post is
+ *     refused (OOKD_ERR_ARG): bursts can then never overlap.
+ *   - A burst begins at run 0 and at every run r + 1 with g_r > max_gap (strict:
+ *     a gap of exactly max_gap joins).  Burst b with runs [r0, r1] covers outputs
+ *     [lo, hi), lo = a_r0 - min(a_r0, pre), hi = min(n_out, f_r1 + post), and in
+ *     input samples [first, end), first = min(n, lo D), end = min(n, hi D).
+ *     num_samples = end - first; it is 0 for a burst that lies wholly in the
+ *     padding behind n, and such a burst stays in the table.
+ *     offset_b = the sum of num_samples over the capture's bursts before b, and
+ *     total = the sum over all of them.
+ *   - The table is one ookd_burst per burst.  The cut is `total` samples in the
+ *     capture's own format (4 bytes for SC16Q11, 2 for CS8 / CU8, never
+ *     widened): sample offset_b + i of the cut is sample first_b + i of the
+ *     capture, byte for byte.  Samples at or beyond n are never read: the
+ *     capture's allocation may end at n.  In a carrier context list k cuts the
+ *     one capture it was decoded from.
+ *   - Everything is an exact function of the edge list and the capture's bytes.
+ *
+ * ookd_find_bursts is the rule on the host, pure C++ (no GPU), over one list.
+ * It follows the ookd_rx_get_edges convention: *num_bursts receives the count,
+ * at most `capacity` entries are stored, table may be NULL; *total (may be
+ * NULL) receives the cut's length.  OOKD_ERR_ARG for max_gap < pre + post, a
+ * NULL edge array that is not empty, or D = 0.
+ *
+ * ookd_rx_bursts makes the table for all captures (or carriers) of the last
+ * run in one timed pass on the context's stream (ookd_rx_bursts_kernel_ms: its
+ * HIP-event time, 0 while nobody has asked or there was nothing to launch).
+ * Like ookd_rx_pulse_hist it is a by-product of a finished run: a run nobody
+ * asks about launches and allocates nothing.  It refuses what
+ * ookd_rx_pulse_hist refuses, with the same codes.  OOKD_BURSTS_CLEAN reads the
+ * cleaned list of the last run (ookd_rx_clean_edges, or a debounced context's
+ * own) and is refused without one, as ookd_rx_run_levels_clean is.  The same
+ * parameters on the same run launch nothing; other parameters, or another
+ * cleaned list of the same run, make a new table.  The raw and the clean form
+ * keep a table each; ookd_rx_get_burst_info, ookd_rx_get_bursts and the two
+ * copy calls are about the form ookd_rx_bursts was last called with for this
+ * run, and are refused (OOKD_ERR_ARG) when the last run has no table.
+ * ookd_rx_bursts_kernel_ms is the time of that form's pass.
+ *
+ * ookd_rx_copy_bursts_device writes the cut of one capture to device memory of
+ * the context's device: capacity_samples < total is OOKD_ERR_CAPACITY and
+ * nothing is written; nothing at or beyond `total` samples is written either.
+ * The kernel moves 16-byte vectors when d_out is 16-byte aligned (any hipMalloc
+ * pointer is) and single samples otherwise.  ookd_rx_copy_bursts_host does the
+ * same through a device buffer of exactly `total` samples that it allocates and
+ * frees.  ookd_rx_burst_copy_kernel_ms is the HIP-event time of the last copy
+ * kernel about the last run (0: none, or a cut of no samples).
+ *
+ * The capture is read again by the copy, through the pointer and stride the
+ * context recorded at submit: the caller of ookd_rx_process_device /
+ * ookd_rx_submit_device keeps the capture resident and unchanged until the
+ * copy has returned.  After ookd_rx_process_host it is the context's own copy.
+ * The table pass reads the edge list only.
+ *
+ * Limits: shard and pipelined runs are refused; one cut per call (no batch of
+ * captures in one launch); the cut is not resampled or filtered.
+ * ---------------------------------------------------------------------- */
+typedef struct ookd_burst {
+    uint64_t first_sample;          /* input sample of the capture the burst begins at */
+    uint64_t num_samples;
+    uint64_t offset;                /* sample of the cut the burst begins at  */
+    uint64_t first_run;             /* r0                                     */
+    uint64_t num_runs;              /* r1 - r0 + 1                            */
+} ookd_burst;
+
+typedef struct ookd_burst_info {
+    uint64_t num_bursts;
+    uint64_t total_samples;
+    uint64_t num_runs;              /* R                                      */
+    uint64_t pre, post, max_gap;    /* as given to ookd_rx_bursts             */
+    uint32_t flags;                 /* OOKD_BURSTS_*                          */
+    uint32_t sample_bytes;          /* of one sample of the cut: 4 or 2       */
+    uint32_t tile_edges;            /* edges of one tile of the table pass    */
+    uint32_t decimation;            /* D                                      */
+} ookd_burst_info;
+
+enum {
+    OOKD_BURSTS_CLEAN = 1           /* read the cleaned list of the last run  */
+};
+
+int ookd_find_bursts(const uint64_t *edges, uint64_t E, uint64_t n_out, uint64_t D, uint64_t n,
+                     uint64_t pre, uint64_t post, uint64_t max_gap, ookd_burst *table,
+                     uint64_t capacity, uint64_t *num_bursts, uint64_t *total);
+int ookd_rx_bursts(ookd_rx *rx, uint64_t pre, uint64_t post, uint64_t max_gap, uint32_t flags);
+int ookd_rx_get_burst_info(const ookd_rx *rx, uint32_t capture, ookd_burst_info *out);
+int ookd_rx_get_bursts(const ookd_rx *rx, uint32_t capture, ookd_burst *table, uint64_t capacity,
+                       uint64_t *num_bursts);
+int ookd_rx_copy_bursts_device(ookd_rx *rx, uint32_t capture, void *d_out, uint64_t capacity_samples);
+int ookd_rx_copy_bursts_host(ookd_rx *rx, uint32_t capture, void *out, uint64_t capacity_samples);
+float ookd_rx_bursts_kernel_ms(const ookd_rx *rx);
+float ookd_rx_burst_copy_kernel_ms(const ookd_rx *rx);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

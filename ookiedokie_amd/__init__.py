@@ -28,6 +28,8 @@ here                              reference (OOKiedokie ``src/``)
 ``Receiver.set_debounce``         list, so a glitch no longer costs a message
 ``Receiver.run_levels`` /         nothing: the peak power of every pulse and a
 ``Receiver.message_levels``       signal level per decoded message
+``Receiver.bursts`` /             ``--rx-rec`` writes everything: the keyed
+``Receiver.burst_samples``        stretches of a capture alone, cut on the GPU
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -225,6 +227,21 @@ class CarrierStruct(C.Structure):
 class RunLevels(C.Structure):
     _fields_ = [("num_runs", C.c_uint64), ("tiles_total", C.c_uint64), ("tiles_filtered", C.c_uint64),
                 ("tile_outputs", C.c_uint32), ("reserved", C.c_uint32), ("hist", LevelHist)]
+
+
+class Burst(C.Structure):
+    _fields_ = [("first_sample", C.c_uint64), ("num_samples", C.c_uint64), ("offset", C.c_uint64),
+                ("first_run", C.c_uint64), ("num_runs", C.c_uint64)]
+
+
+class BurstInfo(C.Structure):
+    _fields_ = [("num_bursts", C.c_uint64), ("total_samples", C.c_uint64), ("num_runs", C.c_uint64),
+                ("pre", C.c_uint64), ("post", C.c_uint64), ("max_gap", C.c_uint64), ("flags", C.c_uint32),
+                ("sample_bytes", C.c_uint32), ("tile_edges", C.c_uint32), ("decimation", C.c_uint32)]
+
+
+BURSTS_CLEAN = 1                        # OOKD_BURSTS_CLEAN
+BURST_FIELDS = tuple(name for name, _ in Burst._fields_)
 
 
 class PulseHist(C.Structure):
@@ -436,6 +453,15 @@ _PROTOTYPES = {
     "ookd_rx_levels_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_message_levels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                       C.c_void_p]),
+    "ookd_find_bursts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                   C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ookd_rx_bursts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
+    "ookd_rx_get_burst_info": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BurstInfo)]),
+    "ookd_rx_get_bursts": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_copy_bursts_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "ookd_rx_copy_bursts_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "ookd_rx_bursts_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_rx_burst_copy_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_device_from_suggestion": (C.c_void_p, [C.POINTER(DeviceSuggestion), C.c_uint32]),
     "ookd_device_suggestion_json": (C.c_size_t, [C.POINTER(DeviceSuggestion), C.c_char_p, C.c_char_p, C.c_size_t]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
@@ -1185,6 +1211,92 @@ class Receiver:
         """HIP-event time of the pass behind `run_levels` for the last run; 0 while nobody has asked about it."""
         return float(lib().ookd_rx_levels_kernel_ms(self._h))
 
+    # -- burst extraction ------------------------------------------------------------
+    def _burst_info(self, capture: int) -> BurstInfo:
+        info = BurstInfo()
+        _check(lib().ookd_rx_get_burst_info(self._h, capture, C.byref(info)))
+        return info
+
+    def bursts(self, pre: int, post: int, max_gap: int, clean: bool = False) -> List[dict]:
+        """The burst table of every capture (or carrier) of the last run, made on the GPU (ookd_rx_bursts; the rule is
+        `find_bursts` at module level): on-runs whose gaps are at most max_gap decimated samples form one burst, which
+        reaches `pre` outputs in front of its first rise and `post` behind its last fall; max_gap >= pre + post.
+        Returns per capture num_bursts, total_samples, num_runs, pre, post, max_gap, sample_bytes, tile_edges,
+        decimation and the table as uint64 arrays first_sample, num_samples, offset (input samples), first_run and
+        burst_runs.  The same parameters on the same run launch nothing.  clean=True: over the cleaned list
+        (`clean_edges` first, or a debounced context).  `burst_samples` then returns the cut."""
+        _check(lib().ookd_rx_bursts(self._h, int(pre), int(post), int(max_gap), BURSTS_CLEAN if clean else 0))
+        out = []
+        info = BurstInfo()
+        # (the call above answered the last run: the first refusal is the capture behind the run's last)
+        while lib().ookd_rx_get_burst_info(self._h, len(out), C.byref(info)) == 0:
+            nb = int(info.num_bursts)
+            table = np.zeros((max(nb, 1), len(BURST_FIELDS)), dtype=np.uint64)
+            n = C.c_uint64(0)
+            _check(lib().ookd_rx_get_bursts(self._h, len(out), table.ctypes.data, nb, C.byref(n)))
+            table = table[:int(n.value)]
+            d = {name: int(getattr(info, name)) for name, _ in BurstInfo._fields_ if name != "num_runs"}
+            d["num_runs"] = int(info.num_runs)
+            for k, name in enumerate(BURST_FIELDS):
+                d["burst_runs" if name == "num_runs" else name] = table[:, k].copy()
+            out.append(d)
+        return out
+
+    def burst_samples(self, capture: int = 0) -> np.ndarray:
+        """The cut of one capture (in a carrier context: of the one capture, by carrier `capture`'s list) after
+        `bursts`: [total_samples, 2] in the format's dtype -- sample offset[b] + i is sample first_sample[b] + i of
+        the capture, byte for byte (ookd_rx_copy_bursts_host).  Only the cut crosses PCIe.  A capture handed over as a
+        device pointer stays resident and unchanged until this returns."""
+        total = int(self._burst_info(capture).total_samples)
+        out = np.zeros((max(total, 1), 2), dtype=self._sample_dtype)
+        _check(lib().ookd_rx_copy_bursts_host(self._h, capture, out.ctypes.data, total))
+        return out[:total]
+
+    def burst_samples_device(self, capture: int, ptr: int, capacity: int) -> int:
+        """The same cut into device memory at `ptr` with room for `capacity` samples (ookd_rx_copy_bursts_device); a
+        16-byte aligned `ptr` is copied in vectors.  Returns total_samples; nothing at or beyond it is written."""
+        _check(lib().ookd_rx_copy_bursts_device(self._h, capture, ptr, int(capacity)))
+        return int(self._burst_info(capture).total_samples)
+
+    def message_bursts(self, result: RxResult, capture: Optional[int] = None) -> np.ndarray:
+        """For each message of `result` (this context's last run) the index of the burst of its capture's table whose
+        outputs [lo, hi) hold its `sample`, or -1; int64 aligned with the messages.  capture: only that capture's
+        messages get an index (the others -1).  Host only, after `bursts`."""
+        out = np.full(len(result.msg_samples), -1, dtype=np.int64)
+        for c in np.unique(result.captures):
+            if capture is not None and int(c) != int(capture):
+                continue
+            info = self._burst_info(int(c))
+            nb = int(info.num_bursts)
+            if nb == 0:
+                continue
+            table = np.zeros((nb, len(BURST_FIELDS)), dtype=np.uint64)
+            _check(lib().ookd_rx_get_bursts(self._h, int(c), table.ctypes.data, nb, None))
+            e = self.edges(int(c), bool(info.flags & BURSTS_CLEAN))
+            n_out = self.stats()["decimated_samples"]
+            r0 = table[:, 3].astype(np.int64)
+            r1 = r0 + table[:, 4].astype(np.int64) - 1
+            a = e[2 * r0].astype(np.int64)
+            f = np.array([int(e[2 * r + 1]) if 2 * r + 1 < e.size else n_out for r in r1], dtype=np.int64)
+            lo = a - np.minimum(a, int(info.pre))
+            hi = np.minimum(n_out, f + int(info.post))
+            m = np.nonzero(result.captures == c)[0]
+            s = result.msg_samples[m].astype(np.int64)
+            b = np.searchsorted(lo, s, side="right") - 1
+            ok = (b >= 0) & (s < hi[np.maximum(b, 0)])
+            out[m] = np.where(ok, b, -1)
+        return out
+
+    @property
+    def bursts_kernel_ms(self) -> float:
+        """HIP-event time of the pass behind `bursts` for the last run; 0 while nobody has asked about it."""
+        return float(lib().ookd_rx_bursts_kernel_ms(self._h))
+
+    @property
+    def burst_copy_kernel_ms(self) -> float:
+        """HIP-event time of the last `burst_samples` / `burst_samples_device` kernel about the last run."""
+        return float(lib().ookd_rx_burst_copy_kernel_ms(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_rx_destroy(self._h)
@@ -1209,6 +1321,26 @@ def clean_edges(edges, min_on: int, min_off: int) -> np.ndarray:
     _check(lib().ookd_clean_edges(e.ctypes.data if e.size else None, e.size, int(min_on), int(min_off), out.ctypes.data,
                                   e.size, C.byref(n)))
     return out[:n.value]
+
+
+# --------------------------------------------------------------------------
+# burst extraction
+
+def find_bursts(edges, n_out: int, decimation: int, n: int, pre: int, post: int, max_gap: int) -> dict:
+    """ookd_find_bursts: the bursts of one edge list -- on-runs joined across gaps of at most max_gap outputs, `pre`
+    in front and `post` behind, in input samples clipped at n.  Returns num_bursts, total_samples and the table as
+    uint64 arrays first_sample, num_samples, offset, first_run, burst_runs.  Pure host code."""
+    e = np.ascontiguousarray(edges, dtype=np.uint64)
+    cap = (e.size + 1) // 2
+    table = np.zeros((max(cap, 1), len(BURST_FIELDS)), dtype=np.uint64)
+    nb, total = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().ookd_find_bursts(e.ctypes.data if e.size else None, e.size, int(n_out), int(decimation), int(n), int(pre),
+                                  int(post), int(max_gap), table.ctypes.data, cap, C.byref(nb), C.byref(total)))
+    table = table[:int(nb.value)]
+    d = dict(num_bursts=int(nb.value), total_samples=int(total.value))
+    for k, name in enumerate(BURST_FIELDS):
+        d["burst_runs" if name == "num_runs" else name] = table[:, k].copy()
+    return d
 
 
 # --------------------------------------------------------------------------

@@ -19,7 +19,8 @@ LIB = os.path.join(HERE, "lib", "libookiedokie_amd.so")
 SOURCES = ["loaders.cpp", "front_plan.cpp", "rx.cpp", "synth.cpp", "stream_fir.cpp", "backend.cpp", "edges_fsm.hip", "fsm_scan.hip",
            "formatter.cpp", "kernels.hip", "fir_mfma.hip", "fir_tuned.hip", "scan_ctx.cpp", "survey.cpp", "survey.hip",
            "survey_tuned.hip", "survey_carriers.hip", "survey_carriers_fir2.hip", "spectrum.cpp", "spectrum.hip", "edge_pass.cpp", "pulses.cpp", "pulses.hip",
-           "symbols.cpp", "symbols.hip", "clean.cpp", "clean.hip", "run_levels.cpp", "run_levels.hip"]
+           "symbols.cpp", "symbols.hip", "clean.cpp", "clean.hip", "run_levels.cpp", "run_levels.hip",
+           "bursts.cpp", "bursts.hip"]
 ARCH = "gfx950"
 
 
