@@ -10,7 +10,7 @@
  *   gcc -std=c99 -Wall -Iinclude examples/ookd_rx.c -o ookd_rx \
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
- * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] [--levels]
+ * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] [--levels] [--carriers]
  *         [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>]]
  *         <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]
  *
@@ -37,6 +37,14 @@
  * the peak powers of the message's last num_bits + 2 pulses (ookd_rx_get_run_peaks, ookd_message_levels) as
  * 10 log10(power), 0 dBFS being a full-scale carrier.  Of the list the state machine decoded: the cleaned one when a
  * debounce is on.  stdout is what it is without the option.
+ *
+ * --carriers: after the messages (and the level lines), one line per message on stderr,
+ * `carrier <capture> <sample> <Hz> <dBFS> <coherence>`: which transmitter sent it.  The carrier is the phase step between
+ * neighbouring filter outputs summed over the message's last num_bits + 2 pulses (ookd_rx_get_run_moments,
+ * ookd_message_carriers), in Hz beside the capture's centre (in cycles per sample when the sample rate is given as 0),
+ * on the branch nearest --tune; the level is the mean power of the same pulses as 10 log10(power); the coherence is 1 for
+ * one clean carrier and less with noise or a second signal in the band.  Of the list the state machine decoded, as with
+ * --levels.  stdout is what it is without the option.
  *
  * --bursts <file>: after the messages, the keyed stretches of the capture alone are cut out on the GPU
  * (ookd_rx_bursts, ookd_rx_copy_bursts_host) and written to <file> in the capture's own sample format: give it the
@@ -76,7 +84,7 @@ int main(int argc, char **argv)
 {
     /* --threshold <value>|auto is taken out of argv; what is left is positional, as before */
     float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
-    int threshold_auto = 0, tune_auto = 0, bad_option = 0, levels = 0;
+    int threshold_auto = 0, tune_auto = 0, bad_option = 0, levels = 0, carriers = 0;
     double tune_hz = 0.0, min_on_us = 0.0, min_off_us = 0.0;
     double burst_pre_us = 500.0, burst_post_us = 19500.0, burst_gap_us = 20000.0;
     const char *bursts_path = NULL;
@@ -113,6 +121,8 @@ int main(int argc, char **argv)
             bursts_path = argv[i];
         } else if (!strcmp(argv[i], "--levels")) {
             levels = 1;
+        } else if (!strcmp(argv[i], "--carriers")) {
+            carriers = 1;
         } else {
             argv[kept++] = argv[i];
         }
@@ -120,7 +130,7 @@ int main(int argc, char **argv)
     argc = kept;
     if (argc < 5 || bad_option) {
         fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] "
-                        "[--levels] [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>]] "
+                        "[--levels] [--carriers] [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>]] "
                         "<capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
                 argv[0]);
         return EXIT_FAILURE;
@@ -156,6 +166,8 @@ int main(int argc, char **argv)
     char *text = NULL;
     uint64_t *edges = NULL, *at = NULL;
     float *peaks = NULL, *level = NULL;
+    ookd_run_moment *moments = NULL;
+    ookd_message_carrier *sent = NULL;
     ookd_burst *bursts = NULL;
     void *cut = NULL;
     char *idx_path = NULL;
@@ -309,6 +321,49 @@ int main(int argc, char **argv)
                 fprintf(stderr, "level %u %llu -inf\n", msgs[m].capture, (unsigned long long) at[m]);
         }
     }
+    if (carriers && nmsg) {                 /* the same pass with another epilogue: sums in the place of a maximum */
+        ookd_clean_info ci;
+        ookd_run_moments info;
+        const int clean = ookd_rx_get_clean_info(rx, 0, &ci) == 0;
+        uint64_t ne = 0, nr = 0;
+        if (ookd_rx_get_stats(rx, &st) != 0) { fail("ookd_rx_get_stats"); goto out; }   /* n_out ends an open last run */
+        if ((clean ? ookd_rx_get_clean_edges(rx, 0, NULL, 0, &ne) : ookd_rx_get_edges(rx, 0, NULL, 0, &ne)) != 0) {
+            fail("ookd_rx_get_edges");
+            goto out;
+        }
+        if ((clean ? ookd_rx_run_moments_clean(rx, 0, &info) : ookd_rx_run_moments(rx, 0, &info)) != 0) {
+            fail("ookd_rx_run_moments");
+            goto out;
+        }
+        nr = info.num_runs;
+        free(edges);
+        free(at);
+        edges = malloc((ne + 1) * sizeof *edges);
+        at = malloc(nmsg * sizeof *at);
+        moments = malloc((nr + 1) * sizeof *moments);
+        sent = malloc(nmsg * sizeof *sent);
+        if (!edges || !at || !moments || !sent) goto out;
+        if ((clean ? ookd_rx_get_clean_edges(rx, 0, edges, ne, &ne) : ookd_rx_get_edges(rx, 0, edges, ne, &ne)) != 0 ||
+            (clean ? ookd_rx_get_run_moments_clean(rx, 0, moments, nr, &nr) : ookd_rx_get_run_moments(rx, 0, moments, nr, &nr)) != 0) {
+            fail("ookd_rx_get_run_moments");
+            goto out;
+        }
+        for (uint64_t m = 0; m < nmsg; ++m) at[m] = msgs[m].sample;
+        if (ookd_message_carriers(edges, ne, st.decimated_samples, moments, nr, at, nmsg, ookd_device_num_bits(device) + 2,
+                                  info.decimation, tune.nu, sent) != 0) {
+            fail("ookd_message_carriers");
+            goto out;
+        }
+        for (uint64_t m = 0; m < nmsg; ++m) {
+            const double where = rate ? sent[m].carrier * (double) rate : sent[m].carrier;
+            if (sent[m].mean_power > 0.0)
+                fprintf(stderr, "carrier %u %llu %.*f %.2f %.4f\n", msgs[m].capture, (unsigned long long) at[m], rate ? 1 : 9, where,
+                        decibel(sent[m].mean_power), sent[m].coherence);
+            else
+                fprintf(stderr, "carrier %u %llu %.*f -inf %.4f\n", msgs[m].capture, (unsigned long long) at[m], rate ? 1 : 9, where,
+                        sent[m].coherence);
+        }
+    }
     if (bursts_path) {                      /* the table from the edge list, then the cut from the capture in HBM */
         ookd_clean_info ci;
         ookd_burst_info bi;
@@ -352,6 +407,8 @@ out:
     free(idx_path);
     free(cut);
     free(bursts);
+    free(sent);
+    free(moments);
     free(level);
     free(at);
     free(peaks);

@@ -1527,6 +1527,123 @@ int ookd_message_levels(const uint64_t *edges, uint64_t E, const float *peaks, u
                         const uint64_t *msg_samples, uint64_t M, uint32_t pulses, float *levels);
 
 /* ------------------------------------------------------------------------
+ * Pulse moments: the mean power and the carrier of every on-run of the last run,
+ * and per message.  Two remotes of one model on one channel decode to the same
+ * kind of message and, at like distances, to like levels; they almost always
+ * differ in their carrier.  The phase step between neighbouring filter outputs
+ * of a pulse is the transmitter's frequency, and the filter's complex output is
+ * formed anyway where the pulse levels take its power.
+ *
+ * The contract.  Take capture (or carrier) c of the context's last run, its edge
+ * list e[0..E) and n_out.  On-run r covers outputs [a_r, f_r) exactly as "Pulse
+ * levels" defines them: a_r = e[2r], f_r = e[2r + 1], or n_out for an open last
+ * run, the padding to whole buffers included, inputs at or beyond n zero and
+ * never loaded.
+ *   - y_j = (re_j, im_j) is the float32 complex filter output whose power the
+ *     levels' contract calls p_j, by the context's kind: the untuned survey
+ *     contract, the tuned survey contract with that carrier's nu, or the
+ *     unpacked sample without a filter.  p_j = re*re + im*im with three
+ *     roundings, as there.
+ *   - For j > a_r inside the run the lag product against the output before is
+ *     formed without fused multiply-adds, each product rounded, then the sum or
+ *     the difference rounded:
+ *         zr_j = (re_j * re_{j-1}) + (im_j * im_{j-1})
+ *         zi_j = (im_j * re_{j-1}) - (re_j * im_{j-1})
+ *   - q(v) = llrint((double)v * 2^30), ties to even, after v has been clamped to
+ *     [-2^32, 2^32]; a NaN gives 0.  The product in double is exact, and for
+ *     |v| >= 2^-7 the rounding does nothing (a float32 of that size has no bits
+ *     below 2^-30).
+ *   - power[r]  = sum over j = a_r     .. f_r - 1 of q(p_j)
+ *     lag_re[r] = sum over j = a_r + 1 .. f_r - 1 of q(zr_j)
+ *     lag_im[r] = sum over j = a_r + 1 .. f_r - 1 of q(zi_j)
+ *     each an int64 taken modulo 2^64 (two's complement wrap).  A run of one
+ *     output has lag 0.  No pair joins two captures: a run that rises at output
+ *     0 has its first pair at j = 1.
+ *   - Integer sums need no order, so the result is an exact function of the
+ *     capture and the edge list, however many workgroups share a run -- the
+ *     argument the levels make for the maximum of bit patterns.
+ *   - The sums do not wrap for runs of up to 2^21 outputs of a full-scale
+ *     SC16Q11 capture through a filter with sum |h| <= 2: |y| <= 32 sqrt 2 there,
+ *     every term is at most 2^11 * 2^30 in magnitude, and 2^21 of them stay
+ *     below 2^63 (the clamp bounds a term by 2^62 whatever the capture holds).
+ *     Nominal signals, |y| <= 1, have room for runs just short of 2^33 outputs.
+ *   - tile_outputs, tiles_total and tiles_filtered are as at ookd_run_levels, for
+ *     this pass's own tile: it keeps one more output per tile than the levels'
+ *     pass, so its tile may be smaller for the same filter.  decimation is D,
+ *     the filter's total decimation (1 without a filter).
+ *
+ * The calls behave as the pulse levels' do: a by-product of a finished run that
+ * launches and allocates nothing unless asked; one timed pass on the context's
+ * stream for all captures or carriers at the first call about a run
+ * (ookd_rx_moments_kernel_ms, the raw list's), later calls answer from what it
+ * left; the refusals of ookd_rx_pulse_hist with the same codes, and the LDS
+ * window's; a run of no samples is valid and launches nothing; the capture is
+ * read again and stays resident and unchanged until the first call has returned;
+ * the _clean forms read the cleaned list, keep their own pass, and make a new
+ * pass when ookd_rx_clean_edges has made another list.
+ * ookd_rx_get_run_moments follows the ookd_rx_get_edges convention.
+ *
+ * ookd_run_moments_of is the contract on the host, pure C++ (no GPU), given the
+ * filter's output y[n_out][2] and one list: out[0..R), R = ceil(E / 2).
+ * OOKD_ERR_ARG for a NULL array that is not empty, R != ceil(E / 2), or edges
+ * that do not ascend strictly below n_out.
+ *
+ * ookd_message_carriers is host only.  edges, moments and msg_samples are one
+ * capture's, as at ookd_message_levels, and message m takes the on-runs that
+ * rule takes: the last `pulses` of those rising in (msg_samples[m - 1],
+ * msg_samples[m]].  Their three sums and their lengths (an open last run ends
+ * at n_out) are added as doubles in ascending r to P, Zr, Zi and `outputs`:
+ *     mean_power = P / 2^30 / outputs          (0 without a run)
+ *     coherence  = hypot(Zr, Zi) / P           (0 when P = 0): 1 for one clean
+ *                  carrier, less with noise or a second signal in the band
+ *     carrier    = nu + wrap(atan2(Zi, Zr) / 2 pi - nu D) / D, wrap into
+ *                  [-1/2, 1/2), in cycles per INPUT sample -- the unit of
+ *                  ookd_rx tuning.  The tuned filter is a band-pass, not a
+ *                  mixer: y advances by 2 pi f D per output whatever nu is, so
+ *                  the estimate is absolute modulo 1 / D and the branch nearest
+ *                  nu is taken (nu = 0 for an untuned context).
+ * Without a pair (Zr = Zi = 0) carrier = nu and coherence = 0.  OOKD_ERR_ARG for
+ * what ookd_message_levels refuses, decimation = 0, or an open last run that
+ * begins at or beyond n_out.
+ *
+ * Limits: on-runs only; lag 1 only; the estimate is unambiguous within
+ * +-1 / (2 D) of nu; a DC term or a second carrier inside the filter's band
+ * biases it; shard and pipelined runs are refused.
+ * ---------------------------------------------------------------------- */
+typedef struct ookd_run_moment {
+    int64_t power, lag_re, lag_im;  /* fixed point, 30 fraction bits          */
+} ookd_run_moment;
+
+typedef struct ookd_run_moments {
+    uint64_t num_runs;              /* R                                      */
+    uint64_t tiles_total;
+    uint64_t tiles_filtered;
+    uint32_t tile_outputs;
+    uint32_t decimation;            /* D                                      */
+} ookd_run_moments;
+
+typedef struct ookd_message_carrier {
+    double carrier;                 /* cycles per input sample                */
+    double mean_power;
+    double coherence;
+    uint64_t outputs;
+} ookd_message_carrier;
+
+int ookd_rx_run_moments(ookd_rx *rx, uint32_t capture, ookd_run_moments *out);
+int ookd_rx_run_moments_clean(ookd_rx *rx, uint32_t capture, ookd_run_moments *out);
+int ookd_rx_get_run_moments(ookd_rx *rx, uint32_t capture, ookd_run_moment *moments,
+                            uint64_t capacity, uint64_t *num_runs);
+int ookd_rx_get_run_moments_clean(ookd_rx *rx, uint32_t capture, ookd_run_moment *moments,
+                                  uint64_t capacity, uint64_t *num_runs);
+float ookd_rx_moments_kernel_ms(const ookd_rx *rx);
+int ookd_run_moments_of(const float *y, uint64_t n_out, const uint64_t *edges, uint64_t E,
+                        ookd_run_moment *out, uint64_t R);
+int ookd_message_carriers(const uint64_t *edges, uint64_t E, uint64_t n_out,
+                          const ookd_run_moment *moments, uint64_t R, const uint64_t *msg_samples,
+                          uint64_t M, uint32_t pulses, uint32_t decimation, double nu,
+                          ookd_message_carrier *out);
+
+/* ------------------------------------------------------------------------
  * Burst extraction: the on-stretches of the last run's captures, cut out of
  * the capture on the GPU.  A run says where the transmissions are and what
  * they hold; this hands back the signal itself -- only the part that matters,

@@ -28,6 +28,8 @@ here                              reference (OOKiedokie ``src/``)
 ``Receiver.set_debounce``         list, so a glitch no longer costs a message
 ``Receiver.run_levels`` /         nothing: the peak power of every pulse and a
 ``Receiver.message_levels``       signal level per decoded message
+``Receiver.run_moments`` /        nothing: the mean power and the carrier of every
+``Receiver.message_carriers``     pulse, and which transmitter sent a message
 ``Receiver.bursts`` /             ``--rx-rec`` writes everything: the keyed
 ``Receiver.burst_samples``        stretches of a capture alone, cut on the GPU
 ================================  ==========================================
@@ -227,6 +229,16 @@ class CarrierStruct(C.Structure):
 class RunLevels(C.Structure):
     _fields_ = [("num_runs", C.c_uint64), ("tiles_total", C.c_uint64), ("tiles_filtered", C.c_uint64),
                 ("tile_outputs", C.c_uint32), ("reserved", C.c_uint32), ("hist", LevelHist)]
+
+
+class RunMoments(C.Structure):
+    _fields_ = [("num_runs", C.c_uint64), ("tiles_total", C.c_uint64), ("tiles_filtered", C.c_uint64),
+                ("tile_outputs", C.c_uint32), ("decimation", C.c_uint32)]
+
+
+class MessageCarrier(C.Structure):
+    _fields_ = [("carrier", C.c_double), ("mean_power", C.c_double), ("coherence", C.c_double),
+                ("outputs", C.c_uint64)]
 
 
 class Burst(C.Structure):
@@ -453,6 +465,14 @@ _PROTOTYPES = {
     "ookd_rx_levels_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_message_levels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                       C.c_void_p]),
+    "ookd_rx_run_moments": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RunMoments)]),
+    "ookd_rx_run_moments_clean": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RunMoments)]),
+    "ookd_rx_get_run_moments": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_get_run_moments_clean": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_moments_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_run_moments_of": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "ookd_message_carriers": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                        C.c_uint32, C.c_uint32, C.c_double, C.c_void_p]),
     "ookd_find_bursts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                    C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ookd_rx_bursts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
@@ -1211,6 +1231,52 @@ class Receiver:
         """HIP-event time of the pass behind `run_levels` for the last run; 0 while nobody has asked about it."""
         return float(lib().ookd_rx_levels_kernel_ms(self._h))
 
+    # -- pulse moments ---------------------------------------------------------------
+    def run_moments(self, capture: int = 0, clean: bool = False) -> dict:
+        """The summed power and the summed lag-1 product of every on-run of one capture (or carrier) of the last run
+        (ookd_rx_run_moments): int64 arrays `power`, `lag_re`, `lag_im` [num_runs], fixed point with 30 fraction bits
+        -- run r begins at edge 2 r of `edges(capture, clean)` --, num_runs, tile_outputs, tiles_total, tiles_filtered
+        and decimation.  Exact integers, whatever the order the GPU summed them in.  Computed for all captures at the
+        first call after a run, from the capture itself, as `run_levels` is; clean=True: over the cleaned list."""
+        out = RunMoments()
+        _check((lib().ookd_rx_run_moments_clean if clean else lib().ookd_rx_run_moments)(self._h, capture, C.byref(out)))
+        sums = np.zeros((max(int(out.num_runs), 1), 3), dtype=np.int64)
+        n = C.c_uint64(0)
+        get = lib().ookd_rx_get_run_moments_clean if clean else lib().ookd_rx_get_run_moments
+        _check(get(self._h, capture, sums.ctypes.data, int(out.num_runs), C.byref(n)))
+        sums = sums[:int(n.value)]
+        return dict(num_runs=int(out.num_runs), tiles_total=int(out.tiles_total), tiles_filtered=int(out.tiles_filtered),
+                    tile_outputs=int(out.tile_outputs), decimation=int(out.decimation),
+                    power=sums[:, 0].copy(), lag_re=sums[:, 1].copy(), lag_im=sums[:, 2].copy())
+
+    def message_carriers(self, result: RxResult, pulses: Optional[int] = None, clean: bool = False) -> dict:
+        """Per message of `result` (this context's last run), aligned with it: `carrier` (cycles per input sample; the
+        branch nearest the context's nu), `mean_power` (10 log10 of it is the level in dBFS), `coherence` (float64) and
+        `outputs` (uint64), from the moments of the message's last `pulses` on-runs (`message_carriers` at module
+        level; pulses defaults to the device's num_bits + 2).  In a carrier context each message uses its carrier's
+        list and nu."""
+        if pulses is None:
+            if self._device is None:
+                raise ValueError("pulses is needed on a context without a device")
+            pulses = self._device.num_bits + 2
+        count = len(result.msg_samples)
+        out = dict(carrier=np.zeros(count), mean_power=np.zeros(count), coherence=np.zeros(count),
+                   outputs=np.zeros(count, dtype=np.uint64))
+        n_out = self.stats()["decimated_samples"]
+        for c in np.unique(result.captures):
+            m = np.nonzero(result.captures == c)[0]
+            mo = self.run_moments(int(c), clean)
+            nu = self.carrier(int(c))[0] if self.num_carriers else self.tune
+            got = message_carriers(self.edges(int(c), clean), mo, result.msg_samples[m], pulses, mo["decimation"], nu, n_out)
+            for key in out:
+                out[key][m] = got[key]
+        return out
+
+    @property
+    def moments_kernel_ms(self) -> float:
+        """HIP-event time of the pass behind `run_moments` for the last run; 0 while nobody has asked about it."""
+        return float(lib().ookd_rx_moments_kernel_ms(self._h))
+
     # -- burst extraction ------------------------------------------------------------
     def _burst_info(self, capture: int) -> BurstInfo:
         info = BurstInfo()
@@ -1357,6 +1423,48 @@ def message_levels(edges, peaks, msg_samples, pulses: int) -> np.ndarray:
     _check(lib().ookd_message_levels(e.ctypes.data if e.size else None, e.size, p.ctypes.data if p.size else None, p.size,
                                      m.ctypes.data if m.size else None, m.size, int(pulses), out.ctypes.data))
     return out[:m.size]
+
+
+# --------------------------------------------------------------------------
+# pulse moments
+
+def _moment_rows(moments) -> np.ndarray:
+    if isinstance(moments, dict):
+        moments = np.stack([np.asarray(moments[k], dtype=np.int64) for k in ("power", "lag_re", "lag_im")], axis=1)
+    return np.ascontiguousarray(moments, dtype=np.int64).reshape(-1, 3)
+
+
+def run_moments_of(y, edges) -> dict:
+    """ookd_run_moments_of: the pulse moments' contract on the host, given the filter's complex output y [n_out, 2]
+    float32 and one capture's edges: int64 arrays `power`, `lag_re`, `lag_im`, one entry per on-run.  Pure host
+    code."""
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1, 2)
+    e = np.ascontiguousarray(edges, dtype=np.uint64)
+    runs = (e.size + 1) // 2
+    out = np.zeros((max(runs, 1), 3), dtype=np.int64)
+    _check(lib().ookd_run_moments_of(y.ctypes.data if y.size else None, y.shape[0], e.ctypes.data if e.size else None,
+                                     e.size, out.ctypes.data if runs else None, runs))
+    out = out[:runs]
+    return dict(power=out[:, 0].copy(), lag_re=out[:, 1].copy(), lag_im=out[:, 2].copy())
+
+
+def message_carriers(edges, moments, msg_samples, pulses: int, decimation: int, nu: float, n_out: int) -> dict:
+    """ookd_message_carriers: message m takes the on-runs `message_levels` takes and adds their sums: `carrier`
+    (cycles per input sample, the branch nearest nu), `mean_power`, `coherence` (float64) and `outputs` (uint64).
+    moments: `Receiver.run_moments`'s or `run_moments_of`'s dict, or an int64 array [R, 3].  n_out ends an open last
+    run.  Pure host code."""
+    e = np.ascontiguousarray(edges, dtype=np.uint64)
+    mo = _moment_rows(moments)
+    m = np.ascontiguousarray(msg_samples, dtype=np.uint64)
+    out = (MessageCarrier * max(m.size, 1))()
+    _check(lib().ookd_message_carriers(e.ctypes.data if e.size else None, e.size, int(n_out),
+                                       mo.ctypes.data if mo.size else None, mo.shape[0], m.ctypes.data if m.size else None,
+                                       m.size, int(pulses), int(decimation), float(nu), out))
+    rows = [out[k] for k in range(m.size)]
+    return dict(carrier=np.array([r.carrier for r in rows], dtype=np.float64),
+                mean_power=np.array([r.mean_power for r in rows], dtype=np.float64),
+                coherence=np.array([r.coherence for r in rows], dtype=np.float64),
+                outputs=np.array([r.outputs for r in rows], dtype=np.uint64))
 
 
 # --------------------------------------------------------------------------

@@ -168,7 +168,7 @@ int clean_chain_reserve(ookd_rx *rx, int dev, uint64_t edge_capacity, uint32_t c
         c->serial = 0;
         c->kernel_ms = 0.0f;
         c->counts_pending = false;
-        for (EdgePassId id : {kEdgePassCleanPulse, kEdgePassCleanSymbol, kEdgePassCleanLevels, kEdgePassCleanBursts}) {
+        for (EdgePassId id : {kEdgePassCleanPulse, kEdgePassCleanSymbol, kEdgePassCleanLevels, kEdgePassCleanBursts, kEdgePassCleanMoments}) {
             if (EdgePass *reader = ookd_rx_edge_pass(rx, id).get()) {
                 reader->serial = 0;
                 reader->kernel_ms = 0.0f;
@@ -255,7 +255,7 @@ int ookd_rx_clean_edges(ookd_rx *rx, uint64_t min_on, uint64_t min_off) {
     }
     if (ctx->serial == run.serial && ctx->min_on == min_on && ctx->min_off == min_off) return OOKD_OK;
     // another list from here on: what the clean readers keep is about the one before
-    for (EdgePassId id : {kEdgePassCleanPulse, kEdgePassCleanSymbol, kEdgePassCleanLevels, kEdgePassCleanBursts}) {
+    for (EdgePassId id : {kEdgePassCleanPulse, kEdgePassCleanSymbol, kEdgePassCleanLevels, kEdgePassCleanBursts, kEdgePassCleanMoments}) {
         if (EdgePass *reader = ookd_rx_edge_pass(rx, id).get()) {
             reader->serial = 0;
             reader->kernel_ms = 0.0f;

@@ -577,6 +577,11 @@ struct SurveyParams {
 // LDS offsets of `p` and returns the dynamic LDS size through *lds_bytes.  tap_floats: floats per tap in the
 // workgroup's LDS copy of the taps (2 for the tuned survey's pairs).
 uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes, uint32_t tap_floats = 1);
+// The same for a pass that also needs the output in front of every tile and keeps the last level in LDS (the pulse
+// moments, run_moments.hip): the level buffers hold the slices of tile + 1 outputs, the last level's among them, and
+// `table_bytes` of the pass's own storage lie at lds_hist_off in the place of the histograms.  The tile may come out
+// smaller than survey_tile's for the same filter.
+uint32_t survey_tile_lag(SurveyParams &p, size_t *lds_bytes, uint32_t tap_floats, size_t table_bytes);
 // ctaps == null: the untuned survey, real taps from p.taps.  Otherwise the tuned survey in the contract's order for
 // any shape (at least one stage), its complex taps from ctaps (below).
 hipError_t launch_survey(const SurveyParams &p, const float *ctaps, uint32_t num_captures, size_t lds_bytes,

@@ -181,6 +181,46 @@ uint32_t survey_tile(SurveyParams &p, size_t *lds_bytes, uint32_t tap_floats) {
     return 0;
 }
 
+uint32_t survey_tile_lag(SurveyParams &p, size_t *lds_bytes, uint32_t tap_floats, size_t table_bytes) {
+    uint64_t num_taps = 0;
+    for (uint32_t s = 0; s < p.num_stages; ++s) num_taps += p.stage[s].ntaps;
+    if (num_taps * tap_floats * sizeof(float) > kSurveyLdsBudget) return 0;
+    const size_t taps_bytes = (size_t)((num_taps * tap_floats + 3) & ~3ull) * sizeof(float);
+    table_bytes = (table_bytes + 15u) & ~(size_t)15u;
+    for (uint32_t tile = 1024; tile >= 1; tile >>= 1) {
+        int64_t a[kMaxStages + 1];
+        uint32_t n[kMaxStages + 1];
+        uint64_t even = 0, odd = 0;
+        bool fits = true;
+        if (p.num_stages) {
+            // tile + 1 outputs: the one in front of the tile, which the first lag product reads
+            uint64_t len = (uint64_t)tile + 1u;
+            for (int s = (int)p.num_stages - 1; s >= 0 && fits; --s) {
+                len = (uint64_t)p.stage[s].decim * (len - 1) + p.stage[s].ntaps;
+                fits = len * sizeof(float2) <= kSurveyLdsBudget;
+            }
+            if (!fits) continue;
+            survey_levels(p, 0, tile + 1u, a, n);
+            for (uint32_t s = 0; s <= p.num_stages; ++s) {      // (the last level is kept as well: s = num_stages)
+                uint64_t &m = (s & 1) ? odd : even;
+                if (n[s] > m) m = n[s];
+            }
+        }
+        even = (even + 1) & ~1ull;
+        odd = (odd + 1) & ~1ull;
+        const size_t total = (size_t)(even + odd) * sizeof(float2) + table_bytes + taps_bytes;
+        if (total > kSurveyLdsBudget) continue;
+        p.tile = tile;
+        p.lds_b_off = (uint32_t)even;
+        p.lds_hist_off = (uint32_t)((even + odd) * sizeof(float2));
+        p.lds_taps_off = p.lds_hist_off + (uint32_t)table_bytes;
+        p.num_taps = (uint32_t)num_taps;
+        if (lds_bytes) *lds_bytes = total;
+        return tile;
+    }
+    return 0;
+}
+
 hipError_t survey_device_cus(int *cus) {
     int dev = 0;
     const hipError_t e = hipGetDevice(&dev);
