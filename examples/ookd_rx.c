@@ -11,7 +11,7 @@
  *       -Lookiedokie_amd/lib -lookiedokie_amd -Wl,-rpath,$PWD/ookiedokie_amd/lib
  *
  * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] [--levels] [--carriers]
- *         [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>]]
+ *         [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>] [--burst-carriers]]
  *         <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]
  *
  * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
@@ -53,6 +53,13 @@
  * are at most --burst-gap-us (default 20000) form one burst, which begins --burst-pre-us (default 500) in front of
  * its first rise and ends --burst-post-us (default 19500) behind its last fall; the gap is raised to pre + post when
  * it is given smaller.  Of the list the state machine decoded, as with --levels.  stdout is what it is without the option.
+ *
+ * --burst-carriers (with --bursts): a Welch spectrum of every burst of that table is summed on the GPU
+ * (ookd_rx_burst_spectra) and ookd_suggest_burst_carriers groups the bursts by their peak bin -- which transmitter
+ * keyed when, for a capture without a filter and a threshold above the noise of the whole band.  stderr gets a line
+ * `burst carrier <k>: <Hz> Hz, <bursts> bursts, <frames> frames` per carrier and a line
+ * `burst <first_sample> <num_samples> <carrier Hz|none> <share>` per burst, share = peak / (total - DC bins).  The
+ * files and stdout are what they are without the option.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -84,7 +91,7 @@ int main(int argc, char **argv)
 {
     /* --threshold <value>|auto is taken out of argv; what is left is positional, as before */
     float threshold = 0.1f;                 /* ookiedokie_cfg.h default */
-    int threshold_auto = 0, tune_auto = 0, bad_option = 0, levels = 0, carriers = 0;
+    int threshold_auto = 0, tune_auto = 0, bad_option = 0, levels = 0, carriers = 0, burst_carriers = 0;
     double tune_hz = 0.0, min_on_us = 0.0, min_off_us = 0.0;
     double burst_pre_us = 500.0, burst_post_us = 19500.0, burst_gap_us = 20000.0;
     const char *bursts_path = NULL;
@@ -123,15 +130,21 @@ int main(int argc, char **argv)
             levels = 1;
         } else if (!strcmp(argv[i], "--carriers")) {
             carriers = 1;
+        } else if (!strcmp(argv[i], "--burst-carriers")) {
+            burst_carriers = 1;
         } else {
             argv[kept++] = argv[i];
         }
     }
     argc = kept;
+    if (burst_carriers && !bursts_path) {
+        fprintf(stderr, "%s: --burst-carriers needs --bursts <file>: it is the spectra of that burst table\n", argv[0]);
+        return EXIT_FAILURE;
+    }
     if (argc < 5 || bad_option) {
         fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] "
-                        "[--levels] [--carriers] [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>]] "
-                        "<capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
+                        "[--levels] [--carriers] [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>] "
+                        "[--burst-carriers]] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
                 argv[0]);
         return EXIT_FAILURE;
     }
@@ -169,6 +182,8 @@ int main(int argc, char **argv)
     ookd_run_moment *moments = NULL;
     ookd_message_carrier *sent = NULL;
     ookd_burst *bursts = NULL;
+    ookd_burst_spectrum *spectra = NULL;
+    int32_t *carrier_of = NULL;
     void *cut = NULL;
     char *idx_path = NULL;
 
@@ -400,10 +415,40 @@ int main(int argc, char **argv)
                         "copy %.3f ms)\n", (unsigned long long) bi.total_samples, (unsigned long long) n,
                 (unsigned long long) nb, (unsigned long long) pre, (unsigned long long) post, (unsigned long long) max_gap,
                 ookd_rx_bursts_kernel_ms(rx), ookd_rx_burst_copy_kernel_ms(rx));
+        if (burst_carriers) {               /* a spectrum per burst of that table, and whose burst is whose */
+            ookd_burst_carrier found[16];
+            uint32_t count = 0;
+            uint64_t ns = 0;
+            spectra = malloc((size_t) (nb + 1) * sizeof *spectra);
+            carrier_of = malloc((size_t) (nb + 1) * sizeof *carrier_of);
+            if (!spectra || !carrier_of) goto out;
+            if (ookd_rx_burst_spectra(rx, 0, 0) != 0 || ookd_rx_get_burst_spectra(rx, 0, spectra, nb, &ns) != 0 || ns != nb) {
+                fail("ookd_rx_burst_spectra");
+                goto out;
+            }
+            if (ookd_suggest_burst_carriers(spectra, nb, 0.0, 0, found, 16, &count, carrier_of) != 0) {
+                fail("ookd_suggest_burst_carriers");
+                goto out;
+            }
+            for (uint32_t k = 0; k < count; ++k)
+                fprintf(stderr, "burst carrier %u: %.6g Hz, %llu bursts, %llu frames\n", k, found[k].nu * (double) rate,
+                        (unsigned long long) found[k].bursts, (unsigned long long) found[k].frames);
+            for (uint64_t b = 0; b < nb; ++b) {
+                const double rest = spectra[b].total_power - spectra[b].dc_power;
+                char hz[32];
+                if (carrier_of[b] >= 0) snprintf(hz, sizeof hz, "%.6g", found[carrier_of[b]].nu * (double) rate);
+                else snprintf(hz, sizeof hz, "none");
+                fprintf(stderr, "burst %llu %llu %s %.4f\n", (unsigned long long) bursts[b].first_sample,
+                        (unsigned long long) bursts[b].num_samples, hz, rest > 0.0 ? spectra[b].peak_power / rest : 0.0);
+            }
+            fprintf(stderr, "burst spectra: %.3f ms\n", ookd_rx_burst_spectra_kernel_ms(rx));
+        }
     }
     status = EXIT_SUCCESS;
 
 out:
+    free(carrier_of);
+    free(spectra);
     free(idx_path);
     free(cut);
     free(bursts);

@@ -1751,6 +1751,158 @@ float ookd_rx_bursts_kernel_ms(const ookd_rx *rx);
 float ookd_rx_burst_copy_kernel_ms(const ookd_rx *rx);
 
 /* ------------------------------------------------------------------------
+ * Burst spectra: a Welch spectrum and the carrier of every burst of the burst
+ * table, on the GPU -- which transmitter keyed when in a wide-band capture.
+ * ookd_spectrum_* sums over the whole capture: it names the carriers, not the
+ * bursts they belong to, and a transmitter's ratio to the median falls with
+ * its duty cycle.  Here a context without a filter (threshold on |x|^2) cuts
+ * every transmitter's bursts, each burst gets its own spectrum, and the host
+ * rule ookd_suggest_burst_carriers groups the bursts by their peak bin.
+ *
+ * The contract.  Take capture (or carrier list) c and the burst table that
+ * ookd_rx_bursts last made for this run: the raw or the clean form, whichever
+ * was last called.  With no table the call is OOKD_ERR_ARG.
+ *   - Burst b has first_sample, num_samples and F_b = floor(num_samples / 1024)
+ *     whole frames; frame f of burst b is capture samples
+ *     [first_sample + 1024 f, first_sample + 1024 f + 1024).  Nothing is padded
+ *     and nothing outside the burst is read; the ragged rest behind the last
+ *     whole frame is not counted.
+ *   - Unpack, window, transform and |X|^2 are exactly those of ookd_spectrum_*
+ *     (v / 2048, 16 v for the 8-bit formats first, periodic Hann, FFT order,
+ *     the sign convention of ookd_tune.nu).
+ *   - power_b[k] = sum_f |X_{b,f}[k]|^2.  fp32 inside a frame, at most 32 frames
+ *     in fp32 between folds into double, double beyond: the spectrum section's
+ *     budget, so its bound holds per burst with S and E taken over that burst,
+ *         |power_b[k] - S_b[k]| <= 2 EPS sqrt(S_b[k] E_b) + EPS^2 E_b + EPS S_b[k],
+ *     EPS = OOKD_SPECTRUM_EPS.
+ *   - Per burst one ookd_burst_spectrum.  A constant through the periodic Hann
+ *     window lands on bins -1, 0, +1 exactly: those three are set apart as
+ *     dc_power = (power_b[1023] + power_b[0]) + power_b[1], and the peak is the
+ *     largest power_b[k] over k = 2 .. 1022, ties going to the lowest k.
+ *     peak_bin and peak_power are exact functions of the power_b[] this library
+ *     computed: power[peak_bin] == peak_power bit for bit, with power[] from
+ *     ookd_rx_burst_spectrum.  total_power is within 1024 * 2^-53 (relative) of
+ *     the float64 sum of that power_b[].  With frames = 0 everything is 0.
+ *   - The keyed spectrum of the capture is an ookd_spectrum_result with
+ *     frames = sum_b F_b and power[k] = sum_b power_b[k]: the Welch spectrum of
+ *     the keyed part alone, which ookd_suggest_carriers takes unchanged.  It has
+ *     the same kind of bound, with S and E over all bursts.
+ *   - No floating-point atomics, no workgroup waits for another, every sum has
+ *     a fixed order: two calls with the same arguments on the same run return
+ *     bitwise identical results.  The order depends on span_frames; results at
+ *     different spans agree within the bound, not bit for bit.
+ *
+ * span_frames.  The cut's coordinate offset_b + 1024 f orders all frames of a
+ * capture; workgroup g takes the frames whose coordinate lies in
+ * [g S 1024, (g + 1) S 1024), S = span_frames, so there are
+ * spans = ceil(total / (1024 S)) workgroups.  A burst whose frames lie in more
+ * than one span leaves a row of 1024 doubles per span, at most two rows per
+ * span; a second kernel adds them in span order.  partial_rows = 2 spans rows
+ * of 8 KiB are kept, capped at 64 MiB (8192 rows), beside 8 KiB per span for
+ * the keyed spectrum.  span_frames must be 0 or a power of two >= 32, anything
+ * else is OOKD_ERR_ARG; 0 takes the smallest that fits the cap: 32 for every
+ * cut of up to 2^27 samples.  A span whose rows exceed the cap is
+ * OOKD_ERR_CAPACITY and the error text names the smallest span that fits.
+ * Buffers are grown, never shrunk, and freed with the context.
+ *
+ * A by-product of a finished run like ookd_rx_bursts: nothing is launched or
+ * allocated until it is asked for, it refuses what ookd_rx_pulse_hist refuses
+ * with the same codes, one capture per call.  The same run, table, capture and
+ * span_frames launch nothing; a new run, a new table (other margins, another
+ * cleaned list) or another span makes a new result.  The getters are
+ * OOKD_ERR_ARG while the last run's table has no result for that capture.  The
+ * capture is read again through the pointer the run recorded: the residency
+ * rule is that of ookd_rx_copy_bursts_*.  Frames are loaded sample by sample
+ * (a burst's first sample is rarely 16-byte aligned), so no byte outside a
+ * frame is touched: the capture's allocation may end at n.
+ *
+ * ookd_rx_burst_spectrum returns all 1024 doubles of one burst: the same
+ * kernels over that burst alone, at the span the summaries were made with, so
+ * it is the power_b[] the summary was taken from.  It needs the summaries of
+ * that capture first (OOKD_ERR_ARG otherwise, and for burst >= num_bursts).
+ *
+ * Limits: this needs the signal above DC plus noise in the full band (with a
+ * receiver's DC term a quarter-level signal may sit below the threshold that
+ * clears it).  Not part of it: a spectrum per on-run, other frame lengths,
+ * overlapping or zero-padded frames, more than one peak per burst (two
+ * transmitters keying at once show as a lower share), interpolated peaks, shard
+ * and pipelined runs, all captures of a batch in one launch.
+ * ---------------------------------------------------------------------- */
+typedef struct ookd_burst_spectrum {
+    uint64_t frames;                /* F_b                                             */
+    double total_power;             /* sum over all k of power_b[k]                    */
+    double dc_power;                /* power_b[1023] + power_b[0] + power_b[1]         */
+    double peak_power;              /* the largest power_b[k] over k in 2 .. 1022      */
+    uint32_t peak_bin;              /* its k; ties go to the lowest k; 0 when frames = 0 */
+    uint32_t reserved;
+} ookd_burst_spectrum;
+
+typedef struct ookd_burst_spectra_info {
+    uint64_t num_bursts;
+    uint64_t total_frames;          /* sum of F_b                                      */
+    uint64_t spans;                 /* workgroups of the first kernel                  */
+    uint64_t partial_rows;          /* rows of 1024 doubles kept for bursts across spans: 2 spans */
+    uint32_t span_frames;           /* S as used                                       */
+    uint32_t flags;                 /* OOKD_BURSTS_* of the table that was read        */
+    float reduce_kernel_ms;         /* of kernel_ms: the second kernel and the keyed sum */
+    uint32_t reserved;
+} ookd_burst_spectra_info;
+
+#define OOKD_BURST_SPECTRA_MIN_SPAN 32
+#define OOKD_BURST_SPECTRA_MAX_ROWS 8192        /* 64 MiB of partial rows */
+
+int ookd_rx_burst_spectra(ookd_rx *rx, uint32_t capture, uint32_t span_frames /* 0 = chosen */);
+/* the ookd_rx_get_edges convention: *num_bursts receives the count, at most
+ * `capacity` entries are stored, out may be NULL */
+int ookd_rx_get_burst_spectra(const ookd_rx *rx, uint32_t capture, ookd_burst_spectrum *out,
+                              uint64_t capacity, uint64_t *num_bursts);
+int ookd_rx_get_keyed_spectrum(const ookd_rx *rx, uint32_t capture, ookd_spectrum_result *out);
+int ookd_rx_get_burst_spectra_info(const ookd_rx *rx, uint32_t capture, ookd_burst_spectra_info *out);
+int ookd_rx_burst_spectrum(ookd_rx *rx, uint32_t capture, uint64_t burst, ookd_spectrum_result *out);
+/* HIP-event time of the last ookd_rx_burst_spectra pass about the last run (0: none, or nothing to launch) */
+float ookd_rx_burst_spectra_kernel_ms(const ookd_rx *rx);
+/* The span ookd_rx_burst_spectra takes for a cut of total_samples with span_frames = 0, and the check it makes
+ * of a given one (host only): OOKD_OK and *span_used, OOKD_ERR_ARG, or OOKD_ERR_CAPACITY. */
+int ookd_burst_spectra_span(uint64_t total_samples, uint32_t span_frames, uint32_t *span_used);
+
+/* Carriers of a burst table's spectra, pure host code (no GPU needed).  The
+ * rule, a contract:
+ *   1. Burst b qualifies when frames >= 1, total_power - dc_power > 0 and
+ *      peak_power >= min_share * (total_power - dc_power).
+ *   2. weight[k] = the sum of peak_power over the qualifying bursts with
+ *      peak_bin = k, added in burst order.
+ *   3. Repeat, as ookd_suggest_carriers does: take the live bin of largest
+ *      weight, ties going to the lowest k; stop when that weight is not > 0 or
+ *      `capacity` carriers have been emitted; emit it -- its members are the
+ *      qualifying bursts whose peak_bin lies within circular distance
+ *      <= min_spacing_bins of it and is still live -- and kill those bins.
+ *   4. Output is in decreasing weight.  carrier_of_burst[b] is the index in out,
+ *      or -1 for a burst that does not qualify or was not reached before
+ *      `capacity`.
+ * A carrier's bursts and frames count its members, power is the sum of their
+ * peak_power in burst order; nu is the centre of the emitted bin.
+ * OOKD_BURST_MIN_SHARE, 1/8 of the power outside the DC bins: a tone on a bin
+ * centre keeps 2/3 of its power in the peak bin under Hann, a tone midway
+ * between two bins 0.48; the largest of 1021 bins of one frame of white noise
+ * holds about ln(1021) / 1021 ~ 0.007 of the total, and P(one bin > 1/8 of the
+ * total) is of the order e^-127.
+ * 0, or OOKD_ERR_ARG for NULL s with num_bursts > 0, NULL count, NULL out with
+ * capacity > 0, a negative or NaN min_share, or a peak_bin >= 1024. */
+typedef struct ookd_burst_carrier {
+    double nu;                      /* ookd_spectrum_bin_nu of the bin                 */
+    int32_t bin;                    /* -512 .. 511                                     */
+    uint32_t reserved;
+    uint64_t bursts, frames;        /* members and their frames                        */
+    double power;                   /* sum of the members' peak_power                  */
+} ookd_burst_carrier;
+#define OOKD_BURST_MIN_SHARE 0.125
+int ookd_suggest_burst_carriers(const ookd_burst_spectrum *s, uint64_t num_bursts,
+                                double min_share /* 0 = OOKD_BURST_MIN_SHARE */,
+                                uint32_t min_spacing_bins /* 0 = OOKD_CARRIER_MIN_SPACING */,
+                                ookd_burst_carrier *out, uint32_t capacity, uint32_t *count,
+                                int32_t *carrier_of_burst /* [num_bursts] or NULL; -1 = none */);
+
+/* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout
  * text.  Replaces formatter_data_to_keyval
  * (src/formatter.c:715-739, field rules :425-573), rx_print

@@ -32,6 +32,8 @@ here                              reference (OOKiedokie ``src/``)
 ``Receiver.message_carriers``     pulse, and which transmitter sent a message
 ``Receiver.bursts`` /             ``--rx-rec`` writes everything: the keyed
 ``Receiver.burst_samples``        stretches of a capture alone, cut on the GPU
+``Receiver.burst_spectra`` /      nothing: a spectrum and the carrier of every
+``suggest_burst_carriers``        burst -- which transmitter keyed when
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -252,7 +254,28 @@ class BurstInfo(C.Structure):
                 ("sample_bytes", C.c_uint32), ("tile_edges", C.c_uint32), ("decimation", C.c_uint32)]
 
 
+class BurstSpectrum(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("total_power", C.c_double), ("dc_power", C.c_double),
+                ("peak_power", C.c_double), ("peak_bin", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BurstSpectraInfo(C.Structure):
+    _fields_ = [("num_bursts", C.c_uint64), ("total_frames", C.c_uint64), ("spans", C.c_uint64),
+                ("partial_rows", C.c_uint64), ("span_frames", C.c_uint32), ("flags", C.c_uint32),
+                ("reduce_kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+class BurstCarrierStruct(C.Structure):
+    _fields_ = [("nu", C.c_double), ("bin", C.c_int32), ("reserved", C.c_uint32), ("bursts", C.c_uint64),
+                ("frames", C.c_uint64), ("power", C.c_double)]
+
+
 BURSTS_CLEAN = 1                        # OOKD_BURSTS_CLEAN
+BURST_MIN_SHARE = 0.125                 # OOKD_BURST_MIN_SHARE
+BURST_SPECTRA_MIN_SPAN = 32             # OOKD_BURST_SPECTRA_MIN_SPAN
+BURST_SPECTRA_MAX_ROWS = 8192           # OOKD_BURST_SPECTRA_MAX_ROWS
+BURST_SPECTRUM_DTYPE = np.dtype([("frames", "<u8"), ("total_power", "<f8"), ("dc_power", "<f8"), ("peak_power", "<f8"),
+                                 ("peak_bin", "<u4"), ("reserved", "<u4")])
 BURST_FIELDS = tuple(name for name, _ in Burst._fields_)
 
 
@@ -482,6 +505,15 @@ _PROTOTYPES = {
     "ookd_rx_copy_bursts_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "ookd_rx_bursts_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_rx_burst_copy_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_rx_burst_spectra": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "ookd_rx_get_burst_spectra": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_get_keyed_spectrum": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SpectrumResult)]),
+    "ookd_rx_get_burst_spectra_info": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BurstSpectraInfo)]),
+    "ookd_rx_burst_spectrum": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(SpectrumResult)]),
+    "ookd_rx_burst_spectra_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_burst_spectra_span": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ookd_suggest_burst_carriers": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_uint32, C.c_void_p, C.c_uint32,
+                                              C.POINTER(C.c_uint32), C.c_void_p]),
     "ookd_device_from_suggestion": (C.c_void_p, [C.POINTER(DeviceSuggestion), C.c_uint32]),
     "ookd_device_suggestion_json": (C.c_size_t, [C.POINTER(DeviceSuggestion), C.c_char_p, C.c_char_p, C.c_size_t]),
     "sdr_hip_file_init": (C.c_void_p, [C.c_void_p]),
@@ -1363,6 +1395,46 @@ class Receiver:
         """HIP-event time of the last `burst_samples` / `burst_samples_device` kernel about the last run."""
         return float(lib().ookd_rx_burst_copy_kernel_ms(self._h))
 
+    # -- burst spectra ---------------------------------------------------------------
+    def burst_spectra(self, capture: int = 0, span_frames: int = 0) -> dict:
+        """A Welch spectrum of every burst of the table `bursts` last made for this run, summed on the GPU
+        (ookd_rx_burst_spectra): per burst the arrays frames, total_power, dc_power (bins -1, 0, +1), peak_power and
+        peak_bin (the largest of bins 2 .. 1022), and num_bursts, total_frames, span_frames, spans, partial_rows,
+        flags, reduce_kernel_ms.  The input of `suggest_burst_carriers`.  The same run, table, capture and span
+        launch nothing.  span_frames: 0, or a power of two >= 32 (the header has the rule)."""
+        _check(lib().ookd_rx_burst_spectra(self._h, capture, int(span_frames)))
+        info = BurstSpectraInfo()
+        _check(lib().ookd_rx_get_burst_spectra_info(self._h, capture, C.byref(info)))
+        nb = int(info.num_bursts)
+        table = np.zeros(max(nb, 1), dtype=BURST_SPECTRUM_DTYPE)
+        n = C.c_uint64(0)
+        _check(lib().ookd_rx_get_burst_spectra(self._h, capture, table.ctypes.data, nb, C.byref(n)))
+        d = dict(num_bursts=nb, total_frames=int(info.total_frames), span_frames=int(info.span_frames),
+                 spans=int(info.spans), partial_rows=int(info.partial_rows), flags=int(info.flags),
+                 reduce_kernel_ms=float(info.reduce_kernel_ms))
+        for name in ("frames", "total_power", "dc_power", "peak_power", "peak_bin"):
+            d[name] = table[name][:nb].copy()
+        return d
+
+    def burst_spectrum(self, burst: int, capture: int = 0) -> np.ndarray:
+        """power_b[1024] (float64, FFT order) of one burst: the sums its entry of `burst_spectra` was taken from,
+        made again by the same kernels over that burst alone (ookd_rx_burst_spectrum).  After `burst_spectra`."""
+        r = SpectrumResult()
+        _check(lib().ookd_rx_burst_spectrum(self._h, capture, int(burst), C.byref(r)))
+        return np.frombuffer(bytes(r.power), dtype=np.float64).copy()
+
+    def keyed_spectrum(self, capture: int = 0) -> SpectrumResult:
+        """The Welch spectrum of the keyed part of the capture alone -- frames and power summed over its bursts
+        (ookd_rx_get_keyed_spectrum); `suggest_carriers` takes it.  After `burst_spectra`."""
+        r = SpectrumResult()
+        _check(lib().ookd_rx_get_keyed_spectrum(self._h, capture, C.byref(r)))
+        return r
+
+    @property
+    def burst_spectra_kernel_ms(self) -> float:
+        """HIP-event time of the last `burst_spectra` pass about the last run; 0 while nobody has asked about it."""
+        return float(lib().ookd_rx_burst_spectra_kernel_ms(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_rx_destroy(self._h)
@@ -1407,6 +1479,44 @@ def find_bursts(edges, n_out: int, decimation: int, n: int, pre: int, post: int,
     for k, name in enumerate(BURST_FIELDS):
         d["burst_runs" if name == "num_runs" else name] = table[:, k].copy()
     return d
+
+
+# --------------------------------------------------------------------------
+# burst spectra
+
+@dataclass
+class BurstCarrier:
+    nu: float           # bin centre, cycles per input sample: Receiver(carriers=[...])
+    bin: int            # -512 .. 511
+    bursts: int         # members
+    frames: int         # and their frames
+    power: float        # the sum of their peak_power
+
+
+def burst_spectra_span(total_samples: int, span_frames: int = 0) -> int:
+    """The span `Receiver.burst_spectra` uses for a cut of total_samples (ookd_burst_spectra_span): span_frames itself,
+    or for 0 the smallest power of two >= 32 whose partial rows fit the workspace.  Raises as the call would."""
+    used = C.c_uint32(0)
+    _check(lib().ookd_burst_spectra_span(int(total_samples), int(span_frames), C.byref(used)))
+    return int(used.value)
+
+
+def suggest_burst_carriers(spectra, min_share: float = 0.0, min_spacing_bins: int = 0,
+                           capacity: int = 16) -> Tuple[List[BurstCarrier], np.ndarray]:
+    """ookd_suggest_burst_carriers over what `Receiver.burst_spectra` returns (a dict with the arrays frames,
+    total_power, dc_power, peak_power, peak_bin): (carriers in decreasing weight, carrier_of_burst as int32, -1 = none).
+    The rule is stated in the header.  Pure host code."""
+    nb = len(spectra["frames"])
+    table = np.zeros(max(nb, 1), dtype=BURST_SPECTRUM_DTYPE)
+    for name in ("frames", "total_power", "dc_power", "peak_power", "peak_bin"):
+        table[name][:nb] = np.asarray(spectra[name])
+    out = (BurstCarrierStruct * max(1, capacity))()
+    count = C.c_uint32(0)
+    of = np.full(max(nb, 1), -1, dtype=np.int32)
+    _check(lib().ookd_suggest_burst_carriers(table.ctypes.data if nb else None, nb, float(min_share), int(min_spacing_bins),
+                                             C.addressof(out) if capacity else None, int(capacity), C.byref(count),
+                                             of.ctypes.data))
+    return ([BurstCarrier(c.nu, c.bin, int(c.bursts), int(c.frames), c.power) for c in out[:count.value]], of[:nb].copy())
 
 
 # --------------------------------------------------------------------------
@@ -1805,6 +1915,8 @@ def suggest_carriers(power_or_result, min_ratio: float = 0.0, min_spacing_bins: 
     """ookd_suggest_carriers over 1024 powers, or over the (frames, power) pair `Spectrum.result` returns:
     (carriers in decreasing power, floor).  The rule is stated in the header.  Pure host code.  A bare power
     array counts as one frame unless `frames` says otherwise."""
+    if isinstance(power_or_result, SpectrumResult):         # (Receiver.keyed_spectrum)
+        power_or_result = (int(power_or_result.frames), np.frombuffer(bytes(power_or_result.power), dtype=np.float64))
     if isinstance(power_or_result, tuple):
         if frames is None:
             frames = int(power_or_result[0])

@@ -25,6 +25,7 @@ struct BurstCtx : EdgePass {
     // of run `serial`
     uint64_t pre = 0, post = 0, max_gap = 0;
     uint64_t asked = 0;                 // orders the raw and the clean form: the later ookd_rx_bursts call has the larger
+    uint64_t made = 0;                  // which table this is, of all that were made (BurstTableRef::made)
     uint32_t captures = 0;
     std::vector<uint64_t> host;         // [captures][kBurstWords]
     std::vector<BurstDev> table;        // the captures' entries one after the other
@@ -43,7 +44,7 @@ struct BurstCtx : EdgePass {
 
 namespace {
 
-uint64_t g_asked = 0;
+uint64_t g_asked = 0, g_made = 0;
 
 template <typename T>
 bool grow(T *&p, uint64_t want) {
@@ -102,6 +103,27 @@ BurstCtx *table_of(const char *who, const ookd_rx *rx, uint32_t capture, EdgeRun
     }
     return c;
 }
+
+}  // namespace
+
+namespace ookd {
+
+bool burst_table_ref(const char *who, const ookd_rx *rx, uint32_t capture, EdgeRun &run, BurstTableRef &out) {
+    const BurstCtx *c = table_of(who, rx, capture, run);
+    if (!c) return false;
+    const uint64_t *r = c->host.data() + (size_t)capture * kBurstWords;
+    out.num_bursts = c->table_at[capture + 1u] - c->table_at[capture];
+    out.total = r[kBurstWordTotal];
+    out.d_table = c->d_table ? c->d_table + burst_table_base(r[kBurstWordLo], capture) : nullptr;
+    out.table = c->table.data() + c->table_at[capture];
+    out.made = c->made;
+    out.clean = ookd_rx_edge_pass(const_cast<ookd_rx *>(rx), kEdgePassCleanBursts).get() == c;
+    return true;
+}
+
+}  // namespace ookd
+
+namespace {
 
 uint32_t cut_sample_bytes(const ookd_rx *rx) {
     RunLevelSource src;
@@ -305,6 +327,7 @@ int ookd_rx_bursts(ookd_rx *rx, uint64_t pre, uint64_t post, uint64_t max_gap, u
     ctx->post = post;
     ctx->max_gap = max_gap;
     ctx->asked = ++g_asked;
+    ctx->made = ++g_made;
     return OOKD_OK;
 }
 

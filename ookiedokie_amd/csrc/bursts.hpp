@@ -115,4 +115,18 @@ struct BurstCopyParams {
 // nothing to launch for total = 0
 hipError_t launch_burst_copy(const BurstCopyParams &p, hipStream_t stream);
 
+// ---- the table as another reader of it (burst_spectra.cpp) sees it ---------------------------------------------
+
+struct EdgeRun;
+struct BurstTableRef {
+    const BurstDev *d_table = nullptr;  // the capture's entries in device memory
+    const BurstDev *table = nullptr;    // and on the host
+    uint64_t num_bursts = 0, total = 0;
+    uint64_t made = 0;                  // counts the tables made: the same number is the same table
+    bool clean = false;                 // of the cleaned list
+};
+// The table the context's copy calls are about (the form ookd_rx_bursts was last called with for the last run) for
+// `capture`, and the last run; false + error without one.
+bool burst_table_ref(const char *who, const ookd_rx *rx, uint32_t capture, EdgeRun &run, BurstTableRef &out);
+
 }  // namespace ookd

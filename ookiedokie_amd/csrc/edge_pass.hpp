@@ -1,5 +1,5 @@
 // edge_pass.hpp -- what the readers of a finished run's edge list (pulses.cpp, symbols.cpp, run_levels.cpp, bursts.cpp,
-// run_moments.cpp) have in common on the host, and what they share with rx.cpp, the context whose edge list it is: the last run as a reader sees it, the
+// run_moments.cpp, burst_spectra.cpp) have in common on the host, and what they share with rx.cpp, the context whose edge list it is: the last run as a reader sees it, the
 // refusals, and the timed pass with its result buffer.  `who` names the entry point in the messages.  No device code:
 // the kernels' side is edge_list_dev.hpp.
 #pragma once
@@ -65,7 +65,9 @@ enum EdgePassId {
     kEdgePassCleanBursts = 8,
     kEdgePassMoments = 9,           // the pulse moments (run_moments.cpp) over the run's list, and over the cleaned one
     kEdgePassCleanMoments = 10,
-    kEdgePasses = 11
+    kEdgePassBurstSpectra = 11,     // the burst spectra (burst_spectra.cpp) of the raw burst table, and of the clean one
+    kEdgePassCleanBurstSpectra = 12,
+    kEdgePasses = 13
 };
 
 // The refusals every reader shares, after its own argument checks: fills `run`, then OOKD_OK, or OOKD_ERR_ARG (no

@@ -652,6 +652,9 @@ struct SpectrumParams {
     double *partial;            // [captures][groups][1024], every element written by the run
     double *power;              // [captures][1024]
 };
+// SpectrumParams' twiddle and window on the host, [1024] each: built in double, rounded once (spectrum.cpp); the
+// one builder of the tables spectrum.hip and burst_spectra.hip read
+void spectrum_tables(float2 *twiddle, float *window);
 // workgroups per capture for a run (0 when there is nothing to do): fills the device once
 uint32_t spectrum_groups(uint64_t frames, uint32_t num_captures, int cus);
 hipError_t launch_spectrum(const SpectrumParams &p, uint32_t num_captures, uint32_t groups, hipStream_t stream);

@@ -35,6 +35,25 @@ struct ookd_spectrum : ScanCtx {
     }
 };
 
+namespace ookd {
+
+// the tables, in double, rounded once: the angle is reduced to an exact multiple of 1/1024 turn first
+void spectrum_tables(float2 *tw, float *win) {
+    const double two_pi = 6.283185307179586476925286766559;
+    auto w1024 = [&](int m) {               // e^{-j 2 pi m / 1024}
+        const double a = two_pi * (double)(m % kSpecBins) / (double)kSpecBins;
+        return make_float2((float)std::cos(a), (float)-std::sin(a));
+    };
+    for (int m = 0; m < kSpecBins; ++m) win[m] = (float)(0.5 - 0.5 * std::cos(two_pi * (double)m / (double)kSpecBins));
+    for (int kj = 1; kj < 4; ++kj)          // the order the lanes read them (kernels.hpp, SpectrumParams::twiddle)
+        for (int i = 0; i < 4; ++i)
+            for (int L = 0; L < 64; ++L) tw[(kj - 1) * 256 + i * 64 + L] = w1024((4 * L + i) * kj);
+    for (int kt = 0; kt < 16; ++kt)
+        for (int s = 0; s < 16; ++s) tw[768 + 16 * kt + s] = w1024(4 * s * kt);
+}
+
+}  // namespace ookd
+
 extern "C" {
 
 double ookd_spectrum_bin_nu(uint32_t bin) {
@@ -96,20 +115,9 @@ ookd_spectrum *ookd_spectrum_create(int32_t hip_device, uint32_t sample_flags, u
         set_error("ookd_spectrum_create: cannot read the device's CU count");
         return nullptr;
     }
-    // the tables, in double, rounded once: the angle is reduced to an exact multiple of 1/1024 turn first
     std::vector<float2> tw(kSpecBins);
     std::vector<float> win(kSpecBins);
-    const double two_pi = 6.283185307179586476925286766559;
-    auto w1024 = [&](int m) {               // e^{-j 2 pi m / 1024}
-        const double a = two_pi * (double)(m % kSpecBins) / (double)kSpecBins;
-        return make_float2((float)std::cos(a), (float)-std::sin(a));
-    };
-    for (int m = 0; m < kSpecBins; ++m) win[m] = (float)(0.5 - 0.5 * std::cos(two_pi * (double)m / (double)kSpecBins));
-    for (int kj = 1; kj < 4; ++kj)          // the order the lanes read them (kernels.hpp, SpectrumParams::twiddle)
-        for (int i = 0; i < 4; ++i)
-            for (int L = 0; L < 64; ++L) tw[(kj - 1) * 256 + i * 64 + L] = w1024((4 * L + i) * kj);
-    for (int kt = 0; kt < 16; ++kt)
-        for (int s = 0; s < 16; ++s) tw[768 + 16 * kt + s] = w1024(4 * s * kt);
+    spectrum_tables(tw.data(), win.data());
     if (hipMalloc(reinterpret_cast<void **>(&s->d_twiddle), tw.size() * sizeof(float2)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&s->d_window), win.size() * sizeof(float)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&s->d_power), (size_t)max_captures * kSpecBins * sizeof(double)) !=
