@@ -12,6 +12,7 @@
  *
  * ookd_rx [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] [--levels] [--carriers]
  *         [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>] [--burst-carriers]]
+ *         [--baseband <file.cf32|.sc16q11>]
  *         <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]
  *
  * --threshold (anywhere on the line; default 0.1, the reference's --rx-threshold default): a number is used as
@@ -60,6 +61,14 @@
  * `burst carrier <k>: <Hz> Hz, <bursts> bursts, <frames> frames` per carrier and a line
  * `burst <first_sample> <num_samples> <carrier Hz|none> <share>` per burst, share = peak / (total - DC bins).  The
  * files and stdout are what they are without the option.
+ *
+ * --baseband <file>: after the messages, the filter's complex output over the same bursts is cut out on the GPU
+ * (ookd_rx_burst_baseband_host) and written to <file>: float32 pairs for a name ending in .cf32, int16 pairs for one
+ * ending in .sc16q11 -- which reads back as a capture at samplerate / decimation for a context without a filter; any
+ * other extension is refused.  <file>.idx gets one text line per burst, `first_output num_outputs offset`, in
+ * filter outputs.  With or without --bursts, and with the same --burst-*-us margins.  stderr names the cut's sample
+ * rate and where the carrier sits in it: a tuned filter is a band-pass, not a mixer.  stdout is what it is without the
+ * option.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -94,7 +103,8 @@ int main(int argc, char **argv)
     int threshold_auto = 0, tune_auto = 0, bad_option = 0, levels = 0, carriers = 0, burst_carriers = 0;
     double tune_hz = 0.0, min_on_us = 0.0, min_off_us = 0.0;
     double burst_pre_us = 500.0, burst_post_us = 19500.0, burst_gap_us = 20000.0;
-    const char *bursts_path = NULL;
+    const char *bursts_path = NULL, *baseband_path = NULL;
+    uint32_t baseband_format = OOKD_BASEBAND_CF32;
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--threshold")) {
@@ -126,6 +136,9 @@ int main(int argc, char **argv)
         } else if (!strcmp(argv[i], "--bursts")) {
             if (++i >= argc) { bad_option = 1; break; }
             bursts_path = argv[i];
+        } else if (!strcmp(argv[i], "--baseband")) {
+            if (++i >= argc) { bad_option = 1; break; }
+            baseband_path = argv[i];
         } else if (!strcmp(argv[i], "--levels")) {
             levels = 1;
         } else if (!strcmp(argv[i], "--carriers")) {
@@ -144,9 +157,18 @@ int main(int argc, char **argv)
     if (argc < 5 || bad_option) {
         fprintf(stderr, "usage: %s [--threshold <value>|auto] [--tune <hz>|auto] [--min-on-us <us>] [--min-off-us <us>] "
                         "[--levels] [--carriers] [--bursts <file> [--burst-pre-us <us>] [--burst-post-us <us>] [--burst-gap-us <us>] "
-                        "[--burst-carriers]] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
+                        "[--burst-carriers]] [--baseband <file.cf32|.sc16q11>] <capture.sc16q11|.cs8|.cu8> <device.json> <filter.json|none> <samplerate> [csv|pretty] [dig.csv]\n",
                 argv[0]);
         return EXIT_FAILURE;
+    }
+    if (baseband_path) {
+        const size_t len = strlen(baseband_path);
+        if (len >= 5 && !strcmp(baseband_path + len - 5, ".cf32")) baseband_format = OOKD_BASEBAND_CF32;
+        else if (len >= 8 && !strcmp(baseband_path + len - 8, ".sc16q11")) baseband_format = OOKD_BASEBAND_SC16Q11;
+        else {
+            fprintf(stderr, "%s: --baseband %s: the extension names the format, .cf32 or .sc16q11\n", argv[0], baseband_path);
+            return EXIT_FAILURE;
+        }
     }
     if (threshold_auto && (tune_auto || tune_hz != 0.0)) {
         char where[48];
@@ -182,6 +204,7 @@ int main(int argc, char **argv)
     ookd_run_moment *moments = NULL;
     ookd_message_carrier *sent = NULL;
     ookd_burst *bursts = NULL;
+    ookd_baseband_burst *basebands = NULL;
     ookd_burst_spectrum *spectra = NULL;
     int32_t *carrier_of = NULL;
     void *cut = NULL;
@@ -444,6 +467,45 @@ int main(int argc, char **argv)
             fprintf(stderr, "burst spectra: %.3f ms\n", ookd_rx_burst_spectra_kernel_ms(rx));
         }
     }
+    if (baseband_path) {                    /* the filter's output over the same bursts: the same table (made once) */
+        ookd_clean_info ci;
+        ookd_baseband_info info;
+        const double out_rate = (double) rate / (double) decimation;
+        const uint64_t pre = (uint64_t) (burst_pre_us * 1e-6 * out_rate), post = (uint64_t) (burst_post_us * 1e-6 * out_rate);
+        uint64_t max_gap = (uint64_t) (burst_gap_us * 1e-6 * out_rate), count = 0;
+        const size_t element = baseband_format == OOKD_BASEBAND_CF32 ? 8 : 4;
+        FILE *f;
+        if (max_gap < pre + post) max_gap = pre + post;
+        if (ookd_rx_bursts(rx, pre, post, max_gap, ookd_rx_get_clean_info(rx, 0, &ci) == 0 ? OOKD_BURSTS_CLEAN : 0) != 0) {
+            fail("ookd_rx_bursts");
+            goto out;
+        }
+        if (ookd_rx_get_baseband_info(rx, 0, &info) != 0) { fail("ookd_rx_get_baseband_info"); goto out; }
+        free(cut);
+        free(idx_path);
+        basebands = malloc((size_t) (info.num_bursts + 1) * sizeof *basebands);
+        cut = malloc((size_t) (info.total_outputs + 1) * element);
+        idx_path = malloc(strlen(baseband_path) + 5);
+        if (!basebands || !cut || !idx_path) goto out;
+        if (ookd_rx_get_baseband_bursts(rx, 0, basebands, info.num_bursts, &count) != 0) { fail("ookd_rx_get_baseband_bursts"); goto out; }
+        if (ookd_rx_burst_baseband_host(rx, 0, baseband_format, cut, info.total_outputs) != 0) { fail("ookd_rx_burst_baseband_host"); goto out; }
+        f = fopen(baseband_path, "wb");
+        if (!f || fwrite(cut, element, (size_t) info.total_outputs, f) != (size_t) info.total_outputs || fclose(f) != 0) {
+            fprintf(stderr, "%s: cannot write\n", baseband_path);
+            goto out;
+        }
+        strcpy(idx_path, baseband_path);
+        strcat(idx_path, ".idx");
+        f = fopen(idx_path, "w");
+        if (!f) { fprintf(stderr, "%s: cannot write\n", idx_path); goto out; }
+        for (uint64_t b = 0; b < count; ++b)
+            fprintf(f, "%llu %llu %llu\n", (unsigned long long) basebands[b].first_output,
+                    (unsigned long long) basebands[b].num_outputs, (unsigned long long) basebands[b].offset);
+        if (fclose(f) != 0) { fprintf(stderr, "%s: cannot write\n", idx_path); goto out; }
+        fprintf(stderr, "baseband: %llu outputs in %llu bursts at %.6g Hz, carrier at %.6g Hz (%.3f ms)\n",
+                (unsigned long long) info.total_outputs, (unsigned long long) count, out_rate, info.turn * out_rate,
+                ookd_rx_baseband_kernel_ms(rx));
+    }
     status = EXIT_SUCCESS;
 
 out:
@@ -452,6 +514,7 @@ out:
     free(idx_path);
     free(cut);
     free(bursts);
+    free(basebands);
     free(sent);
     free(moments);
     free(level);

@@ -1713,7 +1713,8 @@ int ookd_message_carriers(const uint64_t *edges, uint64_t E, uint64_t n_out,
  * The table pass reads the edge list only.
  *
  * Limits: shard and pipelined runs are refused; one cut per call (no batch of
- * captures in one launch); the cut is not resampled or filtered.
+ * captures in one launch); the cut is not resampled or filtered ("Burst
+ * basebands" hands back the filter's output over the same bursts).
  * ---------------------------------------------------------------------- */
 typedef struct ookd_burst {
     uint64_t first_sample;          /* input sample of the capture the burst begins at */
@@ -1901,6 +1902,122 @@ int ookd_suggest_burst_carriers(const ookd_burst_spectrum *s, uint64_t num_burst
                                 uint32_t min_spacing_bins /* 0 = OOKD_CARRIER_MIN_SPACING */,
                                 ookd_burst_carrier *out, uint32_t capacity, uint32_t *count,
                                 int32_t *carrier_of_burst /* [num_bursts] or NULL; -1 = none */);
+
+/* ------------------------------------------------------------------------
+ * Burst basebands: the filtered, decimated signal of every burst of the burst
+ * table -- the slicer's own input, transmitter by transmitter.  The raw cut of
+ * "Burst extraction" is wide-band input at the capture's rate: every carrier
+ * list of a carrier context gets the same samples, and behind a filter of
+ * decimation D it has D times the bytes that survive the channel filter.
+ * Here the cut is the complex filter output y over the bursts' outputs, in a
+ * carrier context through list k's own taps: transmitter k alone, at rate
+ * fs / D, ready for a second decoder or a file.
+ *
+ * The contract.  Take capture (or carrier list) c of the context's last run
+ * and the burst table the copy calls are about: the raw or the clean form,
+ * whichever ookd_rx_bursts was last called with for this run.  D, n_out and n
+ * are as in "Burst extraction".
+ *   - The baseband table.  Burst b of the burst table covers outputs
+ *     [first_output_b, first_output_b + num_outputs_b):
+ *         first_output_b = ceil(first_sample_b / D)
+ *         num_outputs_b  = ceil((first_sample_b + num_samples_b) / D) - first_output_b
+ *     offset_b = the sum of num_outputs over the capture's bursts before b, and
+ *     total_outputs = the sum over all of them.  In the terms of the burst rule
+ *     that is [min(lo_b, m), min(hi_b, m)) with m = min(n_out, ceil(n / D)): the
+ *     outputs whose newest input exists.  The table is a function of the burst
+ *     table and D alone; a burst in the padding behind n has 0 outputs and
+ *     stays in the table.  Bursts ascend and never overlap: two bursts with
+ *     outputs lie at least one output apart.
+ *   - The cut.  Element offset_b + i is y_j at output j = first_output_b + i:
+ *     the float32 complex filter output exactly as "Pulse moments" defines y_j
+ *     -- by the context's kind the untuned survey contract, the tuned survey
+ *     contract with the list's own nu and taps, or the unpacked sample without
+ *     a filter; inputs in front of the capture and at or beyond n are zero, the
+ *     latter never loaded.
+ *       OOKD_BASEBAND_CF32:     (re, im) as two float32, the bits of y_j.
+ *       OOKD_BASEBAND_SC16Q11:  (s(re), s(im)) as two int16; s(v) is v * 2048
+ *           formed in float32, a NaN taken as 0, clamped to [-32768, 32767],
+ *           rounded to the nearest integer with ties to even.  The file reads
+ *           back as an SC16Q11 capture at rate fs / D.
+ *   - turn = nu D - rint(nu D), in cycles per output sample: where the list's
+ *     carrier sits in the cut.  The tuned filter is a band-pass, not a mixer, so
+ *     nothing is derotated: y advances by 2 pi nu D per output.  0 for an
+ *     untuned context.  Informative, computed on the host in double.
+ *   - Everything is an exact function of the burst table and the capture's
+ *     bytes.  Every element has one writer: two calls leave the same bytes.
+ *   - tile_outputs, tiles_total and tiles_filtered are as at ookd_run_levels: a
+ *     tile is filtered when it holds an output of a burst.
+ *
+ * ookd_baseband_bursts is the table rule on the host, pure C++ (no GPU), over
+ * one burst table.  It follows the ookd_rx_get_edges convention: at most
+ * `capacity` entries are stored, out may be NULL, *total_outputs (may be NULL)
+ * receives the cut's length.  OOKD_ERR_ARG for a NULL table that is not empty,
+ * or D = 0.
+ *
+ * ookd_baseband_of is the contract on the host, pure C++ (no GPU), given the
+ * filter's output y[n_out][2] and a baseband table: out receives the cut in
+ * `format`.  OOKD_ERR_ARG for an unknown format, a NULL array that is not
+ * empty, or a table that reaches beyond n_out; OOKD_ERR_CAPACITY, with nothing
+ * written, when the table's outputs exceed capacity_outputs.
+ *
+ * The ookd_rx_* calls behave as ookd_rx_copy_bursts_* do.  They are about the
+ * table ookd_rx_bursts was last called with for the last run and are
+ * OOKD_ERR_ARG without one.  A by-product of a finished run: nothing is
+ * launched or allocated before the first ookd_rx_burst_baseband_* call, which
+ * builds the filter as the pulse levels' pass does and refuses, in the same
+ * words, a filter whose history does not fit the kernel's LDS window.
+ * ookd_rx_get_baseband_info and ookd_rx_get_baseband_bursts are host work over
+ * the burst table.  capacity_outputs < total_outputs is OOKD_ERR_CAPACITY and
+ * nothing is written; nothing at or beyond total_outputs elements is written
+ * either.  d_out must be aligned to its element, 8 bytes for CF32 and 4 for
+ * SC16Q11 (OOKD_ERR_ARG).  A cut of no outputs launches nothing.  The derived
+ * table is kept per burst table and made again when ookd_rx_bursts has made
+ * another.  ookd_rx_burst_baseband_host goes through a device buffer of exactly
+ * the cut's size that it allocates and frees.  ookd_rx_baseband_kernel_ms is
+ * the HIP-event time, on the context's stream, of the filtering kernel of the
+ * last such call about the last run (0: none, or nothing to launch);
+ * tiles_filtered is that kernel's count, 0 until it has run for this table.
+ * The capture is read again through the pointer the run recorded: the
+ * residency rule is that of ookd_rx_copy_bursts_*.
+ *
+ * Limits: no derotation to 0 Hz and no resampling to other rates (both need
+ * an oscillator and a contract for it); shard and pipelined runs are refused,
+ * as for every reader of the edge list; one capture per call.
+ * ---------------------------------------------------------------------- */
+enum {
+    OOKD_BASEBAND_CF32 = 0,
+    OOKD_BASEBAND_SC16Q11 = 1
+};
+
+typedef struct ookd_baseband_burst {
+    uint64_t first_output;          /* output of the capture the burst begins at */
+    uint64_t num_outputs;
+    uint64_t offset;                /* element of the cut the burst begins at  */
+} ookd_baseband_burst;
+
+typedef struct ookd_baseband_info {
+    uint64_t num_bursts;
+    uint64_t total_outputs;
+    uint64_t tiles_total;
+    uint64_t tiles_filtered;        /* of the last pass about this table, else 0 */
+    uint32_t tile_outputs;
+    uint32_t decimation;            /* D                                       */
+    double nu;                      /* the list's tuning, cycles per input sample */
+    double turn;                    /* nu D - rint(nu D), cycles per output    */
+} ookd_baseband_info;
+
+int ookd_baseband_bursts(const ookd_burst *table, uint64_t num_bursts, uint64_t D,
+                         ookd_baseband_burst *out, uint64_t capacity, uint64_t *total_outputs);
+int ookd_baseband_of(const float *y, uint64_t n_out, const ookd_baseband_burst *table,
+                     uint64_t num_bursts, uint32_t format, void *out, uint64_t capacity_outputs);
+int ookd_rx_get_baseband_info(ookd_rx *rx, uint32_t capture, ookd_baseband_info *out);
+int ookd_rx_get_baseband_bursts(ookd_rx *rx, uint32_t capture, ookd_baseband_burst *table,
+                                uint64_t capacity, uint64_t *num_bursts);
+int ookd_rx_burst_baseband_device(ookd_rx *rx, uint32_t capture, uint32_t format, void *d_out,
+                                  uint64_t capacity_outputs);
+int ookd_rx_burst_baseband_host(ookd_rx *rx, uint32_t capture, uint32_t format, void *out,
+                                uint64_t capacity_outputs);
+float ookd_rx_baseband_kernel_ms(const ookd_rx *rx);
 
 /* ------------------------------------------------------------------------
  * Host side of a decoded message: payload bits -> per-field text -> stdout

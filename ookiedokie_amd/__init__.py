@@ -34,6 +34,8 @@ here                              reference (OOKiedokie ``src/``)
 ``Receiver.burst_samples``        stretches of a capture alone, cut on the GPU
 ``Receiver.burst_spectra`` /      nothing: a spectrum and the carrier of every
 ``suggest_burst_carriers``        burst -- which transmitter keyed when
+``Receiver.burst_baseband``       nothing: the filtered, decimated signal of
+                                  every burst, transmitter by transmitter
 ================================  ==========================================
 
 There is no CPU fallback: the library is hand-written HIP for gfx950 and
@@ -270,6 +272,20 @@ class BurstCarrierStruct(C.Structure):
                 ("frames", C.c_uint64), ("power", C.c_double)]
 
 
+class BasebandBurst(C.Structure):
+    _fields_ = [("first_output", C.c_uint64), ("num_outputs", C.c_uint64), ("offset", C.c_uint64)]
+
+
+class BasebandInfo(C.Structure):
+    _fields_ = [("num_bursts", C.c_uint64), ("total_outputs", C.c_uint64), ("tiles_total", C.c_uint64),
+                ("tiles_filtered", C.c_uint64), ("tile_outputs", C.c_uint32), ("decimation", C.c_uint32),
+                ("nu", C.c_double), ("turn", C.c_double)]
+
+
+BASEBAND_CF32 = 0                       # OOKD_BASEBAND_CF32
+BASEBAND_SC16Q11 = 1                    # OOKD_BASEBAND_SC16Q11
+BASEBAND_FORMATS = {"cf32": BASEBAND_CF32, "sc16q11": BASEBAND_SC16Q11}
+BASEBAND_FIELDS = tuple(name for name, _ in BasebandBurst._fields_)
 BURSTS_CLEAN = 1                        # OOKD_BURSTS_CLEAN
 BURST_MIN_SHARE = 0.125                 # OOKD_BURST_MIN_SHARE
 BURST_SPECTRA_MIN_SPAN = 32             # OOKD_BURST_SPECTRA_MIN_SPAN
@@ -505,6 +521,13 @@ _PROTOTYPES = {
     "ookd_rx_copy_bursts_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "ookd_rx_bursts_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_rx_burst_copy_kernel_ms": (C.c_float, [C.c_void_p]),
+    "ookd_baseband_bursts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_baseband_of": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "ookd_rx_get_baseband_info": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(BasebandInfo)]),
+    "ookd_rx_get_baseband_bursts": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ookd_rx_burst_baseband_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "ookd_rx_burst_baseband_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "ookd_rx_baseband_kernel_ms": (C.c_float, [C.c_void_p]),
     "ookd_rx_burst_spectra": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "ookd_rx_get_burst_spectra": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ookd_rx_get_keyed_spectrum": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(SpectrumResult)]),
@@ -1435,6 +1458,53 @@ class Receiver:
         """HIP-event time of the last `burst_spectra` pass about the last run; 0 while nobody has asked about it."""
         return float(lib().ookd_rx_burst_spectra_kernel_ms(self._h))
 
+    # -- burst basebands -------------------------------------------------------------
+    def baseband_info(self, capture: int = 0) -> dict:
+        """The baseband table of the burst table `bursts` last made for this run (ookd_rx_get_baseband_info,
+        ookd_rx_get_baseband_bursts; host work, the rule is `baseband_bursts` at module level): num_bursts,
+        total_outputs, tiles_total, tiles_filtered (of the last `burst_baseband` about this table, else 0),
+        tile_outputs, decimation, nu, turn (where the carrier sits in the cut, cycles per output) and per burst the
+        uint64 arrays first_output, num_outputs, offset."""
+        info = BasebandInfo()
+        _check(lib().ookd_rx_get_baseband_info(self._h, capture, C.byref(info)))
+        nb = int(info.num_bursts)
+        table = np.zeros((max(nb, 1), len(BASEBAND_FIELDS)), dtype=np.uint64)
+        n = C.c_uint64(0)
+        _check(lib().ookd_rx_get_baseband_bursts(self._h, capture, table.ctypes.data, nb, C.byref(n)))
+        table = table[:nb]
+        d = {name: (float if name in ("nu", "turn") else int)(getattr(info, name)) for name, _ in BasebandInfo._fields_}
+        for k, name in enumerate(BASEBAND_FIELDS):
+            d[name] = table[:, k].copy()
+        return d
+
+    def burst_baseband(self, capture: int = 0, format: str = "cf32") -> np.ndarray:
+        """The filter's complex output over every burst of the table `bursts` last made for this run, burst after
+        burst (ookd_rx_burst_baseband_host): complex64 [total_outputs], or int16 [total_outputs, 2] for "sc16q11" --
+        element offset[b] + i is y at output first_output[b] + i, in a tuned or carrier context through the list's
+        own taps.  The rate is fs / decimation; nothing is derotated (`baseband_info`'s turn)."""
+        fmt = BASEBAND_FORMATS[format]
+        info = BasebandInfo()
+        _check(lib().ookd_rx_get_baseband_info(self._h, capture, C.byref(info)))
+        total = int(info.total_outputs)
+        out = np.zeros(max(total, 1), dtype=np.complex64) if fmt == BASEBAND_CF32 else np.zeros((max(total, 1), 2), dtype=np.int16)
+        _check(lib().ookd_rx_burst_baseband_host(self._h, capture, fmt, out.ctypes.data, total))
+        return out[:total]
+
+    def burst_baseband_device(self, capture: int, ptr: int, capacity: int, format: str = "cf32") -> int:
+        """The same cut into device memory at `ptr` (aligned to its element: 8 bytes for "cf32", 4 for "sc16q11") with
+        room for `capacity` outputs (ookd_rx_burst_baseband_device).  Returns total_outputs; nothing at or beyond it
+        is written."""
+        _check(lib().ookd_rx_burst_baseband_device(self._h, capture, BASEBAND_FORMATS[format], ptr, int(capacity)))
+        info = BasebandInfo()
+        _check(lib().ookd_rx_get_baseband_info(self._h, capture, C.byref(info)))
+        return int(info.total_outputs)
+
+    @property
+    def baseband_kernel_ms(self) -> float:
+        """HIP-event time of the filtering kernel of the last `burst_baseband` about the last run; 0 while nobody has
+        asked or there was nothing to launch."""
+        return float(lib().ookd_rx_baseband_kernel_ms(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().ookd_rx_destroy(self._h)
@@ -1479,6 +1549,49 @@ def find_bursts(edges, n_out: int, decimation: int, n: int, pre: int, post: int,
     for k, name in enumerate(BURST_FIELDS):
         d["burst_runs" if name == "num_runs" else name] = table[:, k].copy()
     return d
+
+
+# --------------------------------------------------------------------------
+# burst basebands
+
+def _baseband_rows(table) -> np.ndarray:
+    if isinstance(table, dict):
+        table = np.stack([np.asarray(table[k], dtype=np.uint64) for k in BASEBAND_FIELDS], axis=1)
+    return np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, len(BASEBAND_FIELDS))
+
+
+def baseband_bursts(table, decimation: int) -> dict:
+    """ookd_baseband_bursts: the baseband table of a burst table (`find_bursts`' or `Receiver.bursts`' dict, or a
+    uint64 array [B, 5]) -- per burst first_output = ceil(first_sample / D), num_outputs and offset as uint64 arrays,
+    and num_bursts, total_outputs.  Pure host code."""
+    if isinstance(table, dict):
+        table = np.stack([np.asarray(table["burst_runs" if k == "num_runs" else k], dtype=np.uint64) for k in BURST_FIELDS], axis=1)
+    t = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, len(BURST_FIELDS))
+    nb = t.shape[0]
+    out = np.zeros((max(nb, 1), len(BASEBAND_FIELDS)), dtype=np.uint64)
+    total = C.c_uint64(0)
+    _check(lib().ookd_baseband_bursts(t.ctypes.data if nb else None, nb, int(decimation), out.ctypes.data, nb, C.byref(total)))
+    d = dict(num_bursts=nb, total_outputs=int(total.value))
+    for k, name in enumerate(BASEBAND_FIELDS):
+        d[name] = out[:nb, k].copy()
+    return d
+
+
+def baseband_of(y, table, format: str = "cf32") -> np.ndarray:
+    """ookd_baseband_of: the burst basebands' contract on the host, given the filter's complex output y (complex64
+    [n_out] or float32 [n_out, 2]) and a baseband table (`baseband_bursts`' or `Receiver.baseband_info`'s dict, or a
+    uint64 array [B, 3]): complex64 [total], or int16 [total, 2] for "sc16q11".  Pure host code."""
+    fmt = BASEBAND_FORMATS[format]
+    y = np.asarray(y)
+    if np.iscomplexobj(y):
+        y = np.ascontiguousarray(y, dtype=np.complex64).view(np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1, 2)
+    t = _baseband_rows(table)
+    total = int(t[:, 1].sum())
+    out = np.zeros(max(total, 1), dtype=np.complex64) if fmt == BASEBAND_CF32 else np.zeros((max(total, 1), 2), dtype=np.int16)
+    _check(lib().ookd_baseband_of(y.ctypes.data if y.size else None, y.shape[0], t.ctypes.data if t.size else None,
+                                  t.shape[0], fmt, out.ctypes.data, total))
+    return out[:total]
 
 
 # --------------------------------------------------------------------------

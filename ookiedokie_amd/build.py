@@ -20,7 +20,8 @@ SOURCES = ["loaders.cpp", "front_plan.cpp", "rx.cpp", "synth.cpp", "stream_fir.c
            "formatter.cpp", "kernels.hip", "fir_mfma.hip", "fir_tuned.hip", "scan_ctx.cpp", "survey.cpp", "survey.hip",
            "survey_tuned.hip", "survey_carriers.hip", "survey_carriers_fir2.hip", "spectrum.cpp", "spectrum.hip", "edge_pass.cpp", "pulses.cpp", "pulses.hip",
            "symbols.cpp", "symbols.hip", "clean.cpp", "clean.hip", "run_levels.cpp", "run_levels.hip",
-           "bursts.cpp", "bursts.hip", "run_moments.cpp", "run_moments.hip", "burst_spectra.cpp", "burst_spectra.hip"]
+           "bursts.cpp", "bursts.hip", "run_moments.cpp", "run_moments.hip", "burst_spectra.cpp", "burst_spectra.hip",
+           "burst_baseband.cpp", "burst_baseband.hip"]
 ARCH = "gfx950"
 
 

@@ -1,5 +1,5 @@
 // edge_pass.hpp -- what the readers of a finished run's edge list (pulses.cpp, symbols.cpp, run_levels.cpp, bursts.cpp,
-// run_moments.cpp, burst_spectra.cpp) have in common on the host, and what they share with rx.cpp, the context whose edge list it is: the last run as a reader sees it, the
+// run_moments.cpp, burst_spectra.cpp, burst_baseband.cpp) have in common on the host, and what they share with rx.cpp, the context whose edge list it is: the last run as a reader sees it, the
 // refusals, and the timed pass with its result buffer.  `who` names the entry point in the messages.  No device code:
 // the kernels' side is edge_list_dev.hpp.
 #pragma once
@@ -67,7 +67,9 @@ enum EdgePassId {
     kEdgePassCleanMoments = 10,
     kEdgePassBurstSpectra = 11,     // the burst spectra (burst_spectra.cpp) of the raw burst table, and of the clean one
     kEdgePassCleanBurstSpectra = 12,
-    kEdgePasses = 13
+    kEdgePassBaseband = 13,         // the burst basebands (burst_baseband.cpp) of the raw burst table, and of the clean one
+    kEdgePassCleanBaseband = 14,
+    kEdgePasses = 15
 };
 
 // The refusals every reader shares, after its own argument checks: fills `run`, then OOKD_OK, or OOKD_ERR_ARG (no
